@@ -21,8 +21,19 @@ one frame overlaps the compute of the next.  The timed region still issues exact
 RCCL; fewer GPUs than ranks is an error, OLSR_BENCH_BACKEND=gloo shares devices for functional checks).  `--exchange
 {sparse,all_reduce,reduce_scatter}` picks how the shared-Gaussian gradients travel; sparse (default) exchanges only the rows
 that are non-zero on some rank, capacity-bound and without a host synchronisation.  The contract's K-step region is run
-`--repeats` times back to back (default: until the timed regions total `--min-timed-s` = 2 s): `value` is the median run,
+`--repeats` times back to back (default 1; with `--full`, until the timed regions total `--min-timed-s` = 2 s): `value` is the median run,
 `config.value_runs` lists all of them.  `--scene room` runs the same legs on the surface-structured map of scene.make_room_scene.
+
+A plain run (without `--full`) does only what the headline needs: set-up, the untimed set-up frames, the W warm-up steps,
+exactly K timed steps (one region; `--repeats` is 1 unless given), `--dump-outputs` if asked for, and the JSON line, whose
+`roofline` is then null.  `--full` adds everything below the headline: the K-step region repeated until `--min-timed-s`,
+the isolated, profiled, non-coherent, drop-in, bracket and config-4 legs, the workload statistics, the check of the
+multi-rank exchange and the CPU baseline.
+
+`--dump-outputs DIR` writes, after the timed region, what its last step computed — the forward's images, radii and
+n_touched, the gradient bucket, its densification statistics and max radii, dL_dtau_sum — as DIR/<name>.npy in float32:
+small arrays whole, the largest ones as a fixed seeded sample of their pixels / rows, 60 MB in all at most.  The inputs are
+seeded, so two builds given the same arguments can be compared array for array.
 
 Rank 0 prints ONE JSON line.  `non_coherent`: the camera changes every step.  `isolated` repeats the measurement with ONE frame in flight: there the
 intervals between the library's HIP events (recorded on the launch stream) ARE the kernel durations, whereas
@@ -149,6 +160,30 @@ def measured_valu_cycles():
     rows = json.load(open(path))["rows"]
     full = [r["cycles_per_inst_per_simd"] for r in rows if r["op"] in ("v_fma_f32", "v_mul_f32", "v_add_f32", "v_fmac_f32")]
     return (min(full) if full else None), os.path.basename(path)
+
+
+DUMP_BUDGET_BYTES = 60 * 2**20
+
+
+def dump_outputs(path, arrays):
+    """`arrays`: name -> tensor, each [items, ...] (pixels or Gaussians first).  Saved as path/<name>.npy in float32.  The
+    budget is filled smallest array first, each taking at most an even share of what is left: an array over its share keeps
+    a fixed seeded sample of its items (sorted indices of a randperm of seed 0), so equal shapes give equal samples."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = sorted(((k, v) for k, v in arrays.items() if v is not None and v.numel() > 0), key=lambda kv: kv[1].numel())
+    budget = DUMP_BUDGET_BYTES // 4
+    for i, (name, t) in enumerate(arrays):
+        share = budget // (len(arrays) - i)
+        t = t.detach()
+        if t.numel() > share:
+            rows = t.shape[0]
+            keep = max(1, share // (t.numel() // rows))
+            idx = torch.randperm(rows, generator=torch.Generator().manual_seed(0))[:keep].sort().values
+            t = t.index_select(0, idx.to(t.device))
+        a = t.float().cpu().numpy()
+        np.save(os.path.join(path, f"{name}.npy"), a)
+        budget -= a.size
 
 
 def percentiles(xs):
@@ -937,6 +972,8 @@ def views_mode(a, sc, dev, rank, world, dist):
     if dist is not None:
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     el = float(el.item())
+    if rank == 0 and a.dump_outputs:
+        dump_outputs(a.dump_outputs, params)   # the parameters after the last step's Adam update and all-gather
     if rank == 0:
         width = 11 + 3 * M + F
         print(json.dumps({
@@ -1012,10 +1049,16 @@ def main():
     ap.add_argument("--rank-view", default="", help="K,N[,arc]: with one rank, render what rank K of an N-GPU run renders instead of "
                                                     "the identity pose (the per-rank cost of a weak-scaling point); ',arc': "
                                                     "pose K of the N-pose arc of the mapping mode")
-    ap.add_argument("--repeats", type=int, default=0,
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline, every other leg: the repeated K-step region, isolated / profiled / non-coherent "
+                         "/ drop-in / bracket / config-4 legs, workload statistics, the exchange check and the CPU baseline")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed region, write what its last step computed as DIR/<name>.npy (float32, seeded "
+                         "sample of the largest arrays, 60 MB at most)")
+    ap.add_argument("--repeats", type=int, default=None,
                     help="how many times the contract's K-step region is run; the value is the median run (all in "
-                         "config.value_runs).  0 (default): as many as it takes for the timed regions to total --min-timed-s "
-                         "seconds (at least 5)")
+                         "config.value_runs).  Default 1, with --full 0: as many as it takes for the timed regions to total "
+                         "--min-timed-s seconds (at least 5)")
     ap.add_argument("--min-timed-s", type=float, default=2.0,
                     help="with --repeats 0: repeat the K-step region until the timed regions total this many seconds, so that "
                          "the GPU is visibly busy to an outside sampler (the K = 20 region alone lasts 9 ms)")
@@ -1032,8 +1075,11 @@ def main():
                          "repaired in two launches, exact by a device-side fall-back to the radix passes); the legs whose camera "
                          "changes every step run without, and the line reports the same-view rates without it as well")
     ap.add_argument("--setup-steps", type=int, default=40, help="untimed frames before the W warm-up steps (steady state)")
-    ap.add_argument("--isolated-steps", type=int, default=30, help="steps of the single-stream re-measurement (0 = skip)")
+    ap.add_argument("--isolated-steps", type=int, default=30, help="steps of the single-stream re-measurement of --full (0 = skip)")
     a = ap.parse_args()
+    if a.repeats is None:
+        a.repeats = 0 if a.full else 1
+    isolated_steps = a.isolated_steps if a.full else 0
 
     if "WORLD_SIZE" not in os.environ and (a.gpus > 1 or a.self_launch):
         sys.exit(self_launch(a.gpus))
@@ -1206,10 +1252,12 @@ def main():
 
     view_cycle = [None]  # non-coherent leg: the cameras one_step cycles through instead of the rank's own view
     step_no = [0]
+    last_lane = [None]  # the lane of the latest step: what --dump-outputs writes
 
     def one_step(lane, record=False):
         # every rank renders exactly one view per step (weak scaling): its own
         ws, bucket, stream = lane
+        last_lane[0] = lane
         cam_ = c0
         if view_cycle[0] is not None:
             cam_ = view_cycle[0][step_no[0] % len(view_cycle[0])]
@@ -1326,14 +1374,24 @@ def main():
     run_fps = [world * a.steps / r_[0] for r_ in runs]
     order_ = sorted(range(len(runs)), key=lambda i: run_fps[i])
     elapsed, avg, lat = runs[order_[len(runs) // 2]]   # the median run (the upper one of an even count), as value_runs.median
+    if rank == 0 and a.dump_outputs:
+        # (the exchange of the last step has completed: timed() ends in a device synchronisation)
+        ws_, bucket_, _ = last_lane[0]
+        o_ = ws_.out
+        pixels = lambda t: t.flatten(1).t()  # noqa: E731  ([C, H, W] -> [H*W, C]: pixels are the items)
+        dump_outputs(a.dump_outputs, {
+            "color": pixels(o_["color"]), "language": pixels(o_["language"]), "depth": pixels(o_["depth"]),
+            "opacity": pixels(o_["opacity"]), "radii": o_["radii"], "n_touched": o_["n_touched"],
+            "grad_bucket": bucket_.flat, "densify": bucket_.densify, "max_radii": bucket_.max_radii,
+            "dL_dtau_sum": ws_.grads["dL_dtau_sum"]})
     iso = prof = nonco = None
     # ONE frame in flight is its own workspace: the lanes' workspaces carry OLSR_FLAG_FRAMES_IN_FLIGHT (four-wave radix blocks,
     # which get onto the CUs beside another lane's composite: + 2 % with four frames in flight, - 11 % with one)
     iso_lane = FrameLanes(1, P, W, H, F, M, capacity, dev, tile=15, bwd_mode=mode, binning=binning, flags=fwd_flags,
                           carry_order=carry).lanes[0] \
-        if (a.isolated_steps > 0 and len(lanes) > 1) else lanes.lanes[0]
+        if (isolated_steps > 0 and len(lanes) > 1) else lanes.lanes[0]
     plain_sort = None   # the same-view rates WITHOUT the carried depth order (the five-launch sort every frame)
-    if carry and world == 1:
+    if carry and world == 1 and a.full:
         with carried_order_off(lanes.lanes):
             for _ in range(2 * len(lanes)):
                 one_step(lanes.next_lane())
@@ -1341,18 +1399,18 @@ def main():
         plain_sort = {"value": round(a.steps / p4[0], 3), "unit": "frames/s", "frames_in_flight_per_gpu": len(lanes)}
         for _ in range(2 * len(lanes)):
             one_step(lanes.next_lane())
-    if a.isolated_steps > 0:
+    if isolated_steps > 0:
         for _ in range(8):
             one_step(iso_lane)
-        iso = timed(a.isolated_steps, 3, lambda: iso_lane)
-        prof = timed(a.isolated_steps, 3, lambda: iso_lane, profile=True)
+        iso = timed(isolated_steps, 3, lambda: iso_lane)
+        prof = timed(isolated_steps, 3, lambda: iso_lane, profile=True)
         if plain_sort is not None:
             with carried_order_off([iso_lane]):
                 for _ in range(3):
                     one_step(iso_lane)
-                p1 = timed(a.isolated_steps, 3, lambda: iso_lane)
-                p1p = timed(a.isolated_steps, 3, lambda: iso_lane, profile=True)
-            plain_sort["isolated_value"] = round(a.isolated_steps / p1[0], 3)
+                p1 = timed(isolated_steps, 3, lambda: iso_lane)
+                p1p = timed(isolated_steps, 3, lambda: iso_lane, profile=True)
+            plain_sort["isolated_value"] = round(isolated_steps / p1[0], 3)
             plain_sort["isolated_depth_sort_ms"] = round(p1p[1].get("depth_sort", 0.0), 4)
             for _ in range(3):
                 one_step(iso_lane)
@@ -1363,19 +1421,19 @@ def main():
             step_no[0] = 0
             with carried_order_off(lanes.lanes, [iso_lane]):
                 nc4 = timed(a.steps, a.warmup, lanes.next_lane, events=False)
-                nc1 = timed(a.isolated_steps, 3, lambda: iso_lane)
+                nc1 = timed(isolated_steps, 3, lambda: iso_lane)
             view_cycle[0] = None
             nonco = {"what": "the camera changes every step (8 arc views, yaw -14..+14 deg, 0.15 m apart): the tile-order hint "
                              "a lane carries belongs to another view",
                      "value": round(a.steps / nc4[0], 3), "unit": "frames/s", "frames_in_flight_per_gpu": len(lanes),
-                     "isolated_value": round(a.isolated_steps / nc1[0], 3), "carried_depth_order": False,
+                     "isolated_value": round(isolated_steps / nc1[0], 3), "carried_depth_order": False,
                      "overflow": bool(any(l_[0].rendered()[1] for l_ in lanes.lanes))}
             # (back to the coherent steady state for the legs below)
             for _ in range(2 * len(lanes)):
                 one_step(lanes.next_lane())
             one_step(iso_lane)
             torch.cuda.synchronize(dev)
-    ws0 = iso_lane[0] if a.isolated_steps > 0 else lanes.lanes[0][0]
+    ws0 = iso_lane[0] if isolated_steps > 0 else lanes.lanes[0][0]
     exch_detail = None
     if dist is not None:
         b0 = lanes.lanes[0][1]
@@ -1392,52 +1450,53 @@ def main():
             stt = torch.stack([lane_[1]._capped["status"] for lane_ in lanes.lanes if getattr(lane_[1], "_capped", None)])
             exch_detail.update({"packed_capacity_rows": sparse_cap[0], "rows_in_union_last_step": int(stt[:, 0].max()),
                                 "overflow": bool(int(stt[:, 1].max()))})
-        # The exchange, checked where it ran (outside every timed region): one more frame of this rank's view into lane 0's
-        # bucket, the chosen exchange on it, against the dense all-reduce (SUM of gradients and statistics, MAX of the radii)
-        # of a copy of the same partial sums.  Two statements come back in the line: every rank holds the SAME bucket
-        # afterwards (checksums of the bits, up to the sign of zeros), and it is the dense result (bit for bit with two ranks; beyond two the
-        # collectives may associate the ranks' terms differently for buffers of different size, so the largest difference
-        # relative to the tensor's largest element is reported and held to 1e-5).
-        ws_, bucket_, stream_ = lanes.lanes[0]
-        with torch.cuda.stream(stream_):
-            for w_ in pending.pop(id(bucket_), ()):
-                w_.wait()
-            ws_.set_scene(sh_degree=sc.sh_degree, **c0, **g_dev)
-            ws_.forward()
-            ws_.backward(dc, dl, dd, bucket=bucket_, first=True, bucket_only=True)
-            ref_sum, ref_rad = bucket_.sum_storage.clone(), bucket_.max_radii.clone()
-            if world > 1:
-                dist.all_reduce(ref_sum, op=dist.ReduceOp.SUM)
-                dist.all_reduce(ref_rad, op=dist.ReduceOp.MAX)
-            exchange(bucket_)
-            for w_ in pending.pop(id(bucket_), ()):
-                w_.wait()
-            got = bucket_.sum_storage
-            scale_ = ref_sum.abs().max().clamp_min(1e-30)
-            diff = ((got - ref_sum).abs().max() / scale_).to(torch.float64).reshape(1)
-            same_rad = (bucket_.max_radii == ref_rad).all().to(torch.float64).reshape(1)
-            # identical on every rank: compare the bits through an order-independent integer checksum
-            # (-0.0 + 0.0 = +0.0: a row outside the union keeps this rank's own zeros, whose sign the dense sum would erase)
-            csum = (got + 0.0).view(torch.int32).to(torch.int64).sum().reshape(1)
-            cmax, cmin = csum.clone(), csum.clone()
-            if world > 1:
-                dist.all_reduce(diff, op=dist.ReduceOp.MAX)
-                dist.all_reduce(same_rad, op=dist.ReduceOp.MIN)
-                dist.all_reduce(cmax, op=dist.ReduceOp.MAX)
-                dist.all_reduce(cmin, op=dist.ReduceOp.MIN)
-        torch.cuda.synchronize(dev)
-        exch_detail["check"] = {"what": "one frame per rank after the timed regions: the chosen exchange against the dense "
-                                        "all-reduce of the same partial sums",
-                                "max_abs_diff_over_max_abs": float(diff.item()),
-                                "equals_dense": bool(float(diff.item()) <= (0.0 if world <= 2 else 1e-5)),
-                                "radii_equal": bool(same_rad.item() == 1.0),
-                                "identical_on_every_rank": bool(int(cmax.item()) == int(cmin.item())),
-                                "nonzero_gradient_rows_after": int((bucket_.flat != 0).any(dim=1).sum().item())}
+        if a.full:
+            # The exchange, checked where it ran (outside every timed region): one more frame of this rank's view into lane 0's
+            # bucket, the chosen exchange on it, against the dense all-reduce (SUM of gradients and statistics, MAX of the radii)
+            # of a copy of the same partial sums.  Two statements come back in the line: every rank holds the SAME bucket
+            # afterwards (checksums of the bits, up to the sign of zeros), and it is the dense result (bit for bit with two ranks; beyond two the
+            # collectives may associate the ranks' terms differently for buffers of different size, so the largest difference
+            # relative to the tensor's largest element is reported and held to 1e-5).
+            ws_, bucket_, stream_ = lanes.lanes[0]
+            with torch.cuda.stream(stream_):
+                for w_ in pending.pop(id(bucket_), ()):
+                    w_.wait()
+                ws_.set_scene(sh_degree=sc.sh_degree, **c0, **g_dev)
+                ws_.forward()
+                ws_.backward(dc, dl, dd, bucket=bucket_, first=True, bucket_only=True)
+                ref_sum, ref_rad = bucket_.sum_storage.clone(), bucket_.max_radii.clone()
+                if world > 1:
+                    dist.all_reduce(ref_sum, op=dist.ReduceOp.SUM)
+                    dist.all_reduce(ref_rad, op=dist.ReduceOp.MAX)
+                exchange(bucket_)
+                for w_ in pending.pop(id(bucket_), ()):
+                    w_.wait()
+                got = bucket_.sum_storage
+                scale_ = ref_sum.abs().max().clamp_min(1e-30)
+                diff = ((got - ref_sum).abs().max() / scale_).to(torch.float64).reshape(1)
+                same_rad = (bucket_.max_radii == ref_rad).all().to(torch.float64).reshape(1)
+                # identical on every rank: compare the bits through an order-independent integer checksum
+                # (-0.0 + 0.0 = +0.0: a row outside the union keeps this rank's own zeros, whose sign the dense sum would erase)
+                csum = (got + 0.0).view(torch.int32).to(torch.int64).sum().reshape(1)
+                cmax, cmin = csum.clone(), csum.clone()
+                if world > 1:
+                    dist.all_reduce(diff, op=dist.ReduceOp.MAX)
+                    dist.all_reduce(same_rad, op=dist.ReduceOp.MIN)
+                    dist.all_reduce(cmax, op=dist.ReduceOp.MAX)
+                    dist.all_reduce(cmin, op=dist.ReduceOp.MIN)
+            torch.cuda.synchronize(dev)
+            exch_detail["check"] = {"what": "one frame per rank after the timed regions: the chosen exchange against the dense "
+                                            "all-reduce of the same partial sums",
+                                    "max_abs_diff_over_max_abs": float(diff.item()),
+                                    "equals_dense": bool(float(diff.item()) <= (0.0 if world <= 2 else 1e-5)),
+                                    "radii_equal": bool(same_rad.item() == 1.0),
+                                    "identical_on_every_rank": bool(int(cmax.item()) == int(cmin.item())),
+                                    "nonzero_gradient_rows_after": int((bucket_.flat != 0).any(dim=1).sum().item())}
     Rr, overflow = ws0.rendered()
     # the reference's num_rendered (bounding-square instances) of this view: the R of the byte model
     R_ref = int(_C.state_field("geometry", ws0.geom, "counters", P=P, F=F, dtype=torch.int32, count=8)[3])
     L_rows, row_overflow = ws0.backward_status()
-    wstats = workload_stats(ws0, P, W, H, F) if rank == 0 else None
+    wstats = workload_stats(ws0, P, W, H, F) if (rank == 0 and a.full) else None
 
     if rank == 0:
         frames = world * a.steps
@@ -1517,8 +1576,9 @@ def main():
                                       "p10": round(sorted(run_fps)[int(0.1 * (len(run_fps) - 1))], 3),
                                       "p90": round(sorted(run_fps)[int(0.9 * (len(run_fps) - 1) + 0.5)], 3),
                                       "fps": [int(round(x)) for x in run_fps],
-                                      "note": "the contract's K-step region (barrier, K steps, barrier) repeated back to back "
-                                              "until the timed regions total --min-timed-s; value = the median run"},
+                                      "note": "the contract's K-step region (barrier, K steps, barrier) run --repeats times back "
+                                              "to back (--full without --repeats: until the timed regions total "
+                                              "--min-timed-s); value = the median run"},
                        "frames_in_flight": len(lanes), "same_view_every_step": True,
                        "P": sc.P, "width": W, "height": H, "F": F, "R": R_ref, "R_over_P": round(R_ref / max(sc.P, 1), 3),
                        "binning": a.binning, "R_binned": Rr, "forward_accumulation": a.fwd_accum,
@@ -1542,20 +1602,20 @@ def main():
             out["non_coherent"] = nonco
         if iso is not None:
             iso_el, iso_avg, iso_lat = iso
-            out["isolated"] = {"frames_in_flight_per_gpu": 1, "steps": a.isolated_steps,
-                               "value": round(world * a.isolated_steps / iso_el, 3), "unit": "frames/s",
-                               "ms_per_frame": round(1e3 * iso_el / a.isolated_steps, 4),
+            out["isolated"] = {"frames_in_flight_per_gpu": 1, "steps": isolated_steps,
+                               "value": round(world * isolated_steps / iso_el, 3), "unit": "frames/s",
+                               "ms_per_frame": round(1e3 * iso_el / isolated_steps, 4),
                                "latency_ms": iso_lat,
                                "stage_ms": {k: round(v, 4) for k, v in prof[1].items()},
                                "stage_ms_note": "from a separate profiled leg (HIP events between the stages, ~6 us each)"}
-        if world == 1 and a.isolated_steps > 0:
-            out["dropin"] = dropin_leg(sc, dev, max(3 * a.isolated_steps, 30), 10)
-        if world == 1 and a.isolated_steps > 0 and not a.no_extra_legs:
+        if world == 1 and isolated_steps > 0:
+            out["dropin"] = dropin_leg(sc, dev, max(3 * isolated_steps, 30), 10)
+        if world == 1 and isolated_steps > 0 and not a.no_extra_legs:
             dims = (P, W, H, F, M)
-            out["bracket"] = bracket_legs(sc, g_dev, c0, (dc, dl, dd), dev, max(10, a.isolated_steps), dims)
+            out["bracket"] = bracket_legs(sc, g_dev, c0, (dc, dl, dd), dev, max(10, isolated_steps), dims)
             if a.config == 3 and room is None:
                 out["config4_substitute"] = config4_substitute(sc, g_dev, dev, dims)
-                out["config4_substitute"]["room_scene"] = room_scene_leg(dev, dims, a.isolated_steps)
+                out["config4_substitute"]["room_scene"] = room_scene_leg(dev, dims, isolated_steps)
         # the driver keeps `config` and `roofline` of this line: the rates a caller sees, beside the headline's
         out["config"]["isolated_fps"] = out["isolated"]["value"] if iso is not None else None
         out["config"]["dropin_fps"] = out["dropin"]["value"] if "dropin" in out else None
@@ -1571,7 +1631,7 @@ def main():
                                            "mapping_ms": {k: v["ms_per_iteration"] for k, v in rs_.get("mapping", {}).items()
                                                           if isinstance(v, dict) and "ms_per_iteration" in v},
                                            "stage_ms": rs_.get("stage_ms")}
-        if world == 1 and not a.no_cpu_baseline:
+        if world == 1 and a.full and not a.no_cpu_baseline:
             lane0 = iso_lane
             one_step(lane0)
             torch.cuda.synchronize(dev)

@@ -5,11 +5,12 @@ frame the contract is checked against a workspace without cut-offs on the same i
    status 3  =>  zero gradients, and the array is repaired enough that a repeat of the SAME view ends in status 0 within 3 tries.
 Prints one line per sequence and a summary; exit code 1 on any violation.   python scripts/depth_cut_campaign.py [n_sequences] [seed]"""
 import math
+import os
 import sys
 
 import torch
 
-sys.path.insert(0, "/root/repo")
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from online_lang_splatting_amd.frame_shard import RasterWorkspace
 from online_lang_splatting_amd.scene import Camera, make_scene
 

@@ -1,5 +1,5 @@
 python -m pytest tests/test_gpu_parity.py tests/test_gpu_row_mask.py tests/test_gpu_api.py tests/test_gpu_pose.py tests/test_gpu_loss.py -x -q 2>&1 | tail -4
-B="python bench.py --steps 60 --warmup 12 --no-cpu-baseline --no-extra-legs"
+B="python bench.py --full --steps 60 --warmup 12 --no-cpu-baseline --no-extra-legs"
 for i in 1 2; do
 $B > gpurun_out/ab_split_$i.json 2>/dev/null
 OLSR_LIB=online_lang_splatting_amd/libolsr_nosplit.so $B > gpurun_out/ab_nosplit_$i.json 2>/dev/null

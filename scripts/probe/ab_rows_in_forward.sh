@@ -1,5 +1,5 @@
 for r in 1 2; do for v in 1 0; do
-out=$(OLSR_ROWS_IN_FORWARD=$v timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1)
+out=$(OLSR_ROWS_IN_FORWARD=$v timeout 300 python bench.py --full --steps 20 --warmup 5 --no-cpu-baseline 2>/dev/null | tail -1)
 python - "$v" "$out" <<'PY'
 import json,sys
 d=json.loads(sys.argv[2]); c=d.get("config4_substitute",{})

@@ -2,7 +2,7 @@
 # A/B of kernel variants: bash scripts/probe/ab_variant.sh [lib ...]  ("" = the in-tree libolsr.so), config 3 and config 5
 for lib in "$@"; do
   for cfg in 3 5; do
-  OLSR_LIB=$lib python bench.py --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --isolated-steps 30 2>/dev/null | python -c "
+  OLSR_LIB=$lib python bench.py --full --config $cfg --steps 20 --warmup 5 --no-cpu-baseline --isolated-steps 30 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 b=d.get('bracket',{})

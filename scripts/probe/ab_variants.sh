@@ -5,7 +5,7 @@ for round in 1 2; do
 for spec in "$@"; do
   name=${spec%%:*}; envs=""; [[ "$spec" == *:* ]] && envs=${spec#*:}
   lib=""; [ "$name" != base ] && lib="OLSR_LIB=$PWD/online_lang_splatting_amd/_variants/libolsr_$name.so"
-  out=$(env $lib ${envs//,/ } timeout 300 python bench.py --steps 60 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra-legs ${BENCH_ARGS} 2>/dev/null | tail -1)
+  out=$(env $lib ${envs//,/ } timeout 300 python bench.py --full --steps 60 --warmup 20 --repeats 3 --no-cpu-baseline --no-extra-legs ${BENCH_ARGS} 2>/dev/null | tail -1)
   python - "$spec" "$out" <<'PY'
 import json, sys
 try:

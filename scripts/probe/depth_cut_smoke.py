@@ -1,5 +1,6 @@
-import sys, torch
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+import os, sys, torch
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 from online_lang_splatting_amd.frame_shard import RasterWorkspace
 from online_lang_splatting_amd.scene import make_scene, arc_cameras
 dev = torch.device("cuda:0")

@@ -1,6 +1,6 @@
 set -x
 python -m pytest tests/test_gpu_sparse_exchange.py tests/test_gpu_frame_shard.py -x -q 2>&1 | tail -5
-B="python bench.py --no-extra-legs --isolated-steps 0 --no-cpu-baseline --steps 60"
+B="python bench.py --full --no-extra-legs --isolated-steps 0 --no-cpu-baseline --steps 60"
 $B > gpurun_out/ex_none.json 2>gpurun_out/ex_none.err
 OLSR_BENCH_FORCE_EXCHANGE=1 $B --exchange sparse > gpurun_out/ex_sparse_fused.json 2>gpurun_out/ex_sparse_fused.err
 OLSR_BENCH_FORCE_EXCHANGE=1 OLSR_BENCH_EXCHANGE_TORCH=1 $B --exchange sparse > gpurun_out/ex_sparse_torch.json 2>gpurun_out/ex_sparse_torch.err

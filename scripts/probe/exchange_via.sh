@@ -2,7 +2,7 @@
 # The forced single-rank exchange legs (everything of the multi-GPU step but the wire), RCCL's C API on the lane's stream
 # against torch.distributed, both scenes, alternating.  -> gpurun_out/exchange_via/*.json
 mkdir -p gpurun_out/exchange_via
-A="--steps 60 --warmup 12 --no-cpu-baseline --no-extra-legs --isolated-steps 0"
+A="--full --steps 60 --warmup 12 --no-cpu-baseline --no-extra-legs --isolated-steps 0"
 for round in 1 2; do for sc in room volume; do
   timeout 120 python bench.py --scene $sc $A > gpurun_out/exchange_via/${sc}_none_$round.json 2>/dev/null
   for ex in auto reduce_scatter; do for via in rccl torch; do

@@ -1,5 +1,5 @@
 # how the frames-in-flight rate and the forced single-rank exchange react to the number of HIP hardware queues
-B="python bench.py --no-extra-legs --isolated-steps 0 --no-cpu-baseline --steps 60"
+B="python bench.py --full --no-extra-legs --isolated-steps 0 --no-cpu-baseline --steps 60"
 run() { name=$1; shift; "$@" > gpurun_out/hq_$name.json 2> gpurun_out/hq_$name.err; python -c "
 import json
 try:

@@ -1,7 +1,8 @@
 """Probe: one rank (collectives forced on), 2 lanes, three exchange phases on the same lanes: tracked vs untracked flat after every step."""
 import os, sys
 import torch, torch.distributed as dist
-sys.path.insert(0, "/root/repo"); sys.path.insert(0, "/root/repo/tests")
+ROOT = os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
 import test_gpu_frame_shard as T
 from online_lang_splatting_amd.frame_shard import FrameLanes, FrameShardedStep, FusedAdam, GradLayout, GradientBucket
 

@@ -1,7 +1,7 @@
 """Tracking iteration at config 3: plain loop with host / device step count, and the depth cut-off loop (wall clock per
 iteration, 3 repeats of 60)."""
-import sys, time, torch
-sys.path.insert(0, "/root/repo")
+import os, sys, time, torch
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspath(__file__)))))
 from online_lang_splatting_amd.frame_shard import RasterWorkspace
 from online_lang_splatting_amd.scene import default_camera, make_config_scene
 from online_lang_splatting_amd.slam_iterations import PoseState, TrackingLoop

@@ -10,8 +10,8 @@ STEPS=${3:-20}
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/$TAG
 mkdir -p $OUT
-python bench.py --scene $SCENE --steps 60 --warmup 12 --no-cpu-baseline > $OUT/bench_$SCENE.json 2> $OUT/bench_$SCENE.err
-B="python bench.py --scene $SCENE --no-cpu-baseline --no-extra-legs --repeats 1"
+python bench.py --full --scene $SCENE --steps 60 --warmup 12 --no-cpu-baseline > $OUT/bench_$SCENE.json 2> $OUT/bench_$SCENE.err
+B="python bench.py --full --scene $SCENE --no-cpu-baseline --no-extra-legs --repeats 1"
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -o s -- $B --steps $STEPS --warmup 5 > $OUT/bench_stats.log 2>&1
 timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats1 -o s -- $B --steps $STEPS --warmup 5 --streams 1 --isolated-steps 0 > $OUT/bench_stats1.log 2>&1
 # ... once more with the plain five-launch depth sort (no carried order), where every launched kernel does its work; the

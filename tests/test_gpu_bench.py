@@ -22,7 +22,7 @@ def _last_json(out):
 
 
 def test_single_process_line():
-    p = subprocess.run([sys.executable, "bench.py", "--config", "1", "--steps", "6", "--warmup", "2"], cwd=ROOT,
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--config", "1", "--steps", "6", "--warmup", "2"], cwd=ROOT,
                        capture_output=True, text=True, timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -48,10 +48,35 @@ def test_single_process_line():
     assert "config4_substitute" not in d  # (config 3 only)
 
 
+def test_plain_line_times_k_steps_and_dumps_the_last_step(tmp_path):
+    """Without --full: one region of exactly K timed steps and none of the other legs; --dump-outputs writes what the last
+    timed step computed, float32, within 64 MB, and a second run with the same arguments computes the same."""
+    import numpy as np
+    dumps = []
+    for run in ("a", "b"):
+        p = subprocess.run([sys.executable, "bench.py", "--config", "1", "--steps", "7", "--warmup", "2", "--dump-outputs",
+                            str(tmp_path / run)], cwd=ROOT, capture_output=True, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        d = _last_json(p.stdout)
+        assert KEYS <= set(d) and d["steps"] == 7 and d["config"]["value_runs"]["runs"] == 1 and d["value"] > 0
+        assert abs(d["value"] * d["ms_per_step"] / 1e3 - 1.0) < 5e-3 and d["roofline"] is None
+        assert not {"isolated", "non_coherent", "dropin", "bracket", "config4_substitute", "cpu_baseline"} & set(d)
+        files = sorted(os.listdir(tmp_path / run))
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= 64 * 10**6
+        dumps.append({f[:-4]: np.load(tmp_path / run / f) for f in files})
+    a, b = dumps
+    assert set(a) == {"color", "depth", "opacity", "radii", "n_touched", "grad_bucket", "densify", "max_radii", "dL_dtau_sum"}
+    assert all(v.dtype == np.float32 for v in a.values()) and a["color"].shape == (256 * 256, 3)
+    assert a["radii"].max() > 0 and np.abs(a["grad_bucket"]).max() > 0
+    for k in a:
+        assert a[k].shape == b[k].shape, k
+        assert np.abs(a[k] - b[k]).max() <= 1e-4 * max(np.abs(a[k]).max(), 1e-30), k
+
+
 def test_config3_line_carries_the_config4_substitute():
     """The driver's line (config 3) also reports the measurable substitute of BASELINE configs[3]: the dependent tracking
     iteration and the 12-view mapping iteration, plus the valu roofline priced against the guide's issue rate."""
-    p = subprocess.run([sys.executable, "bench.py", "--steps", "8", "--warmup", "3", "--isolated-steps", "10",
+    p = subprocess.run([sys.executable, "bench.py", "--full", "--steps", "8", "--warmup", "3", "--isolated-steps", "10",
                         "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=900)
     assert p.returncode == 0, p.stderr[-2000:]
     d = _last_json(p.stdout)
@@ -143,7 +168,7 @@ def test_gpus_flag_launches_its_own_ranks():
     report one GPU; OLSR_BENCH_BACKEND=gloo is the functional fallback in which the ranks share the device."""
     import torch
     env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OLSR_BENCH_BACKEND")}
-    args = [sys.executable, "bench.py", "--gpus", "2", "--config", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
+    args = [sys.executable, "bench.py", "--full", "--gpus", "2", "--config", "1", "--steps", "4", "--warmup", "2", "--no-cpu-baseline"]
     p = subprocess.run(args, cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     if torch.cuda.device_count() >= 2:
         assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-1500:])
@@ -189,7 +214,7 @@ def test_forced_single_rank_exchange_over_rccl_and_a_clean_stdout():
     created; the line must stay the ONLY thing on stdout (the driver parses it), whatever native code prints."""
     for exchange in ("auto", "sparse", "all_reduce", "reduce_scatter"):
         env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "OLSR_BENCH_BACKEND")}
-        p = subprocess.run([sys.executable, "bench.py", "--config", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
+        p = subprocess.run([sys.executable, "bench.py", "--full", "--config", "1", "--steps", "6", "--warmup", "2", "--no-cpu-baseline",
                             "--no-extra-legs", "--isolated-steps", "0", "--repeats", "2", "--exchange", exchange], cwd=ROOT,
                            env=dict(env, OLSR_BENCH_FORCE_EXCHANGE="1"), capture_output=True, text=True, timeout=600)
         assert p.returncode == 0, (exchange, p.stdout[-1500:], p.stderr[-1500:])
