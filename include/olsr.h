@@ -23,7 +23,8 @@
  * Contents: the rasterizer itself (olsr_forward, olsr_forward_async, olsr_backward, olsr_mark_visible and
  * their size / introspection / profiling helpers — SURVEY.md section 8 rows a-e), then the callers and
  * data either side of it (rows f1-f3): olsr_mapping_loss, olsr_tracking_loss, olsr_pose_step,
- * olsr_accumulate_gradients, olsr_sparse_exchange_mask / _pack / _unpack, olsr_adam_step, olsr_knn_mean_dist2.
+ * olsr_accumulate_gradients, olsr_sparse_exchange_mask / _pack / _unpack, olsr_adam_step (and its per-group form
+ * olsr_adam_step_groups), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2.
  */
 #ifndef OLSR_H_INCLUDED
 #define OLSR_H_INCLUDED
@@ -408,6 +409,75 @@ int olsr_adam_step_masked(int32_t P, int32_t M, int32_t F, const olsr_adam_param
 int olsr_bucket_add(int32_t P, int32_t width, float *dst_flat, float *dst_densify, int32_t *dst_max_radii,
                     uint64_t *dst_row_mask, const float *src_flat, const float *src_densify, const int32_t *src_max_radii,
                     const uint64_t *src_row_mask, void *hip_stream);
+
+/* Per-group step counts (the reference's optimiser keeps one `step` per parameter group, and two of its map edits make
+ * groups skip a step: gaussian_model.py replace_tensor_to_optimizer / densification_postfix replace parameters, whose `grad`
+ * is then None in that iteration's optimizer.step()).  group_step[g] is group g's 1-based step count AFTER its increment,
+ * g = OLSR_ADAM_GROUP_*; a group whose bit is set in skip_mask is not touched at all (parameters and moments unchanged).
+ * The other fields of `base` are used as in olsr_adam_step (base.step is ignored).  With every group_step equal to s and
+ * skip_mask 0 the result equals olsr_adam_step_masked with step s, bit for bit. */
+#define OLSR_ADAM_GROUP_XYZ 0
+#define OLSR_ADAM_GROUP_SH_DC 1
+#define OLSR_ADAM_GROUP_SH_REST 2
+#define OLSR_ADAM_GROUP_OPACITY 3
+#define OLSR_ADAM_GROUP_SCALE 4
+#define OLSR_ADAM_GROUP_ROTATION 5
+#define OLSR_ADAM_GROUP_LANGUAGE 6
+#define OLSR_ADAM_GROUPS 7
+typedef struct olsr_adam_group_params {
+  olsr_adam_params base;
+  int32_t group_step[OLSR_ADAM_GROUPS];
+  int32_t skip_mask;
+} olsr_adam_group_params;
+int olsr_adam_step_groups(int32_t P, int32_t M, int32_t F, const olsr_adam_group_params *params, int32_t n_flats,
+                          const float *const *flats, const uint64_t *const *row_masks, float *means3D, float *shs,
+                          float *opacities, float *scales, float *rotations, float *language, float *exp_avg,
+                          float *exp_avg_sq, void *hip_stream);
+
+/* ---- map edits: densify, prune and extend the Gaussian map on the fused buffers (csrc/k_map_edit.hip) --------------
+ * One primitive behind GaussianModel.densify_and_prune / prune_points / extend_from_pcd
+ * (gaussian_splatting/scene/gaussian_model.py:718-961), in two launches around ONE host read:
+ *   olsr_map_edit_plan   classifies every source row (keep / clone / split / drop), counts the output segments per block and
+ *                        prefixes the counts over the blocks; status[0] = P_new (the caller reads it back to size the
+ *                        destination: the edit's one host synchronisation);
+ *   olsr_map_edit_apply  reads every source row once and writes the destination buffers out of place.
+ * Output order is the reference's: [kept originals | kept clones | kept split children k = 0 | k = 1 | appended rows],
+ * each segment in source order.  No atomics on data: two runs on the same inputs give the same bits.
+ * Densify mode (OLSR_MAP_EDIT_DENSIFY; src->stats = {xyz_gradient_accum, denom}): g = accum / denom, 0/0 -> 0;
+ * smax = max(exp(scaling)); clone: g >= max_grad and smax <= clone_max_scale (percent_dense * extent); split:
+ * g >= max_grad and smax > clone_max_scale (N = 2 children; child k of source row j uses z[j, k, 0:3]:
+ * xyz = build_rotation(q) (std * z) + xyz with std = exp(scaling), scaling = log(exp(scaling) / 1.6), other fields raw
+ * copies); then every candidate row is dropped when sigmoid(opacity) < min_opacity, or — screen_size_term != 0 —
+ * max(exp(scaling)) > big_scale (0.1 * extent).  The reference's max_radii2D > max_screen_size term never fires: its
+ * densification_postfix has zeroed max_radii2D just before (:847-849).  Moments: kept originals keep theirs, new rows start
+ * at zero; accumulators (stats, max_radii) are zeroed for EVERY row.
+ * Mask mode (OLSR_MAP_EDIT_MASK): row j is dropped when drop_mask[j] != 0 (NULL: none); moments and accumulators follow the
+ * kept rows (prune_points).  n_append > 0 appends that many rows from `append` (means3D, shs, opacities, scales, rotations;
+ * language zero, kf_id = append_kf_id, n_obs 0, moments zero) and zeroes every row's accumulators (extend_from_pcd).
+ * src_index[i] = the source row destination row i came from, or -(k + 1) for appended row k.
+ * Scratch: olsr_map_edit_scratch_bytes(P); status: int32[8] = {P_new, kept originals, kept clones, kept children per k,
+ * appended, 0, 0, 0}.  dst buffers hold dst_capacity rows; rows past dst_capacity are never written (OLSR_ERR_CAPACITY
+ * from apply when P_new exceeds it - the status is read on the host first). */
+#define OLSR_MAP_EDIT_DENSIFY 0
+#define OLSR_MAP_EDIT_MASK 1
+typedef struct olsr_map_buffers {
+  float *means3D, *shs, *opacities, *scales, *rotations, *language; /* [P,3] [P,M,3] [P] [P,3] [P,4] [P,F] */
+  float *exp_avg, *exp_avg_sq;                                      /* [P, 11 + 3M + F], bucket layout */
+  int32_t *kf_id, *n_obs;                                           /* [P] */
+  float *stats;                                                     /* [P,2] {xyz_gradient_accum, denom} */
+  int32_t *max_radii;                                               /* [P] */
+} olsr_map_buffers;
+typedef struct olsr_map_edit_params {
+  int32_t mode, n_append, append_kf_id, screen_size_term;
+  float max_grad, min_opacity, clone_max_scale, big_scale; /* fp32, as torch compares a float tensor with a Python float */
+} olsr_map_edit_params;
+size_t olsr_map_edit_scratch_bytes(int32_t P);
+int olsr_map_edit_plan(int32_t P, const olsr_map_edit_params *params, const olsr_map_buffers *src, const uint8_t *drop_mask,
+                       void *scratch, int32_t *status, void *hip_stream);
+int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_params *params, const olsr_map_buffers *src,
+                        const float *z, const olsr_map_buffers *append, const void *scratch, const int32_t *status,
+                        int32_t P_new, int32_t dst_capacity, const olsr_map_buffers *dst, int32_t *src_index,
+                        void *hip_stream);
 
 /* ---- the reference's other native dependency ----------------------------
  * mean_dist2[i] = mean of the squared distances from point i to its 3 nearest neighbours (FLT_MAX counts

@@ -86,6 +86,32 @@ class OlsrAdamParams(C.Structure):
                                            "lr_language", "beta1", "beta2", "eps")] + [("step", C.c_int32), ("_pad0", C.c_int32)]
 
 
+class OlsrAdamGroupParams(C.Structure):
+    """struct olsr_adam_group_params, include/olsr.h (group order: OLSR_ADAM_GROUP_*)."""
+
+    _fields_ = [("base", OlsrAdamParams), ("group_step", C.c_int32 * 7), ("skip_mask", C.c_int32)]
+
+
+# OLSR_ADAM_GROUP_*: the reference's parameter groups (gaussian_model.py training_setup) in bucket-column order
+ADAM_GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "f_language")
+
+MAP_EDIT_DENSIFY, MAP_EDIT_MASK = 0, 1
+
+
+class OlsrMapBuffers(C.Structure):
+    """struct olsr_map_buffers, include/olsr.h."""
+
+    _fields_ = [(n, _fp) for n in ("means3D", "shs", "opacities", "scales", "rotations", "language", "exp_avg", "exp_avg_sq",
+                                   "kf_id", "n_obs", "stats", "max_radii")]
+
+
+class OlsrMapEditParams(C.Structure):
+    """struct olsr_map_edit_params, include/olsr.h."""
+
+    _fields_ = [("mode", C.c_int32), ("n_append", C.c_int32), ("append_kf_id", C.c_int32), ("screen_size_term", C.c_int32),
+                ("max_grad", C.c_float), ("min_opacity", C.c_float), ("clone_max_scale", C.c_float), ("big_scale", C.c_float)]
+
+
 class OlsrPoseParams(C.Structure):
     """struct olsr_pose_params, include/olsr.h."""
 

@@ -27,6 +27,13 @@ struct AdamScalars {
       neg_step_language;  // -(lr / bias_correction1)
 };
 
+// per-group bias corrections (olsr_adam_step_groups): the reference's optimiser counts a step per parameter group, and a group
+// whose parameter was replaced in that iteration (reset_opacity, densification) skips it
+struct AdamGroupScalars {
+  float bias_correction2_sqrt[OLSR_ADAM_GROUPS];
+  unsigned skip_mask;
+};
+
 // up to OLSR_ADAM_MAX_BUCKETS gradient buckets summed on the fly, in order: ((f0 + f1) + f2) + ... — what a sum of the lane
 // buckets (frame_shard.FrameLanes) leaves, bit for bit, without writing it anywhere
 struct AdamBuckets {
@@ -39,13 +46,16 @@ struct AdamBuckets {
   const unsigned long long* mask_more[OLSR_ADAM_MAX_BUCKETS - 1];
 };
 
+// GROUPS = false: one step count for every group (olsr_adam_step / _sum / _masked, unchanged); true: the per-group form, the
+// same arithmetic with the group's own sqrt(bias_correction2) and a skip bit per group
+template <bool GROUPS>
 __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int width, const float* __restrict__ flat,
                                                         AdamBuckets extra,
                                                         float* __restrict__ means3D, float* __restrict__ shs,
                                                         float* __restrict__ opacities, float* __restrict__ scales,
                                                         float* __restrict__ rotations, float* __restrict__ language,
                                                         float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                                        AdamScalars hp) {
+                                                        AdamScalars hp, AdamGroupScalars gp) {
   const int g0 = blockIdx.x * ADAM_G;
   const int ng = min(ADAM_G, P - g0);
   const int count = ng * width;
@@ -64,12 +74,19 @@ __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int
     const size_t g = (size_t)(g0 + gl);
     float* p;
     float neg_step;
-    if (c < 3) { p = means3D + 3 * g + c; neg_step = hp.neg_step_xyz; }
-    else if (c < 3 + sh_w) { p = shs + g * sh_w + (c - 3); neg_step = (c < 6) ? hp.neg_step_sh_dc : hp.neg_step_sh_rest; }
-    else if (c < 4 + sh_w) { p = opacities + g; neg_step = hp.neg_step_opacity; }
-    else if (c < 7 + sh_w) { p = scales + 3 * g + (c - 4 - sh_w); neg_step = hp.neg_step_scale; }
-    else if (c < 11 + sh_w) { p = rotations + 4 * g + (c - 7 - sh_w); neg_step = hp.neg_step_rotation; }
-    else { p = language + g * F + (c - 11 - sh_w); neg_step = hp.neg_step_language; }
+    int group;
+    if (c < 3) { p = means3D + 3 * g + c; neg_step = hp.neg_step_xyz; group = OLSR_ADAM_GROUP_XYZ; }
+    else if (c < 3 + sh_w) {
+      p = shs + g * sh_w + (c - 3);
+      neg_step = (c < 6) ? hp.neg_step_sh_dc : hp.neg_step_sh_rest;
+      group = (c < 6) ? OLSR_ADAM_GROUP_SH_DC : OLSR_ADAM_GROUP_SH_REST;
+    }
+    else if (c < 4 + sh_w) { p = opacities + g; neg_step = hp.neg_step_opacity; group = OLSR_ADAM_GROUP_OPACITY; }
+    else if (c < 7 + sh_w) { p = scales + 3 * g + (c - 4 - sh_w); neg_step = hp.neg_step_scale; group = OLSR_ADAM_GROUP_SCALE; }
+    else if (c < 11 + sh_w) { p = rotations + 4 * g + (c - 7 - sh_w); neg_step = hp.neg_step_rotation; group = OLSR_ADAM_GROUP_ROTATION; }
+    else { p = language + g * F + (c - 11 - sh_w); neg_step = hp.neg_step_language; group = OLSR_ADAM_GROUP_LANGUAGE; }
+    if (GROUPS && ((gp.skip_mask >> group) & 1u)) continue;
+    const float bc2_sqrt = GROUPS ? gp.bias_correction2_sqrt[group] : hp.bias_correction2_sqrt;
     float grad = ((w0 >> gl) & 1ull) ? flat[base + e] : 0.0f;
 #pragma unroll
     for (int b = 0; b < OLSR_ADAM_MAX_BUCKETS - 1; ++b)
@@ -77,7 +94,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int
     float m = exp_avg[base + e], v = exp_avg_sq[base + e];
     m = m + (grad - m) * hp.one_minus_beta1;              // exp_avg.lerp_(grad, 1 - beta1)
     v = v * hp.beta2 + hp.one_minus_beta2 * grad * grad;  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
-    const float denom = sqrtf(v) / hp.bias_correction2_sqrt + hp.eps;
+    const float denom = sqrtf(v) / bc2_sqrt + hp.eps;
     *p = *p + neg_step * (m / denom);                     // param.addcdiv_(exp_avg, denom, value=-step_size)
     exp_avg[base + e] = m;
     exp_avg_sq[base + e] = v;
@@ -86,7 +103,7 @@ __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int
 
 void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const float* const* flats,
                       const unsigned long long* const* masks, int n_flats, float* means3D, float* shs, float* opacities, float* scales, float* rotations, float* language,
-                      float* exp_avg, float* exp_avg_sq, hipStream_t st) {
+                      float* exp_avg, float* exp_avg_sq, hipStream_t st, const int32_t* group_step, unsigned skip_mask) {
   if (P <= 0) return;
   const float* flat = flats[0];
   AdamBuckets extra{};
@@ -113,8 +130,33 @@ void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const flo
   k.neg_step_scale = (float)(-(hp.lr_scale / bc1));
   k.neg_step_rotation = (float)(-(hp.lr_rotation / bc1));
   k.neg_step_language = (float)(-(hp.lr_language / bc1));
-  adam_step_kernel<<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities, scales,
-                                                             rotations, language, exp_avg, exp_avg_sq, k);
+  AdamGroupScalars gk{};
+  if (!group_step) {
+    adam_step_kernel<false><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
+                                                                       scales, rotations, language, exp_avg, exp_avg_sq, k, gk);
+    return;
+  }
+  // per group: the same double arithmetic on the group's own step count (torch/optim/adam.py: step_t is per parameter)
+  const double lrs[OLSR_ADAM_GROUPS] = {hp.lr_xyz, hp.lr_sh_dc, hp.lr_sh_rest, hp.lr_opacity, hp.lr_scale, hp.lr_rotation,
+                                        hp.lr_language};
+  float neg[OLSR_ADAM_GROUPS];
+  for (int g = 0; g < OLSR_ADAM_GROUPS; ++g) {
+    const int s = group_step[g] > 0 ? group_step[g] : 1;  // (a skipped group's count is not used)
+    const double gbc1 = 1.0 - pow(hp.beta1, (double)s);
+    const double gbc2 = 1.0 - pow(hp.beta2, (double)s);
+    gk.bias_correction2_sqrt[g] = (float)sqrt(gbc2);
+    neg[g] = (float)(-(lrs[g] / gbc1));
+  }
+  gk.skip_mask = skip_mask;
+  k.neg_step_xyz = neg[OLSR_ADAM_GROUP_XYZ];
+  k.neg_step_sh_dc = neg[OLSR_ADAM_GROUP_SH_DC];
+  k.neg_step_sh_rest = neg[OLSR_ADAM_GROUP_SH_REST];
+  k.neg_step_opacity = neg[OLSR_ADAM_GROUP_OPACITY];
+  k.neg_step_scale = neg[OLSR_ADAM_GROUP_SCALE];
+  k.neg_step_rotation = neg[OLSR_ADAM_GROUP_ROTATION];
+  k.neg_step_language = neg[OLSR_ADAM_GROUP_LANGUAGE];
+  adam_step_kernel<true><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
+                                                                    scales, rotations, language, exp_avg, exp_avg_sq, k, gk);
 }
 
 }  // namespace olsr

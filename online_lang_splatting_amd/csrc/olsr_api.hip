@@ -1183,6 +1183,73 @@ int olsr_debug_backward_ordered(const olsr_scene* scene, const void* geometry_bu
 }
 
 const char* olsr_last_error(void) { return g_err.c_str(); }
+int olsr_adam_step_groups(int32_t P, int32_t M, int32_t F, const olsr_adam_group_params* params, int32_t n_flats,
+                          const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
+                          float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
+                          float* exp_avg_sq, void* hip_stream) {
+  if (P < 0 || M < 0 || !supported_F(F)) return fail(OLSR_ERR_ARG, "P, M must be >= 0 and F one of 0, 3, 15, 16, 32");
+  if (!params) return fail(OLSR_ERR_ARG, "adam group params are required");
+  for (int g = 0; g < OLSR_ADAM_GROUPS; ++g)
+    if (!((params->skip_mask >> g) & 1) && params->group_step[g] < 1)
+      return fail(OLSR_ERR_ARG, "adam_step_groups: the step count of every group that steps must be >= 1");
+  if (n_flats < 1 || n_flats > OLSR_ADAM_MAX_BUCKETS || !flats)
+    return fail(OLSR_ERR_ARG, "adam_step_groups: between 1 and 8 gradient buckets");
+  for (int b = 0; b < n_flats; ++b)
+    if (!flats[b]) return fail(OLSR_ERR_ARG, "adam_step_groups: a gradient bucket is NULL");
+  if (P == 0) return OLSR_OK;
+  if (!means3D || !opacities || !scales || !rotations || !exp_avg || !exp_avg_sq || (M > 0 && !shs) || (F > 0 && !language))
+    return fail(OLSR_ERR_ARG, "every parameter array and both moment buffers are required");
+  launch_adam_step(P, M, F, params->base, flats, reinterpret_cast<const unsigned long long* const*>(row_masks), n_flats,
+                   means3D, shs, opacities, scales, rotations, language, exp_avg, exp_avg_sq, (hipStream_t)hip_stream,
+                   params->group_step, (unsigned)params->skip_mask);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("adam_step_groups launch: ") + hipGetErrorString(e));
+  return OLSR_OK;
+}
+
+size_t olsr_map_edit_scratch_bytes(int32_t P) { return map_edit_scratch_bytes(P); }
+
+static bool map_buffers_complete(const olsr_map_buffers* b, int32_t M, int32_t F) {
+  return b && b->means3D && b->opacities && b->scales && b->rotations && (M == 0 || b->shs) && (F == 0 || b->language) &&
+         b->exp_avg && b->exp_avg_sq && b->kf_id && b->n_obs && b->stats && b->max_radii;
+}
+
+int olsr_map_edit_plan(int32_t P, const olsr_map_edit_params* params, const olsr_map_buffers* src, const uint8_t* drop_mask,
+                       void* scratch, int32_t* status, void* hip_stream) {
+  if (P < 0 || !params || !src || !scratch || !status) return fail(OLSR_ERR_ARG, "map_edit_plan: P >= 0, params, src, scratch and status are required");
+  if (params->mode != OLSR_MAP_EDIT_DENSIFY && params->mode != OLSR_MAP_EDIT_MASK) return fail(OLSR_ERR_ARG, "map_edit_plan: unknown mode");
+  if (params->n_append < 0) return fail(OLSR_ERR_ARG, "map_edit_plan: n_append must be >= 0");
+  if (params->mode == OLSR_MAP_EDIT_DENSIFY && params->n_append != 0)
+    return fail(OLSR_ERR_ARG, "map_edit_plan: densify mode appends nothing");
+  if (P > 0 && params->mode == OLSR_MAP_EDIT_DENSIFY && (!src->stats || !src->scales || !src->opacities))
+    return fail(OLSR_ERR_ARG, "map_edit_plan: densify mode reads stats, scales and opacities");
+  launch_map_edit_plan(P, *params, *src, drop_mask, scratch, status, (hipStream_t)hip_stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("map_edit_plan launch: ") + hipGetErrorString(e));
+  return OLSR_OK;
+}
+
+int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_params* params, const olsr_map_buffers* src,
+                        const float* z, const olsr_map_buffers* append, const void* scratch, const int32_t* status,
+                        int32_t P_new, int32_t dst_capacity, const olsr_map_buffers* dst, int32_t* src_index,
+                        void* hip_stream) {
+  if (P < 0 || M < 0 || !supported_F(F) || !params || !scratch || !status)
+    return fail(OLSR_ERR_ARG, "map_edit_apply: P, M >= 0, F one of 0, 3, 15, 16, 32; params, scratch and status are required");
+  if (P_new > dst_capacity) return fail(OLSR_ERR_CAPACITY, "map_edit_apply: P_new exceeds the destination's capacity");
+  if (P_new == 0) return OLSR_OK;
+  if (!map_buffers_complete(dst, M, F) || !src_index) return fail(OLSR_ERR_ARG, "map_edit_apply: every destination buffer is required");
+  if (P > 0 && !map_buffers_complete(src, M, F)) return fail(OLSR_ERR_ARG, "map_edit_apply: every source buffer is required");
+  if (P > 0 && params->mode == OLSR_MAP_EDIT_DENSIFY && !z) return fail(OLSR_ERR_ARG, "map_edit_apply: densify mode needs z [P,2,3]");
+  if (params->n_append > 0 && (!append || !append->means3D || !append->opacities || !append->scales || !append->rotations ||
+                               (M > 0 && !append->shs)))
+    return fail(OLSR_ERR_ARG, "map_edit_apply: the appended rows need means3D, shs, opacities, scales and rotations");
+  launch_map_edit_apply(P, M, F, *params, *src, z, append, scratch, status, dst_capacity, *dst, src_index,
+                        (hipStream_t)hip_stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("map_edit_apply launch: ") + hipGetErrorString(e));
+  return OLSR_OK;
+}
+
 const char* olsr_version(void) { return "olsr 0.1 (gfx950)"; }
 
 }  // extern "C"

@@ -221,7 +221,16 @@ void launch_bucket_add(int P, int width, float* dst, const float* src, unsigned 
 constexpr int OLSR_ADAM_MAX_BUCKETS = 8;
 void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const float* const* flats,
                       const unsigned long long* const* masks, int n_flats, float* means3D, float* shs, float* opacities, float* scales, float* rotations, float* language,
-                      float* exp_avg, float* exp_avg_sq, hipStream_t st);
+                      float* exp_avg, float* exp_avg_sq, hipStream_t st, const int32_t* group_step = nullptr,
+                      unsigned skip_mask = 0u);
+
+// k_map_edit.hip
+size_t map_edit_scratch_bytes(int P);
+void launch_map_edit_plan(int P, const olsr_map_edit_params& p, const olsr_map_buffers& src, const uint8_t* drop_mask,
+                          void* scratch, int32_t* status, hipStream_t st);
+void launch_map_edit_apply(int P, int M, int F, const olsr_map_edit_params& p, const olsr_map_buffers& src, const float* z,
+                           const olsr_map_buffers* append, const void* scratch, const int32_t* status, int dst_capacity,
+                           const olsr_map_buffers& dst, int32_t* src_index, hipStream_t st);
 
 // k_pose.hip
 void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,

@@ -105,6 +105,35 @@ class GradientBucket:
         self.row_mask = (torch.full(((P + 63) // 64,), -1, dtype=torch.int64, device=device)
                          if (track_rows and torch.device(device).type == "cuda") else None)
 
+    def resize(self, P):
+        """Follow a map edit (gaussian_map.GaussianMap): the bucket now covers P rows.  The storage is reused while it is large
+        enough and reallocated only when P needs more; the contents are zeroed (the rows of the old map mean nothing now)."""
+        P, width = int(P), self.layout.width
+        dev = self.sum_storage.device
+        off = ((P + 1) * width + 3) // 4 * 4
+        need = (off + 2 * P + 63) // 64 * 64
+        if need > self.sum_storage.numel():
+            self.sum_storage = torch.zeros(need, dtype=torch.float32, device=dev)
+        else:
+            self.sum_storage.zero_()
+        self.flat = self.sum_storage[: P * width].view(P, width)
+        self.flat_ext = self.sum_storage[: (P + 1) * width].view(P + 1, width)
+        self.densify = self.sum_storage[off:off + 2 * P].view(P, 2)
+        base = getattr(self, "_radii_base", self.max_radii)
+        if P > base.numel():
+            base = torch.zeros(P, dtype=torch.int32, device=dev)
+        self._radii_base = base
+        self.max_radii = base[:P]
+        self.max_radii.zero_()
+        if self.row_mask is not None:
+            mbase = getattr(self, "_mask_base", self.row_mask)
+            if (P + 63) // 64 > mbase.numel():
+                mbase = torch.empty((P + 63) // 64, dtype=torch.int64, device=dev)
+            self._mask_base = mbase
+            self.row_mask = mbase[: (P + 63) // 64]
+            self.rows_unknown()
+        self._capped = None
+
     def rows_unknown(self):
         """`flat` was written by something other than the backward's fused accumulation: every row may be non-zero."""
         if self.row_mask is not None:
@@ -481,17 +510,33 @@ class FusedAdam:
         self.exp_avg = torch.zeros(P, layout.width, dtype=torch.float32, device=device)
         self.exp_avg_sq = torch.zeros(P, layout.width, dtype=torch.float32, device=device)
         self.step_count = 0
+        # one step count per parameter group (_abi.ADAM_GROUPS order), as torch.optim.Adam keeps one per parameter: a map edit
+        # makes groups skip a step (gaussian_map.GaussianMap), and their bias corrections lag from then on
+        self.group_steps = [0] * len(_abi.ADAM_GROUPS)
         self.use_row_masks = True  # (False: read every gradient row, the A/B leg of tests and bench)
 
-    def step(self, bucket, params: Dict[str, torch.Tensor], lrs: Dict[str, float], rows=None):
+    def step(self, bucket, params: Dict[str, torch.Tensor], lrs: Dict[str, float], rows=None, skip=()):
         """params: means3D [P,3], shs [P,M,3], opacities [P(,1)], scales [P,3], rotations [P,4], language [P,F]
         (contiguous fp32 on the GPU, updated in place); lrs: xyz, sh_dc, sh_rest, opacity, scale, rotation, language.
         rows = (r0, r1): update only that contiguous range of Gaussians (the rows a rank owns after a
-        reduce-scatter); the moments of the other rows are left alone."""
+        reduce-scatter); the moments of the other rows are left alone.
+        skip: names of _abi.ADAM_GROUPS that do not step in this call (parameters, moments and step count untouched) — the
+        reference's groups whose parameter was replaced in this iteration and so has no gradient; "all" skips the call."""
+        skip = set(_abi.ADAM_GROUPS) if skip == "all" else set(skip)
+        unknown = skip - set(_abi.ADAM_GROUPS)
+        if unknown:
+            raise ValueError(f"FusedAdam.step: unknown parameter groups {sorted(unknown)}")
+        if len(skip) == len(_abi.ADAM_GROUPS):
+            return
         self.step_count += 1
+        for gi, name in enumerate(_abi.ADAM_GROUPS):
+            if name not in skip:
+                self.group_steps[gi] += 1
+        uniform = not skip and len(set(self.group_steps)) == 1
         hp = _abi.OlsrAdamParams(lr_xyz=lrs["xyz"], lr_sh_dc=lrs["sh_dc"], lr_sh_rest=lrs["sh_rest"], lr_opacity=lrs["opacity"],
                                  lr_scale=lrs["scale"], lr_rotation=lrs["rotation"], lr_language=lrs.get("language", 0.0),
-                                 beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=self.step_count)
+                                 beta1=self.betas[0], beta2=self.betas[1], eps=self.eps,
+                                 step=self.group_steps[0] if uniform else 1)
         for k, t in params.items():
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()):
                 raise RuntimeError(f"FusedAdam: {k} must be a contiguous fp32 tensor on the GPU")
@@ -513,6 +558,20 @@ class FusedAdam:
         # rows a bucket's row mask proves zero are not read (olsr_adam_step_masked: the update stays dense, the bits are
         # torch.optim.Adam's); a row range that does not start on a mask word (64 rows) takes the unmasked step
         masked = self.use_row_masks and r0 % 64 == 0 and any(b.row_mask is not None for b in buckets)
+        if not uniform:   # (per-group step counts or skipped groups: olsr_adam_step_groups, the same arithmetic per group)
+            gp = _abi.OlsrAdamGroupParams(base=hp, skip_mask=sum(1 << gi for gi, n in enumerate(_abi.ADAM_GROUPS) if n in skip))
+            for gi in range(len(_abi.ADAM_GROUPS)):
+                gp.group_step[gi] = self.group_steps[gi]
+            flats = (C.c_void_p * len(buckets))(*[b.flat.data_ptr() + 4 * r0 * W for b in buckets])
+            masks = None
+            if masked:
+                masks = (C.c_void_p * len(buckets))(*[(b.row_mask.data_ptr() + 8 * (r0 // 64)) if b.row_mask is not None else None
+                                                      for b in buckets])
+            check(lib().olsr_adam_step_groups(r1 - r0, M, F, C.byref(gp), len(buckets), flats, masks, p("means3D"), p("shs"),
+                                              p("opacities"), p("scales"), p("rotations"), p("language"),
+                                              self.exp_avg.data_ptr() + 4 * r0 * W,
+                                              self.exp_avg_sq.data_ptr() + 4 * r0 * W, stream))
+            return
         if len(buckets) > 1 or masked:
             flats = (C.c_void_p * len(buckets))(*[b.flat.data_ptr() + 4 * r0 * W for b in buckets])
             masks = None
@@ -596,6 +655,31 @@ class RasterWorkspace:
                           dL_dsh=torch.empty(P, M, 3, **f32), dL_dscales=torch.empty(P, 3, **f32),
                           dL_drotations=torch.empty(P, 4, **f32), dL_dtau=torch.empty(P, 6, **f32),
                           dL_dtau_sum=torch.empty(6, **f32))
+        self._scene = None
+        self._keep = None
+
+    def resize(self, P):
+        """Follow a map edit: the workspace now renders P Gaussians.  The per-Gaussian buffers (geometry state, radii,
+        n_touched, gradient arrays) are views of allocations that are replaced only when P exceeds them; a carried depth
+        order indexes the old rows and starts again from zeros (no order: the forward sorts)."""
+        P = int(P)
+        L = lib()
+        dev = self.device
+        f32, i32 = dict(dtype=torch.float32, device=dev), dict(dtype=torch.int32, device=dev)
+        if L.olsr_geometry_bytes(P, self.F) > self.geom.numel():
+            self.geom = torch.empty(L.olsr_geometry_bytes(P, self.F), dtype=torch.uint8, device=dev)
+        base = getattr(self, "_per_gaussian", None)
+        if base is None or base["P"] < P:
+            base = dict(P=P, radii=torch.empty(P, **i32), n_touched=torch.empty(P, **i32),
+                        grads={k: torch.empty((P,) + tuple(v.shape[1:]), **f32) for k, v in self.grads.items()
+                               if k != "dL_dtau_sum"})
+            self._per_gaussian = base
+        self.P = P
+        self.out["radii"], self.out["n_touched"] = base["radii"][:P], base["n_touched"][:P]
+        for k, v in base["grads"].items():
+            self.grads[k] = v[:P]
+        if self.depth_order_carry is not None:
+            self.depth_order_carry = torch.zeros(P, **i32)
         self._scene = None
         self._keep = None
 
@@ -785,6 +869,16 @@ class FrameLanes:
 
     def __len__(self):
         return len(self.lanes)
+
+    @property
+    def P(self):
+        return self.lanes[0][0].P
+
+    def resize(self, P):
+        """Every lane's workspace and bucket follow a map edit (RasterWorkspace.resize, GradientBucket.resize)."""
+        for ws, bucket, _ in self.lanes:
+            ws.resize(P)
+            bucket.resize(P)
 
     def next_lane(self):
         lane = self.lanes[self._next % len(self.lanes)]

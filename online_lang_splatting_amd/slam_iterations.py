@@ -14,7 +14,7 @@ Everything numerical happens in libolsr.so (olsr_forward_async, olsr_tracking_lo
 olsr_pose_step, olsr_adam_step); this module only sequences the calls, like the reference's Python does.
 """
 import ctypes as C
-from typing import Dict, Optional, Sequence
+from typing import Callable, Dict, Optional, Sequence
 
 import torch
 
@@ -208,7 +208,8 @@ class MappingStep:
 
     def __init__(self, lanes: FrameLanes, params: Dict[str, torch.Tensor], bg: torch.Tensor, sh_degree: int,
                  cameras: Sequence[Dict], targets: Sequence, lrs: Dict[str, float], exposure=None,
-                 activations=_abi.ACT_ALL, fused_loss="auto", view_ids: Optional[Sequence] = None, carry_order: Optional[bool] = None):
+                 activations=_abi.ACT_ALL, fused_loss="auto", view_ids: Optional[Sequence] = None, carry_order: Optional[bool] = None,
+                 gaussian_map=None, edit_hook: Optional[Callable] = None, record_visibility: bool = False):
         """targets[v] = (gt_image [3,H,W], gt_depth [H,W], gt_language [F,h,w] or None).
         fused_loss: True — the mapping loss is evaluated in the forward composite's epilogue (olsr_forward_async_loss); False —
         olsr_forward_async + olsr_mapping_loss (two kernels; the same cotangents bit for bit, the loss value to summation order);
@@ -226,7 +227,23 @@ class MappingStep:
         None (default) = on with ONE lane only: measured (scripts/probe/mapping_time.py, 12 views, 500 k Gaussians) it takes
         2.5 % off the iteration on the room map and 1.8 % on the volume with one view in flight (4.77 -> 4.65 ms, 8.62 -> 8.46 ms),
         nothing with two, and costs 0.5 % with four — other lanes' composites already hide the sort's dependent launches, and
-        the repair's own work is then extra."""
+        the repair's own work is then extra.
+        gaussian_map (a gaussian_map.GaussianMap; `params` is then ignored): the map owns the parameters, the Adam state and
+        the densification statistics, and may change P between iterations.  Each iteration then adds the step's statistics
+        to the map (the reference's per-view add_densification_stats and max_radii2D update) and, before the Adam step, calls
+        edit_hook(step, total_bucket) — the place of the reference's densify_and_prune / reset_opacity
+        (utils/slam_backend.py:418-445, 716-752).  Whatever the hook edits, the map records which parameter groups it
+        replaced; the step then skips them as the reference's optimizer.step() does (all groups after a topology edit, the
+        opacity group after a reset).  The hook may return "all" or a collection of group names to skip besides.  The next
+        iteration follows the map's new P (FrameLanes.resize; carried depth orders start again, tile-order hints stay).
+        record_visibility: keep each view's radii > 0 and n_touched > 0 of the last iteration (self.visibility[view id],
+        self.touched[view id]): the visibility filters of reset_opacity_nonvisible and the co-visibility count."""
+        self.map, self.edit_hook, self.record_visibility = gaussian_map, edit_hook, bool(record_visibility)
+        self.visibility: Dict = {}
+        self.touched: Dict = {}
+        if gaussian_map is not None:
+            params = gaussian_map.params
+            self._map_edits = gaussian_map.edits
         self.lanes, self.params, self.bg, self.sh_degree = lanes, params, bg, sh_degree
         self.cameras, self.lrs, self.exposure, self.act = cameras, lrs, exposure, activations
         self.view_ids = view_ids
@@ -236,7 +253,9 @@ class MappingStep:
         self._cal = {"n": 0, "pending": [], True: [], False: []}
         self.targets = targets
         ws0 = lanes.lanes[0][0]
-        self.adam = FusedAdam(ws0.P, GradLayout(ws0.M, ws0.F), ws0.device)
+        if gaussian_map is not None and ws0.P != gaussian_map.P:
+            lanes.resize(gaussian_map.P)
+        self.adam = gaussian_map.adam if gaussian_map is not None else FusedAdam(ws0.P, GradLayout(ws0.M, ws0.F), ws0.device)
         self.last_loss = None
         # profile = True: iteration() brackets its caller-side steps (the stand-alone loss kernel, the sum of the lane
         # buckets, the Adam step) with HIP events and leaves (name, ms) pairs in self.stage_ms — for bench.py's breakdown;
@@ -296,7 +315,24 @@ class MappingStep:
             return ev
         return None
 
-    def iteration(self):
+    def _follow_map(self):
+        """A map edit since the last iteration: take the map's parameter views, resize the lanes to its P, drop the carried
+        depth orders (they index the old rows; the tile-order hints are per tile and stay)."""
+        m = self.map
+        self.params = m.params
+        m.new_gradients()   # (this iteration's backward gives every current parameter a gradient)
+        if m.edits != self._map_edits:
+            self._map_edits = m.edits
+            if self.lanes.P != m.P:
+                self.lanes.resize(m.P)
+            self.view_orders = {}
+            self.visibility, self.touched = {}, {}
+
+    def iteration(self, stats: bool = True):
+        """stats=False (with a map): the statistics of this iteration are not added — the reference's co-visibility prune
+        iteration returns before add_densification_stats (utils/slam_backend.py:683-716)."""
+        if self.map is not None:
+            self._follow_map()
         lanes = self.lanes
         dev = lanes.device
         used = []
@@ -319,8 +355,10 @@ class MappingStep:
             if first:
                 used.append(bucket)
             vid = self.view_ids[v] if self.view_ids is not None else v
-            if vid not in self.view_hints:   # (created on the caller's stream, which the lanes are ordered behind)
-                self.view_hints[vid] = self._hint_proto.clone()
+            if vid not in self.view_hints or (self.carry_order and vid not in self.view_orders):
+                # (created on the caller's stream, which the lanes are ordered behind)
+                if vid not in self.view_hints:
+                    self.view_hints[vid] = self._hint_proto.clone()
                 if self.carry_order:
                     self.view_orders[vid] = torch.zeros(ws.P, dtype=torch.int32, device=dev)
                 stream.wait_stream(main)
@@ -338,6 +376,9 @@ class MappingStep:
                     mark("loss:end", stream)
                     if ws.F > 0 and self.targets[v][2] is None:
                         lo["dL_dlanguage"] = None
+                if self.record_visibility:
+                    self.visibility[vid] = ws.out["radii"] > 0
+                    self.touched[vid] = ws.out["n_touched"] > 0
                 ws.backward(lo["dL_dimage"], lo["dL_dlanguage"], lo["dL_ddepth"], bucket=bucket, first=first,
                             bucket_only=True)
                 self.last_loss = lo["loss"]
@@ -362,7 +403,14 @@ class MappingStep:
             for b in used[8:]:
                 used[0].add_bucket(b)
             used = used[:8]
-        self.adam.step(total if multi else used, self.params, self.lrs)
+        if self.map is None:
+            self.adam.step(total if multi else used, self.params, self.lrs)
+        else:
+            if stats:
+                self.map.add_densification_stats(total)
+            skip = self.edit_hook(self, total) if self.edit_hook is not None else None
+            self.map.step(total if multi else used, self.lrs, skip=skip or ())
+            self.params = self.map.params
         mark("adam:end", main)
         if cal_ev is not None:
             end = torch.cuda.Event(enable_timing=True)
