@@ -47,11 +47,11 @@ extern "C" {
  * 2 = synchronisation error: a block of the frame's radix passes or of the row compaction waited for a predecessor's counts
  * until its spin bound ran out — the frame's synchronisation words were overwritten from outside mid-frame.  The library
  * never hangs on that and never writes out of bounds, but the tile lists are garbage: the forward's images must not be used,
- * the backward writes zero gradients.  The synchronising olsr_backward (scratch_alloc != NULL) returns OLSR_ERR_DEVICE; for
- * olsr_forward and for an olsr_backward without status_dev (the reference-shaped bindings) the frame's last kernel raises a
- * flag in mapped host memory and the FIRST olsr_forward / olsr_backward ON THE SAME DEVICE AND STREAM after the GPU got there
- * returns OLSR_ERR_DEVICE (once), the way an asynchronous HIP error surfaces (round 6: the flag is keyed by device and stream —
- * up to 63 pairs, further ones share one word —, so a broken frame on one stream does not fail healthy calls on another). */
+ * the backward writes zero gradients.  For olsr_forward and for an olsr_backward without status_dev (the reference-shaped
+ * bindings) the frame's last kernel raises a flag in mapped host memory and the FIRST olsr_forward / olsr_backward ON THE
+ * SAME DEVICE AND STREAM after the GPU got there returns OLSR_ERR_DEVICE (once), the way an asynchronous HIP error surfaces
+ * (round 6: the flag is keyed by device and stream — up to 63 pairs, further ones share one word —, so a broken frame on one
+ * stream does not fail healthy calls on another). */
 #define OLSR_STATUS_OK 0
 #define OLSR_STATUS_OVERFLOW 1
 #define OLSR_STATUS_SYNC_ERROR 2
@@ -277,11 +277,22 @@ int olsr_forward_async(const olsr_scene *scene,
  * slot) pair that the forward actually blended; the per-Gaussian reduction then sums them in a
  * fixed order (this replaces the reference's float atomicAdd, CR/backward.cu:1176-1198, and
  * makes the gradients bit-reproducible).  The number of such pairs, L <= 4 R, is known on the
- * device after the forward.  Two ways to provide the row buffer, mirroring the forward:
- *   - scratch_alloc != NULL: the function computes L, synchronises once, and asks the callback
- *     for olsr_backward_scratch_bytes(L, F) bytes (what the drop-in Python path does);
+ * device after the forward.  Two ways to provide the row buffer, neither of which synchronises the stream:
+ *   - scratch_alloc != NULL (the drop-in bindings, behind an olsr_forward): the library picks a row count and asks the
+ *     callback for olsr_backward_scratch_bytes(rows, F) bytes.  rows_token is olsr_last_forward_token() taken right after
+ *     the matching olsr_forward (0: none).  The rows are, first that applies: the count that forward posted
+ *     (olsr_live_rows); the bound — 2 rows per instance in the reference mode of 15x15 tiles, else 4 — when the token's
+ *     slot already belongs to a later forward (olsr_live_rows_overwritten); when the bound would cost more than 64 MB and
+ *     an earlier call verified a ratio of rows per instance, a GUESS of 1.5 x ratio x num_rendered + 65536, rounded up to
+ *     a multiple of 128 Ki rows; else olsr_backward_rows.  A guessed backward is launched at once, then the library waits
+ *     up to 20 ms for the exact count; if the guess was too small (that backward wrote zeros) it calls the callback a
+ *     SECOND time, with the exact size, and launches an exact backward on the same stream, which overwrites every output.
+ *     Every exact count updates the process-wide ratio, a slowly decaying maximum: max(now, 0.9 old + 0.1 now)
+ *     (olsr_debug_rows_ratio).  The callback is not called under a library lock.  A second call may release the first
+ *     buffer while the first backward still reads it: the caller's allocator must hand that memory only to work ordered
+ *     behind it on hip_stream, as a stream-ordered caching allocator (PyTorch's) does.
  *   - scratch_alloc == NULL: `scratch` holds olsr_backward_scratch_bytes(scratch_rows, F) bytes;
- *     no synchronisation.  If L > scratch_rows nothing is written and the overflow is reported
+ *     rows_token is ignored.  If L > scratch_rows nothing is written and the overflow is reported
  *     through status_dev.
  * status_dev (device int32[2], may be NULL) receives {L, status}: OLSR_STATUS_OK / _OVERFLOW / _SYNC_ERROR.
  *
@@ -337,19 +348,20 @@ int64_t olsr_live_rows(int32_t token, int32_t packed_survivor_waves);
 /* The same, for a caller that runs ahead of the GPU (a training loop reaches its backward while the forward is still
  * executing): waits — polling the mapped word, the GPU is busy with the forward meanwhile — until the forward has posted
  * its counts, at most timeout_us microseconds, and not at all when the slot already belongs to a later forward.
- * Returns the row count or -1 (then size by the bound).  The drop-in bindings call it when the bound would cost more than
+ * Returns the row count or -1 (then size by the bound).  olsr_backward_rows calls it when the bound would cost more than
  * 64 MB of scratch (OLSR_ROWS_WAIT_US, read once at load, default 5000; 0: never wait). */
 int64_t olsr_live_rows_wait(int32_t token, int32_t packed_survivor_waves, int32_t timeout_us);
 /* 1 when the ring slot of `token` already belongs to a LATER forward (more than 255 forwards were issued before this
  * backward): the count will never be readable, so a caller sizes its scratch by the bound at once instead of guessing and
  * then waiting for a count that cannot arrive. */
 int32_t olsr_live_rows_overwritten(int32_t token);
-/* The bindings' policy in one call: rows to size the backward scratch of (token, R instances, F) with. */
+/* The last step of the drop-in olsr_backward's choice of rows (scratch_alloc != NULL), when it does not guess: the posted
+ * count of (token, R instances, F), waited for when the bound would cost more than 64 MB, else the bound. */
 int64_t olsr_backward_rows(int32_t token, int32_t packed_survivor_waves, int64_t num_rendered, int32_t F);
 int olsr_backward(const olsr_scene *scene, const int32_t *radii,
                   void *geometry_buffer, int32_t num_rendered,
                   void *binning_buffer, const void *image_buffer,
-                  olsr_alloc_fn scratch_alloc, void *scratch_user,
+                  olsr_alloc_fn scratch_alloc, void *scratch_user, int32_t rows_token,
                   void *scratch, int64_t scratch_rows,
                   const float *dL_dout_color, const float *dL_dout_language,
                   const float *dL_dout_depth,
@@ -718,6 +730,11 @@ int olsr_debug_sort_plan(int64_t n, int n_is_capacity, int32_t *keys_per_thread,
  * what its successors see when a status word is lost; spin_limit: polls a look-back makes before it gives up (0 restores the
  * default, 2^22 — seconds; tests use a few thousand).  A negative argument leaves that knob as it is. */
 void olsr_debug_sync_fault(int fault_bits, int spin_limit);
+
+/* The drop-in olsr_backward's guess (scratch_alloc != NULL), process-wide: sets the ratio of rows per instance it guesses
+ * from when ratio >= 0 (packed_survivor_waves != 0: the reference mode of 15x15 tiles), stores in *redone_out (may be NULL)
+ * how many guessed backwards had to be redone exactly so far, and returns the ratio in force. */
+float olsr_debug_rows_ratio(int32_t packed_survivor_waves, float ratio, int32_t *redone_out);
 
 /* Tuning / test knobs of the radix passes, process-wide.  keys_per_thread in {2, 4, 8, 12, 16} pins the instantiation (0:
  * chosen from the input size); resident_blocks > 0 replaces the 256 blocks a round is planned for; legacy != 0 forces the

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("OLSR_LIB") or os.path.join(_HERE, "libolsr.so")
 EXPORTS = (
     "olsr_geometry_bytes", "olsr_image_bytes", "olsr_binning_bytes", "olsr_backward_scratch_bytes", "olsr_last_forward_token", "olsr_live_rows", "olsr_forward", "olsr_forward_async", "olsr_forward_async_loss", "olsr_fused_loss_scratch_bytes",
     "olsr_backward", "olsr_accumulate_gradients", "olsr_sparse_exchange_mask", "olsr_sparse_exchange_scratch_ints", "olsr_sparse_exchange_pack", "olsr_sparse_exchange_unpack", "olsr_mapping_loss", "olsr_mapping_loss_scratch_bytes", "olsr_tracking_loss", "olsr_pose_step", "olsr_pose_step_gated", "olsr_knn_mean_dist2", "olsr_knn_scratch_bytes", "olsr_adam_step", "olsr_adam_step_sum", "olsr_adam_step_masked", "olsr_adam_step_groups", "olsr_map_edit_scratch_bytes", "olsr_map_edit_plan", "olsr_map_edit_apply", "olsr_bucket_add", "olsr_mark_visible", "olsr_geometry_field", "olsr_binning_field", "olsr_image_field",
-    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
+    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
 )
 
 _lib = None
@@ -59,7 +59,7 @@ def lib():
     L.olsr_live_rows_wait.argtypes, L.olsr_live_rows_wait.restype = [i32, i32, i32], i64
     L.olsr_live_rows_overwritten.argtypes, L.olsr_live_rows_overwritten.restype = [i32], i32
     L.olsr_backward_rows.argtypes, L.olsr_backward_rows.restype = [i32, i32, i64, i32], i64
-    L.olsr_backward.argtypes = ([scene_p, vp, vp, i32, vp, vp, _abi.ALLOC_FN, vp, vp, i64] + [vp] * 3 + [vp] * 13
+    L.olsr_backward.argtypes = ([scene_p, vp, vp, i32, vp, vp, _abi.ALLOC_FN, vp, i32, vp, i64] + [vp] * 3 + [vp] * 13
                                 + [C.POINTER(_abi.OlsrGradBucket), vp, vp])
     L.olsr_backward.restype = C.c_int
     L.olsr_accumulate_gradients.argtypes = [i32, i32, i32, i32] + [vp] * 12
@@ -110,6 +110,7 @@ def lib():
     L.olsr_debug_composite_stamps.argtypes, L.olsr_debug_composite_stamps.restype = [vp, C.c_int], None
     L.olsr_debug_sync_fault.argtypes = [C.c_int, C.c_int]
     L.olsr_debug_sync_fault.restype = None
+    L.olsr_debug_rows_ratio.argtypes, L.olsr_debug_rows_ratio.restype = [i32, C.c_float, C.POINTER(i32)], C.c_float
     L.olsr_debug_backward_ordered_scratch_bytes.argtypes, L.olsr_debug_backward_ordered_scratch_bytes.restype = [i64, i32], sz
     L.olsr_debug_backward_ordered.argtypes = [scene_p, vp, i32, vp, vp] + [vp] * 3 + [vp] + [vp] * 6 + [i32, vp]
     L.olsr_debug_backward_ordered.restype = C.c_int

@@ -15,6 +15,7 @@
 #include "olsr_device.h"
 #include "olsr_kernels.h"
 
+#include <algorithm>
 #include <atomic>
 #include <chrono>
 #include <mutex>
@@ -174,6 +175,13 @@ struct RowsRing {
 RowsRing g_rows;
 thread_local int32_t g_last_token = 0;  // token of the last olsr_forward of this thread (0: none)
 thread_local RowsMailbox g_rows_call;
+// The drop-in backward (olsr_backward with scratch_alloc) waits for a posted count, or guesses, only when the bound would
+// cost more scratch than this.
+constexpr size_t ROWS_WAIT_BYTES = (size_t)64 << 20;
+// Gradient rows per instance of the frame whose count the drop-in backward verified last ([1]: packed survivor waves), and
+// how often a guessed scratch size had to be followed by an exact second backward (olsr_debug_rows_ratio).
+std::atomic<float> g_rows_ratio[2] = {{0.f}, {0.f}};
+std::atomic<int32_t> g_rows_redos{0};
 
 // (per-view tile orders of the synchronising entry: described at order_hint_of below)
 using olsr::HINT_HDR;
@@ -612,7 +620,7 @@ int64_t olsr_backward_rows(int32_t token, int32_t packed_survivor_waves, int64_t
   }();
   const int64_t bound = (num_rendered > 0 ? num_rendered : 0) * (packed_survivor_waves ? 2 : 4);
   int64_t v = olsr_live_rows(token, packed_survivor_waves);
-  if (v < 0 && olsr_backward_scratch_bytes(bound, F) > ((size_t)64 << 20))
+  if (v < 0 && olsr_backward_scratch_bytes(bound, F) > ROWS_WAIT_BYTES)
     v = olsr_live_rows_wait(token, packed_survivor_waves, wait_us);
   return (v >= 0 && v <= bound) ? v : bound;
 }
@@ -731,11 +739,11 @@ int olsr_forward_async_loss(const olsr_scene* scene, void* geometry_buffer, void
 
 int olsr_backward(const olsr_scene* scene, const int32_t* radii, void* geometry_buffer, int32_t num_rendered,
                   void* binning_buffer, const void* image_buffer, olsr_alloc_fn scratch_alloc, void* scratch_user,
-                  void* scratch, int64_t scratch_rows, const float* dL_dout_color, const float* dL_dout_language,
-                  const float* dL_dout_depth, float* dL_dmeans2D, float* dL_dconic, float* dL_dopacity,
-                  float* dL_dcolors, float* dL_dlanguage, float* dL_ddepths, float* dL_dmeans3D, float* dL_dcov3D,
-                  float* dL_dsh, float* dL_dscales, float* dL_drotations, float* dL_dtau, float* dL_dtau_sum,
-                  const olsr_grad_bucket* bucket, int32_t* status_dev, void* hip_stream) {
+                  int32_t rows_token, void* scratch, int64_t scratch_rows, const float* dL_dout_color,
+                  const float* dL_dout_language, const float* dL_dout_depth, float* dL_dmeans2D, float* dL_dconic,
+                  float* dL_dopacity, float* dL_dcolors, float* dL_dlanguage, float* dL_ddepths, float* dL_dmeans3D,
+                  float* dL_dcov3D, float* dL_dsh, float* dL_dscales, float* dL_drotations, float* dL_dtau,
+                  float* dL_dtau_sum, const olsr_grad_bucket* bucket, int32_t* status_dev, void* hip_stream) {
   int rc = check_scene(scene, true);
   if (rc != OLSR_OK) return rc;
   const olsr_scene& s = *scene;
@@ -773,59 +781,100 @@ int olsr_backward(const olsr_scene* scene, const int32_t* radii, void* geometry_
   const GeometryState g = GeometryState::carve(geometry_buffer, (size_t)s.P, grad_row(s.F), gb);
   const ImageState im = ImageState::carve(const_cast<void*>(image_buffer), (size_t)d.W * d.H, (size_t)d.ntiles, ib);
   BinningState b = BinningState::carve(binning_buffer, (size_t)num_rendered, bb);
-
-  // compact the partial-gradient rows: one row per (instance, slot) pair the forward blended — unless the forward did
-  // (olsr_scene.backward_row_capacity: rowbase, counters[6] and counters[7] are in place, the backward's last kernel
-  // copies them to status_dev)
+  (void)gb;
+  (void)ib;
+  (void)bb;
   const bool packed_ref15 = (s.bwd_mode == OLSR_BWD_REFERENCE && s.tile == 15);
   const bool rows_compacted = s.backward_row_capacity > 0;
   if (rows_compacted && (scratch_alloc || scratch_rows != s.backward_row_capacity))
     return fail(OLSR_ERR_ARG, "backward_row_capacity: the backward needs a caller-owned scratch of exactly that many rows");
-  if (!rows_compacted) {
-    launch_row_compaction(b.flags, num_rendered, &g.counters[1], packed_ref15, b.rowbase, b.row_status, b.tickets + 8,
-                          scratch_alloc ? 0x7FFFFFFFLL : scratch_rows, g.counters, status_dev, st);
-    STAGE("row_compaction");
-  }
-  if (scratch_alloc) {
-    int32_t c3[3] = {0, 0, 0};  // {live rows, row / instance overflow, synchronisation error}
-    HIP_TRY(hipMemcpyAsync(c3, &g.counters[6], 3 * sizeof(int32_t), hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipStreamSynchronize(st));
-    if (c3[2] != 0)  // (nothing of this frame's lists can be trusted; no gradient has been written)
-      return fail(OLSR_ERR_DEVICE, "device-side synchronisation error: a look-back of this frame's radix sort / row "
-                                   "compaction never received a predecessor's counts (state buffer corrupted mid-frame?)");
-    const int32_t L = c3[0];
-    scratch_rows = L;
-    scratch = scratch_alloc(scratch_user, olsr_backward_scratch_bytes(L, s.F));
-    if (!scratch) return fail(OLSR_ERR_ALLOC, "backward scratch allocation callback returned NULL");
-  }
-  float* rows = (float*)(((uintptr_t)scratch + ALIGN - 1) / ALIGN * ALIGN);
 
-  stamp(st, 2);
-  if (s.bwd_mode == OLSR_BWD_REFERENCE)
-    launch_render_backward_reference(s, F_rows, d, g, b, im, dL_dout_color, dL_dout_language, dL_dout_depth, rows, st);
-  else
-    launch_render_backward_exact(s, F_rows, d, g, b, im, dL_dout_color, dL_dout_language, dL_dout_depth, rows, st);
-  stamp(st, 3);
-  STAGE("render_backward");
-  GradOut o{dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors, dL_dlanguage, dL_ddepths, dL_dmeans3D,
-            dL_dcov3D,   dL_dsh,    dL_dscales,  dL_drotations, dL_dtau,    dL_dtau_sum};
-  if (bucket) {
-    o.bucket_flat = bucket->flat;
-    o.bucket_densify = bucket->densify;
-    o.bucket_max_radii = bucket->max_radii;
-    o.bucket_assign = bucket->assign;
-    o.bucket_row_mask = reinterpret_cast<unsigned long long*>(bucket->row_mask);
+  // one backward whose partial-gradient rows go to `buf`, which holds `capacity` rows
+  auto launch = [&](void* buf, int64_t capacity) -> int {
+    // compact the partial-gradient rows: one row per (instance, slot) pair the forward blended — unless the forward did
+    // (olsr_scene.backward_row_capacity: rowbase, counters[6] and counters[7] are in place, the backward's last kernel
+    // copies them to status_dev)
+    if (!rows_compacted) {
+      launch_row_compaction(b.flags, num_rendered, &g.counters[1], packed_ref15, b.rowbase, b.row_status, b.tickets + 8,
+                            capacity, g.counters, status_dev, st);
+      STAGE("row_compaction");
+    }
+    float* rows = (float*)(((uintptr_t)buf + ALIGN - 1) / ALIGN * ALIGN);
+
+    stamp(st, 2);
+    if (s.bwd_mode == OLSR_BWD_REFERENCE)
+      launch_render_backward_reference(s, F_rows, d, g, b, im, dL_dout_color, dL_dout_language, dL_dout_depth, rows, st);
+    else
+      launch_render_backward_exact(s, F_rows, d, g, b, im, dL_dout_color, dL_dout_language, dL_dout_depth, rows, st);
+    stamp(st, 3);
+    STAGE("render_backward");
+    GradOut o{dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors, dL_dlanguage, dL_ddepths, dL_dmeans3D,
+              dL_dcov3D,   dL_dsh,    dL_dscales,  dL_drotations, dL_dtau,    dL_dtau_sum};
+    if (bucket) {
+      o.bucket_flat = bucket->flat;
+      o.bucket_densify = bucket->densify;
+      o.bucket_max_radii = bucket->max_radii;
+      o.bucket_assign = bucket->assign;
+      o.bucket_row_mask = reinterpret_cast<unsigned long long*>(bucket->row_mask);
+    }
+    o.status_dev = status_dev;
+    o.status_rows = rows_compacted;
+    // (a caller that passes status_dev reads the report there; one that does not — the reference-shaped bindings — gets it
+    //  from the library's next call)
+    o.sticky_error = status_dev ? nullptr : sticky_sync_error_dev(st);
+    launch_preprocess_backward(s, F_rows, d, g, b, rows, radii, o, g.tau_partials, st);
+    STAGE("preprocess_backward");
+    return OLSR_OK;
+  };
+  if (!scratch_alloc) return launch(scratch, scratch_rows);
+
+  // The drop-in policy (include/olsr.h).  A training loop reaches its backward while the forward is still executing; waiting
+  // for the posted count and only then launching left the GPU idle between the forward's last kernel and the backward's first
+  // (13 us per frame at config 3).  So: the count if it is there; else a guess, launched at once and verified while the GPU
+  // works; a guess that was too small (that backward wrote zeros and said so) is followed by an exact second backward on the
+  // same stream, which overwrites every output.
+  const int packed = packed_ref15 ? 1 : 0;
+  const int64_t bound = (int64_t)num_rendered * (packed ? 2 : 4);
+  auto alloc_and_launch = [&](int64_t nrows) -> int {
+    void* buf = scratch_alloc(scratch_user, olsr_backward_scratch_bytes(nrows, s.F));
+    if (!buf) return fail(OLSR_ERR_ALLOC, "backward scratch allocation callback returned NULL");
+    return launch(buf, nrows);
+  };
+  int64_t nrows = olsr_live_rows(rows_token, packed);
+  bool guessed = false;
+  if (nrows < 0 || nrows > bound) {
+    const float ratio = g_rows_ratio[packed].load(std::memory_order_relaxed);
+    if (olsr_live_rows_overwritten(rows_token)) {
+      nrows = bound;  // (the slot belongs to a later forward: no count will ever arrive — no guess, no wait, no second backward)
+    } else if (rows_token > 0 && ratio > 0.f && num_rendered > 0 &&
+               olsr_backward_scratch_bytes(bound, s.F) > ROWS_WAIT_BYTES) {
+      // (rounded up to a multiple of 128 Ki rows — 14 MB at F = 15: a size that changed a little from frame to frame, with the
+      //  decaying ratio, made the caching allocator cut a new block every frame, and every few frames that is a hipMalloc)
+      nrows = (int64_t)(1.5 * (double)ratio * num_rendered) + 65536;
+      nrows = std::min<int64_t>(bound, (nrows + 131071) / 131072 * 131072);
+      guessed = true;
+    } else {
+      nrows = olsr_backward_rows(rows_token, packed, num_rendered, s.F);  // (waits when the bound would cost more than 64 MB)
+    }
   }
-  o.status_dev = status_dev;
-  o.status_rows = rows_compacted;
-  // (a caller that passes status_dev reads the report there; one that does not — the reference-shaped bindings — gets it
-  //  from the library's next call)
-  o.sticky_error = status_dev ? nullptr : sticky_sync_error_dev(st);
-  launch_preprocess_backward(s, F_rows, d, g, b, rows, radii, o, g.tau_partials, st);
-  STAGE("preprocess_backward");
-  (void)gb;
-  (void)ib;
-  (void)bb;
+  rc = alloc_and_launch(nrows);
+  if (rc != OLSR_OK) return rc;
+  int64_t exact = (nrows < bound || bound == 0) ? nrows : -1;
+  if (guessed) {
+    exact = olsr_live_rows_wait(rows_token, packed, 20000);
+    if (exact < 0 || exact > nrows) {
+      g_rows_redos.fetch_add(1, std::memory_order_relaxed);
+      rc = alloc_and_launch((exact < 0 || exact > bound) ? bound : exact);
+      if (rc != OLSR_OK) return rc;
+    }
+  }
+  if (exact >= 0 && num_rendered > 0) {
+    // a slowly decaying maximum: the views of a mapping window differ in rows per instance (the arc views of the benchmark
+    // by 60 %), and a guess sized from the lightest of them would be redone for every heavier one
+    const float now = (float)exact / (float)num_rendered;
+    const float old = g_rows_ratio[packed].load(std::memory_order_relaxed);
+    g_rows_ratio[packed].store(std::max(now, 0.9f * old + 0.1f * now), std::memory_order_relaxed);
+  }
   return OLSR_OK;
 }
 
@@ -1111,6 +1160,13 @@ void olsr_debug_sort_timing(unsigned long long* device_buffer, int max_blocks, i
 void olsr_debug_sync_fault(int fault_bits, int spin_limit) {
   if (fault_bits >= 0) sort_knobs().fault = fault_bits & 3;
   if (spin_limit >= 0) sort_knobs().spin_limit = spin_limit > 0 ? spin_limit : (1 << 22);
+}
+
+float olsr_debug_rows_ratio(int32_t packed_survivor_waves, float ratio, int32_t* redone_out) {
+  std::atomic<float>& r = g_rows_ratio[packed_survivor_waves ? 1 : 0];
+  if (ratio >= 0.f) r.store(ratio);
+  if (redone_out) *redone_out = g_rows_redos.load();
+  return r.load();
 }
 
 void olsr_debug_sort_knobs(int keys_per_thread, int resident_blocks, int legacy) {

@@ -11,8 +11,6 @@
 #include <c10/core/DeviceGuard.h>
 #include <c10/hip/HIPStream.h>
 
-#include <algorithm>
-#include <atomic>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -38,10 +36,11 @@ Tensor prep(const Tensor &t, const char *what) {
 const float *fp(const Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<float>() : nullptr; }
 float *fpw(Tensor &t) { return t.defined() && t.numel() > 0 ? t.data_ptr<float>() : nullptr; }
 
-// resizeFunctional, DGR/rasterize_points.cu:27-33
+// resizeFunctional, DGR/rasterize_points.cu:27-33, with a fresh tensor instead of resize_: resize_ copies the old bytes
+// when it grows a tensor, and the backward's second scratch request replaces a buffer whose contents are dead
 void *resize(void *user, size_t nbytes) {
   Tensor *t = static_cast<Tensor *>(user);
-  t->resize_({static_cast<int64_t>(nbytes)});
+  *t = torch::empty({static_cast<int64_t>(nbytes)}, t->options());
   return t->data_ptr();
 }
 
@@ -137,11 +136,6 @@ std::tuple<int, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, Tensor, 
                          n_touched);
 }
 
-// gradient rows per instance of the frame whose count this process read last ([1]: packed survivor waves), and how often a
-// guessed scratch size had to be followed by an exact second backward (tests / diagnostics)
-std::atomic<float> g_rows_per_instance[2] = {{0.f}, {0.f}};
-std::atomic<int> g_rows_redone{0};
-
 // RasterizeGaussiansBackwardCUDA / RasterizeLanguageGaussiansBackwardCUDA, DGR/rasterize_points.cu:243-331,333-455.
 // Returns {dL_dmeans2D, dL_dcolors, dL_dlanguage, dL_dopacity, dL_dmeans3D, dL_dcov3D, dL_dsh, dL_dscales,
 // dL_drotations, dL_dtau, dL_dtau_sum, dL_dconic, dL_ddepths}; the last two (the reference's internal buffers,
@@ -185,67 +179,20 @@ std::vector<Tensor> backward(int F, const Tensor &bg, const Tensor &means3D, con
   Tensor dc = prep(dL_dout_color, "dL_dout_color"), dl = prep(dL_dout_language, "dL_dout_language"),
          dd = prep(dL_dout_depth, "dL_dout_depth");
   Tensor rad = radii.contiguous();
-  // Row scratch: one partial-gradient row per live (instance, 64-pixel slot) pair (reference mode of 15x15 tiles: per
-  // packed survivor wave).  The caching allocator reuses blocks stream-ordered, so the tensor may die at return.
-  // The forward posts the frame's exact row count to the host; a caller that is ahead of the GPU waits for it (the GPU is
-  // busy with the forward meanwhile) when the bound L <= slots * R would cost more than 64 MB (olsr_backward_rows).
-  // Round 5: a training loop reaches this point while the forward is still executing.  Waiting for its posted count and only
-  // THEN launching left the GPU idle between the forward's last kernel and the backward's first (13 us per frame at config 3).
-  // Now: the count if it is there; else a GUESS — 1.5 x the rows per instance of the frame this process verified last — the
-  // backward is launched with it, and while the GPU works the count is awaited and compared: a guess that was too small (that
-  // backward wrote zeros everywhere and said so) is followed by a second, exact backward on the same stream, which overwrites
-  // every output.  The result is always the exact one; the redo is the price of a scene whose rows per instance jumped by half.
-  const bool packed = (bwd_mode == OLSR_BWD_REFERENCE && tile == 15);
-  const int64_t bound = static_cast<int64_t>(R > 0 ? R : 0) * (packed ? 2 : 4);
-  int64_t rows = olsr_live_rows(rows_token, packed ? 1 : 0);
-  bool guessed = false;
-  if (rows < 0 || rows > bound) {
-    const float ratio = g_rows_per_instance[packed ? 1 : 0].load(std::memory_order_relaxed);
-    if (olsr_live_rows_overwritten(rows_token)) {
-      rows = bound;  // (the slot belongs to a later forward: no count will ever arrive — no guess, no wait, no second backward)
-    } else if (rows_token > 0 && ratio > 0.f && R > 0 && olsr_backward_scratch_bytes(bound, F) > (static_cast<size_t>(64) << 20)) {
-      // (rounded up to a multiple of 128 Ki rows — 14 MB at F = 15: a size that changed a little from frame to frame, with the
-      //  decaying ratio, made the caching allocator cut a new block every frame, and every few frames that is a hipMalloc)
-      rows = static_cast<int64_t>(1.5 * static_cast<double>(ratio) * R) + 65536;
-      rows = std::min<int64_t>(bound, (rows + 131071) / 131072 * 131072);
-      guessed = true;
-    } else {
-      pybind11::gil_scoped_release nogil;
-      rows = olsr_backward_rows(rows_token, packed ? 1 : 0, R, F);  // (waits when the bound would cost more than 64 MB)
-    }
+  // Row scratch: the library sizes it (the forward's posted row count, or a guess it verifies and redoes exactly, see
+  // olsr_backward in include/olsr.h) and resizes `scratch` through the callback, once or twice.  The caching allocator
+  // reuses blocks stream-ordered, so the tensor may die at return.  The GIL is released for the call: the library may wait
+  // for the forward's row count, and the callback only resizes a C++ tensor that no Python object refers to.
+  Tensor scratch = torch::empty({0}, means3D.options().dtype(torch::kUInt8));
+  int rc;
+  {
+    pybind11::gil_scoped_release nogil;
+    rc = olsr_backward(&sc.s, P ? rad.data_ptr<int32_t>() : nullptr, geomBuffer.data_ptr(), R, binningBuffer.data_ptr(),
+                       imageBuffer.data_ptr(), resize, &scratch, rows_token, nullptr, 0, fp(dc), fp(dl), fp(dd), fpw(g[0]),
+                       fpw(g[11]), fpw(g[3]), fpw(g[1]), fpw(g[2]), fpw(g[12]), fpw(g[4]), fpw(g[5]), fpw(g[6]), fpw(g[7]),
+                       fpw(g[8]), fpw(g[9]), fpw(g[10]), nullptr, nullptr, stream_of(means3D));
   }
-  auto launch = [&](int64_t nrows) {
-    Tensor scratch = torch::empty({static_cast<int64_t>(olsr_backward_scratch_bytes(nrows, F))},
-                                  means3D.options().dtype(torch::kUInt8));
-    int rc;
-    {
-      pybind11::gil_scoped_release nogil;  // pure launches, no callback into Python
-      rc = olsr_backward(&sc.s, P ? rad.data_ptr<int32_t>() : nullptr, geomBuffer.data_ptr(), R, binningBuffer.data_ptr(),
-                         imageBuffer.data_ptr(), nullptr, nullptr, scratch.data_ptr(), nrows, fp(dc), fp(dl), fp(dd),
-                         fpw(g[0]), fpw(g[11]), fpw(g[3]), fpw(g[1]), fpw(g[2]), fpw(g[12]), fpw(g[4]), fpw(g[5]),
-                         fpw(g[6]), fpw(g[7]), fpw(g[8]), fpw(g[9]), fpw(g[10]), nullptr, nullptr, stream_of(means3D));
-    }
-    check(rc);
-  };
-  launch(rows);
-  int64_t exact = guessed ? -1 : ((rows < bound || bound == 0) ? rows : -1);
-  if (guessed) {
-    {
-      pybind11::gil_scoped_release nogil;  // (the GPU is busy with the forward and the backward just queued)
-      exact = olsr_live_rows_wait(rows_token, packed ? 1 : 0, 20000);
-    }
-    if (exact < 0 || exact > rows) {
-      g_rows_redone.fetch_add(1, std::memory_order_relaxed);
-      launch((exact < 0 || exact > bound) ? bound : exact);
-    }
-  }
-  if (exact >= 0 && R > 0) {
-    // a slowly decaying maximum: the views of a mapping window differ in rows per instance (the arc views of the benchmark
-    // by 60 %), and a guess sized from the lightest of them would be redone for every heavier one
-    const float now = static_cast<float>(exact) / static_cast<float>(R);
-    const float old = g_rows_per_instance[packed ? 1 : 0].load(std::memory_order_relaxed);
-    g_rows_per_instance[packed ? 1 : 0].store(std::max(now, 0.9f * old + 0.1f * now), std::memory_order_relaxed);
-  }
+  check(rc);
   return g;
 }
 
@@ -272,8 +219,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
   m.def("mark_visible", &mark_visible);
   m.def("last_forward_token", []() { return static_cast<int>(olsr_last_forward_token()); });
   m.def("debug_rows_ratio", [](bool packed, float ratio) {  // ratio < 0: read only.  Returns (ratio in force, backwards redone)
-    if (ratio >= 0.f) g_rows_per_instance[packed ? 1 : 0].store(ratio);
-    return std::make_tuple(g_rows_per_instance[packed ? 1 : 0].load(), g_rows_redone.load());
+    int32_t redone = 0;
+    const float r = olsr_debug_rows_ratio(packed ? 1 : 0, ratio, &redone);
+    return std::make_tuple(r, static_cast<int>(redone));
   });
   m.def("version", []() { return std::string(olsr_version()); });
 }

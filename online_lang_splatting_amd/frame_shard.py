@@ -794,7 +794,7 @@ class RasterWorkspace:
             g = {k: (v if k == "dL_dtau_sum" else None) for k, v in g.items()}
         check(lib().olsr_backward(
             C.byref(self._scene), self.out["radii"].data_ptr(), self.geom.data_ptr(), self.capacity,
-            self.binning.data_ptr(), self.img.data_ptr(), _abi.ALLOC_FN(0), None, self.scratch.data_ptr(),
+            self.binning.data_ptr(), self.img.data_ptr(), _abi.ALLOC_FN(0), None, 0, self.scratch.data_ptr(),
             self.row_capacity, p(dL_dcolor), p(dL_dlanguage), p(dL_ddepth),
             p(g["dL_dmeans2D"]), p(g["dL_dconic"]), p(g["dL_dopacity"]), p(g["dL_dcolors"]), p(g["dL_dlanguage"]),
             p(g["dL_ddepths"]), p(g["dL_dmeans3D"]), p(g["dL_dcov3D"]), p(g["dL_dsh"]), p(g["dL_dscales"]),

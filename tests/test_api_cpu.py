@@ -245,6 +245,24 @@ def test_backward_row_policy_without_a_posted_count(L):
     assert L.olsr_last_forward_token() == 0  # (this thread issued no forward)
 
 
+def test_backward_row_ratio_is_one_per_process_and_mode(L):
+    """olsr_debug_rows_ratio: the rows-per-instance figure the drop-in backward guesses its scratch from is set and read
+    per row layout, it reports the count of redone backwards, and both bindings' debug_rows_ratio read the same figure."""
+    from online_lang_splatting_amd import _C
+    redone = ctypes.c_int32(-1)
+    keep = [L.olsr_debug_rows_ratio(m, -1.0, None) for m in (0, 1)]
+    try:
+        assert L.olsr_debug_rows_ratio(0, 0.25, ctypes.byref(redone)) == 0.25 and redone.value >= 0
+        assert L.olsr_debug_rows_ratio(1, 1.5, None) == 1.5
+        assert L.olsr_debug_rows_ratio(0, -1.0, None) == 0.25  # (setting one mode leaves the other alone)
+        assert _C.debug_rows_ratio(False) == (0.25, redone.value) and _C.debug_rows_ratio(True) == (1.5, redone.value)
+        assert _C.compiled_binding().debug_rows_ratio(True, -1.0) == (1.5, redone.value)
+        assert _C.debug_rows_ratio(True, 0.0) == (0.0, redone.value)
+    finally:
+        for m, r in enumerate(keep):
+            L.olsr_debug_rows_ratio(m, r, None)
+
+
 def test_usable_cpus_respects_affinity_and_quota(monkeypatch, tmp_path):
     """The oracle's thread pool (and bench.py's cpu_baseline `cores`) is sized by the CPUs the container may use — the
     GPU box shows 256 hardware threads and grants 16 — not by os.cpu_count()."""

@@ -902,7 +902,8 @@ def test_corrupted_row_compaction_ticket_is_reported_and_gradients_are_zero(hip)
     """Between a forward and its backward the test overwrites the row compaction's ticket word in the binning buffer: the
     blocks then hold tickets whose predecessors do not exist, their look-back runs into its spin bound.  The library must not
     hang, must not return gradients computed from garbage row offsets, and must say so: status_dev[1] ==
-    OLSR_STATUS_SYNC_ERROR on the sync-free path (zero gradients), OLSR_ERR_DEVICE from the synchronising olsr_backward."""
+    OLSR_STATUS_SYNC_ERROR, with zero gradients.  (A backward without status_dev — the drop-in bindings — reports it through
+    the per-stream flag instead, covered by test_lost_digit_counts_in_a_radix_pass_are_reported.)"""
     from online_lang_splatting_amd._lib import lib
     dev = torch.device(DEV)
     # (rows_in_forward=False: the compaction is the backward's own first launch, so a word corrupted between the forward and
