@@ -594,6 +594,22 @@ int olsr_tracking_loss(const olsr_loss_params *params, const float *image, const
                        float *dL_dimage, float *dL_ddepth, float *loss, float *dL_dexposure,
                        void *scratch, void *hip_stream);
 
+/* ---- colour refinement (third loop of the back end, utils/slam_backend.py:769-819) --------------------------------------
+ * loss = (1 - lambda_dssim) * mean|image - gt_image| + lambda_dssim * (1 - SSIM(image, gt_image)) and its gradient with
+ * respect to `image`.  Replaces l1_loss and ssim (gaussian_splatting/utils/loss_utils.py:21-22, 42-101: 11-tap Gaussian
+ * window, sigma 1.5, normalised in float32, zero padding of 5 without renormalised borders, per channel, C1 = 0.01^2,
+ * C2 = 0.03^2, mean over all 3 H W elements) with their autograd backward: five grouped 11 x 11 convolutions and ~20
+ * elementwise kernels become two launches (one when no gradient is asked for, plus a one-block reduction).  SSIM is also
+ * the reference's evaluation metric (utils/eval_utils.py:174): pass dL_dimage = NULL for the values alone.
+ *   image, gt_image   device float[3,H,W]; any H, W >= 1; gt_image is a constant
+ *   dL_dimage         device float[3,H,W], fully overwritten, or NULL; a tie image == gt_image contributes 0 to the L1 part
+ *   loss              device float[4]: {total, (1 - lambda) L1, lambda (1 - SSIM), SSIM}; deterministic sums, no host read
+ *   scratch           olsr_refinement_loss_scratch_bytes(width, height) bytes (three intermediate [3,H,W] planes) */
+size_t olsr_refinement_loss_scratch_bytes(int32_t width, int32_t height);
+int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim,
+                         const float *image, const float *gt_image, float *dL_dimage, float *loss,
+                         void *scratch, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

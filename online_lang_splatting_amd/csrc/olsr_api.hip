@@ -1011,6 +1011,22 @@ int olsr_tracking_loss(const olsr_loss_params* params, const float* image, const
   return OLSR_OK;
 }
 
+size_t olsr_refinement_loss_scratch_bytes(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0) return ALIGN;
+  return refinement_loss_scratch_bytes(width, height);
+}
+
+int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim, const float* image, const float* gt_image,
+                         float* dL_dimage, float* loss, void* scratch, void* hip_stream) {
+  if (width <= 0 || height <= 0) return fail(OLSR_ERR_ARG, "image size must be positive");
+  if (width > 65535 * 32 || height > 65535 * 16) return fail(OLSR_ERR_ARG, "image size beyond 65535 tiles");
+  if (!image || !gt_image || !loss || !scratch) return fail(OLSR_ERR_ARG, "image, gt_image, loss and scratch are required");
+  launch_refinement_loss(width, height, lambda_dssim, image, gt_image, dL_dimage, loss, scratch, (hipStream_t)hip_stream);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("refinement_loss launch: ") + hipGetErrorString(e));
+  return OLSR_OK;
+}
+
 int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
                               const float* dL_dsh,
                               const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,

@@ -252,4 +252,9 @@ void launch_mapping_loss(const olsr_loss_params& p, const float* image, const fl
                          float* dL_ddepth, float* dL_dlanguage, float* loss, float* dL_dexposure, float* partials,
                          hipStream_t st);
 
+// k_ssim.hip: the colour-refinement loss (1 - lambda) L1 + lambda (1 - SSIM); dL_dimage == nullptr: values only
+size_t refinement_loss_scratch_bytes(int W, int H);
+void launch_refinement_loss(int W, int H, float lambda, const float* image, const float* gt_image, float* dL_dimage,
+                            float* loss, void* scratch, hipStream_t st);
+
 }  // namespace olsr

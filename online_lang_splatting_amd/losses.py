@@ -1,5 +1,6 @@
-"""Host side of olsr_mapping_loss (include/olsr.h): the mapping loss of one view and the cotangents the
-rasterizer backward consumes, in one HIP pass.
+"""Host side of olsr_mapping_loss / olsr_tracking_loss / olsr_refinement_loss (include/olsr.h): the loss of one view and
+the cotangents the rasterizer backward consumes, in one HIP pass (the colour-refinement loss
+with SSIM in two).
 
 Mirrors what utils/slam_backend.py:579-597 + utils/slam_utils.py:124-165 of the reference compute with
 PyTorch ops + autograd:  loss, d loss / d (image, depth, language), d loss / d (exposure_a, exposure_b).
@@ -129,3 +130,72 @@ def tracking_loss(image, depth, opacity, gt_image, gt_depth, grad_mask=None, exp
                                    ptr(out["dL_dexposure"]), scratch.data_ptr(),
                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out
+
+
+def refinement_loss(image, gt_image, *, lambda_dssim=0.2, want_grad=True, buffers=None):
+    """The colour-refinement loss (utils/slam_backend.py:798-801) of one view and its image cotangent (olsr_refinement_loss):
+    (1 - lambda_dssim) * l1_loss(image, gt_image) + lambda_dssim * (1 - ssim(image, gt_image)), image / gt_image [3,H,W].
+    Returns dict(loss[4] = {total, (1 - lambda) L1, lambda (1 - SSIM), SSIM}, dL_dimage [3,H,W] or None);
+    want_grad=False evaluates the values only (the SSIM of the reference's evaluation, utils/eval_utils.py:174).
+    buffers: a dict the caller keeps between calls on images of one size (a loop): outputs and scratch are allocated into it
+    once and reused, so the returned tensors are overwritten by the next call."""
+    image = _image3("refinement_loss: image", image)
+    dev = image.device
+    H, W = image.shape[1], image.shape[2]
+    gt_image = _target("refinement_loss: gt_image", gt_image, (3, H, W), dev)
+    if gt_image is None:
+        raise RuntimeError("refinement_loss: gt_image is required")
+    f32 = dict(dtype=torch.float32, device=dev)
+    L = lib()
+    b = buffers if buffers is not None else {}
+    if b.get("key") != (H, W, dev):
+        b.clear()
+        b.update(key=(H, W, dev), loss=torch.empty(4, **f32), dL_dimage=None,
+                 scratch=torch.empty(L.olsr_refinement_loss_scratch_bytes(W, H), dtype=torch.uint8, device=dev))
+    if want_grad and b["dL_dimage"] is None:
+        b["dL_dimage"] = torch.empty(3, H, W, **f32)
+    out = dict(loss=b["loss"], dL_dimage=b["dL_dimage"] if want_grad else None)
+    scratch = b["scratch"]
+    with torch.cuda.device(dev):
+        check(L.olsr_refinement_loss(W, H, float(lambda_dssim), image.data_ptr(), gt_image.data_ptr(),
+                                     out["dL_dimage"].data_ptr() if want_grad else None, out["loss"].data_ptr(),
+                                     scratch.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return out
+
+
+class _Ssim(torch.autograd.Function):
+    """SSIM through olsr_refinement_loss at lambda = 1: the value is loss[3]; d SSIM / d img1 = -dL_dimage."""
+
+    @staticmethod
+    def forward(ctx, img1, img2):
+        out = refinement_loss(img1.detach(), img2, lambda_dssim=1.0, want_grad=ctx.needs_input_grad[0])
+        ctx.shape = img1.shape
+        ctx.save_for_backward(out["dL_dimage"])
+        return out["loss"][3].clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        (d,) = ctx.saved_tensors
+        if ctx.needs_input_grad[1]:
+            raise RuntimeError("ssim: no gradient is produced for img2 (the target is a constant of olsr_refinement_loss)")
+        return (d * (-grad)).reshape(ctx.shape), None
+
+
+def ssim(img1, img2, window_size=11, size_average=True):
+    """ssim of gaussian_splatting/utils/loss_utils.py:61-69 on the fused entry: img1, img2 [3,H,W] or [1,3,H,W] float32 on
+    the GPU, a 0-d tensor back; differentiable with respect to img1.  Only what the reference's callers use exists: anything
+    else raises (there is no torch fallback)."""
+    if window_size != 11:
+        raise NotImplementedError(f"ssim: window_size must be 11 (the kernel's window is compiled in), got {window_size}")
+    if not size_average:
+        raise NotImplementedError("ssim: size_average=False (per-image means) is not implemented")
+    if not isinstance(img1, torch.Tensor) or not isinstance(img2, torch.Tensor):
+        raise RuntimeError("ssim: img1 and img2 must be tensors")
+    if img2.requires_grad:
+        raise RuntimeError("ssim: no gradient is produced for img2 (detach the target)")
+    shape = tuple(img1.shape)
+    if tuple(img2.shape) != shape or not (len(shape) == 3 or (len(shape) == 4 and shape[0] == 1)) or shape[-3] != 3:
+        raise RuntimeError(f"ssim: img1 and img2 must both be [3,H,W] or [1,3,H,W], got {shape} and {tuple(img2.shape)}")
+    if len(shape) == 4:
+        img1, img2 = img1.reshape(shape[1:]), img2.reshape(shape[1:])
+    return _Ssim.apply(img1, img2)

@@ -10,10 +10,17 @@ TrackingLoop   front end, utils/slam_frontend.py:tracking() (:160-275): up to 10
 MappingStep    back end, utils/slam_backend.py:map() (:499-760): 12 views of the same Gaussians (10 window keyframes +
                2 random), mapping loss incl. the language L1 (:579-597), gradients summed over the views, ONE Adam step.
 
-Everything numerical happens in libolsr.so (olsr_forward_async, olsr_tracking_loss / olsr_mapping_loss, olsr_backward,
-olsr_pose_step, olsr_adam_step); this module only sequences the calls, like the reference's Python does.
+RefinementStep back end, utils/slam_backend.py:color_refinement() (:769-819): 26 000 DEPENDENT iterations of one random
+               keyframe -> (1 - lambda) L1 + lambda (1 - SSIM) on the colour image -> backward -> Adam on every group ->
+               position learning-rate decay.  No densification, pruning or pose update.
+
+Everything numerical happens in libolsr.so (olsr_forward_async, olsr_tracking_loss / olsr_mapping_loss /
+olsr_refinement_loss, olsr_backward, olsr_pose_step, olsr_adam_step); this module only sequences the calls, like the
+reference's Python does.
 """
 import ctypes as C
+import math
+import random
 from typing import Callable, Dict, Optional, Sequence
 
 import torch
@@ -202,6 +209,21 @@ class TrackingLoop:
         return int(self.pose.status[1].item())
 
 
+def _follow_map(step) -> bool:
+    """Shared by the loops that run on a GaussianMap (`step.map`, `step.lanes`, `step.params`, `step._map_edits`): take the
+    map's current parameter views, tell it that this iteration's backward gives every parameter a gradient, and after a
+    topology edit resize the lanes to its P.  Returns True when there was such an edit."""
+    m = step.map
+    step.params = m.params
+    m.new_gradients()
+    if m.edits == step._map_edits:
+        return False
+    step._map_edits = m.edits
+    if step.lanes.P != m.P:
+        step.lanes.resize(m.P)
+    return True
+
+
 class MappingStep:
     """One mapping iteration over `cameras` (all views against the same Gaussians), `lanes` views in flight, gradients
     written / added straight into the flat bucket by the backward kernel, one fused Adam step on the raw parameters."""
@@ -318,13 +340,7 @@ class MappingStep:
     def _follow_map(self):
         """A map edit since the last iteration: take the map's parameter views, resize the lanes to its P, drop the carried
         depth orders (they index the old rows; the tile-order hints are per tile and stay)."""
-        m = self.map
-        self.params = m.params
-        m.new_gradients()   # (this iteration's backward gives every current parameter a gradient)
-        if m.edits != self._map_edits:
-            self._map_edits = m.edits
-            if self.lanes.P != m.P:
-                self.lanes.resize(m.P)
+        if _follow_map(self):
             self.view_orders = {}
             self.visibility, self.touched = {}, {}
 
@@ -443,3 +459,105 @@ class MappingStep:
             for b in self._used[1:]:
                 out.add_(b.flat)
         return out
+
+
+def position_lr(step: int, lr_init: float, lr_final: float, max_steps: int) -> float:
+    """The reference's position learning-rate schedule without delay (gaussian_splatting/utils/general_utils.py:79-94):
+    log-linear from lr_init at step 0 to lr_final at max_steps, constant after; 0 for a negative step or a disabled group."""
+    if step < 0 or (lr_init == 0.0 and lr_final == 0.0):
+        return 0.0
+    t = min(max(step / max_steps, 0.0), 1.0)
+    return math.exp(math.log(lr_init) * (1.0 - t) + math.log(lr_final) * t)
+
+
+class RefinementStep:
+    """The colour-refinement loop on the fused path: per iteration ONE view -> forward -> olsr_refinement_loss -> backward
+    into the bucket -> max_radii2D of that view -> one Adam step on every group -> the xyz rate of the next step.
+
+    Two details of the reference are kept.  Its render() goes through the language rasterizer when the map has language
+    features (gaussian_renderer/__init__.py:39-48) while the loss reads the colour image only: autograd hands the
+    rasterizer a zero language cotangent and optimizer.step() steps the language group with a zero gradient (its moments
+    decay, the leftover momentum still moves it) - here the backward gets a NULL language cotangent, writes zeros into the
+    bucket's language columns, and the group is stepped like the others.  And only max_radii2D is updated
+    (utils/slam_backend.py:809-812): the densification statistics are not.
+    Iterations depend on each other, so one lane (the first of `lanes`) is used; `last_loss` stays on the device."""
+
+    def __init__(self, lanes: FrameLanes, params: Optional[Dict[str, torch.Tensor]], bg: torch.Tensor, sh_degree: int,
+                 cameras: Sequence[Dict], gt_images: Sequence[torch.Tensor], lrs: Dict[str, float], lambda_dssim: float = 0.2,
+                 position_schedule=None, activations=_abi.ACT_ALL, view_ids: Optional[Sequence] = None, gaussian_map=None,
+                 adam: Optional[FusedAdam] = None):
+        """gt_images[v]: [3,H,W], converted once to contiguous float32 on the device.
+        position_schedule = (lr_init, lr_final, max_steps): step i (from 0) runs with xyz rate position_lr(i, ...), as the
+        reference's update_learning_rate(iteration) after every step leaves it (its first step runs with the group's
+        configured rate, which is lr_init); None keeps lrs["xyz"].
+        gaussian_map (`params` is then ignored): the map owns the parameters, the Adam state and max_radii2D; otherwise
+        `params` + `adam` (a FusedAdam; a fresh one when None), and max_radii2D is kept in self.max_radii.
+        view_ids: a stable id per camera keying the per-view tile-order hints (default: its position)."""
+        self.map = gaussian_map
+        if gaussian_map is not None:
+            params = gaussian_map.params
+            self._map_edits = gaussian_map.edits
+        self.lanes, self.params, self.bg, self.sh_degree = lanes, params, bg, sh_degree
+        self.cameras, self.lrs, self.act, self.view_ids = cameras, dict(lrs), activations, view_ids
+        self.lambda_dssim = float(lambda_dssim)
+        ws0 = lanes.lanes[0][0]
+        dev = lanes.device
+        if gaussian_map is not None and ws0.P != gaussian_map.P:
+            lanes.resize(gaussian_map.P)
+        if len(gt_images) != len(cameras):
+            raise ValueError("RefinementStep: one ground-truth image per camera")
+        self.gt_images = [g.detach().to(device=dev, dtype=torch.float32).contiguous() for g in gt_images]
+        if gaussian_map is not None:
+            self.adam = gaussian_map.adam
+            self.max_radii = None
+        else:
+            self.adam = adam if adam is not None else FusedAdam(ws0.P, GradLayout(ws0.M, ws0.F), dev)
+            self.max_radii = torch.zeros(ws0.P, dtype=torch.int32, device=dev)
+        self.schedule = tuple(position_schedule) if position_schedule is not None else None
+        self.steps = 0
+        self.xyz_lr = position_lr(0, *self.schedule) if self.schedule is not None else self.lrs["xyz"]
+        self.last_xyz_lr = None   # the rate the last iteration's step ran with
+        self.last_view = None
+        self.last_loss = None
+        self.view_hints: Dict = {}
+        self._hint_proto = ws0.tile_order.clone()
+        self._loss_buffers: Dict = {}
+
+    def loss(self, image, gt_image):
+        """dict(loss[4], dL_dimage) of one view (olsr_refinement_loss; the buffers are reused between iterations)."""
+        return losses.refinement_loss(image, gt_image, lambda_dssim=self.lambda_dssim, buffers=self._loss_buffers)
+
+    def iteration(self, view: Optional[int] = None):
+        """view: index into `cameras`; None draws one like the reference does (random.randint over the keyframes)."""
+        if self.map is not None:
+            _follow_map(self)
+        v = random.randint(0, len(self.cameras) - 1) if view is None else int(view)
+        ws, bucket, _ = self.lanes.lanes[0]
+        vid = self.view_ids[v] if self.view_ids is not None else v
+        if vid not in self.view_hints:
+            self.view_hints[vid] = self._hint_proto.clone()
+        ws.tile_order = self.view_hints[vid]   # in: this view's order of its last iteration; out: this iteration's
+        ws.depth_order_carry = None            # (a view comes back after many Adam steps: its old depth order proves nothing)
+        ws.set_scene(bg=self.bg, sh_degree=self.sh_degree, activations=self.act, **self.cameras[v], **self.params)
+        out = ws.forward()
+        lo = self.loss(out["color"], self.gt_images[v])
+        ws.backward(lo["dL_dimage"], None, None, bucket=bucket, first=True, bucket_only=True)
+        self.last_loss, self.last_view = lo["loss"], v
+        lrs = dict(self.lrs, xyz=self.xyz_lr)
+        max_radii = self.map.max_radii if self.map is not None else self.max_radii
+        torch.maximum(max_radii, bucket.max_radii, out=max_radii)
+        if self.map is not None:
+            self.map.step([bucket], lrs)   # (honours the groups an edit since the last backward replaced: none here)
+        else:
+            self.adam.step([bucket], self.params, lrs)
+        self.last_xyz_lr = self.xyz_lr
+        self.steps += 1
+        if self.schedule is not None:
+            self.xyz_lr = position_lr(self.steps, *self.schedule)
+        return bucket
+
+    def run(self, n: int, views: Optional[Sequence[int]] = None):
+        """n iterations; views: the view of each (len n), else random ones."""
+        for i in range(n):
+            self.iteration(None if views is None else views[i])
+        return self.last_loss
