@@ -22,6 +22,9 @@ ARCH = "gfx950"
 # (source, object name, extra defines)
 UNITS = [
     ("olsr_api.hip", "olsr_api.o", []),
+    ("olsr_dropin.hip", "olsr_dropin.o", []),
+    ("olsr_entries.hip", "olsr_entries.o", []),
+    ("olsr_diag.hip", "olsr_diag.o", []),
     ("k_preprocess.hip", "k_preprocess.o", []),
     ("k_binning.hip", "k_binning.o", []),
     ("k_sort.hip", "k_sort.o", []),
@@ -40,7 +43,7 @@ UNITS = [
     ("k_map_edit.hip", "k_map_edit.o", []),
     ("k_pose.hip", "k_pose.o", []),
 ]
-HEADERS = ["olsr_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", os.path.join("..", "..", "include", "olsr.h")]
+HEADERS = ["olsr_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", os.path.join("..", "..", "include", "olsr.h")]
 
 
 def hipcc():

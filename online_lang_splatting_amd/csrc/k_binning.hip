@@ -443,8 +443,8 @@ __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
   // from here on (the drop-in entry allocates it after the instance count is known)
   for (int q = (int)(blockIdx.x * EO_T + threadIdx.x); q < bin_sync_quads; q += (int)(gridDim.x * EO_T))
     bin_sync[q] = make_uint4(0u, 0u, 0u, 0u);
-  if (counters[2] != 0) return;  // more instances than the caller's capacity: nothing is emitted (uniform)
-  if (counters[8] != 0) return;  // the depth sort lost a predecessor's counts: its order is garbage, index nothing with it
+  if (counters[CNT_OVERFLOW] != 0) return;  // more instances than the caller's capacity: nothing is emitted (uniform)
+  if (counters[CNT_SYNC_ERROR] != 0) return;  // the depth sort lost a predecessor's counts: its order is garbage, index nothing with it
   const u32 b = blockIdx.x;
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r0 = (int)(b * EMIT_CHUNK + threadIdx.x * EO_PER);  // this thread's four consecutive depth ranks
@@ -522,13 +522,13 @@ __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
     }
   }
   // (the thread that holds the last rank has seen every rank: the number of emitting Gaussians)
-  if ((r0 <= P - 1 && P - 1 < r0 + EO_PER) || (P == 0 && b == 0 && threadIdx.x == 0)) counters[10] = (int32_t)ci;
+  if ((r0 <= P - 1 && P - 1 < r0 + EO_PER) || (P == 0 && b == 0 && threadIdx.x == 0)) counters[CNT_EMITTERS] = (int32_t)ci;
   // the two work lists of the backward's row sums: big footprints from the front, medium ones from the back
-  u32 slot = block_list_base(nbig, &counters[5], s_lsum, &s_lbase);
+  u32 slot = block_list_base(nbig, &counters[CNT_BIG_LIST], s_lsum, &s_lbase);
 #pragma unroll
   for (int k = 0; k < EO_PER; ++k)
     if (n[k] > EMIT_BIG) big_list[slot++] = make_uint4(g[k], off[k], n[k], 0u);
-  u32 mslot = block_list_base(nmid, &counters[4], s_lsum, &s_lbase);
+  u32 mslot = block_list_base(nmid, &counters[CNT_MID_LIST], s_lsum, &s_lbase);
 #pragma unroll
   for (int k = 0; k < EO_PER; ++k)
     if (n[k] > OLSR_MID_FOOTPRINT && n[k] <= EMIT_BIG) big_list[(u32)P_true - 1u - (mslot++)] = make_uint4(g[k], off[k], n[k], 0u);
@@ -569,16 +569,16 @@ __global__ __launch_bounds__(EB_T) void emit_balanced_kernel(
     const u32* __restrict__ order, const u32* __restrict__ rank_off, const u32* __restrict__ win_start,
     const float4* __restrict__ emit_rec, int ellipse, int W, int H, int gx, const int32_t* __restrict__ counters,
     u32* __restrict__ keys, u32* __restrict__ inst_gid, u32 eb_out) {
-  // (order / rank_off: the Gaussian and the first instance of the j-th EMITTING depth rank, j < P = counters[10] —
+  // (order / rank_off: the Gaussian and the first instance of the j-th EMITTING depth rank, j < P = counters[CNT_EMITTERS] —
   //  emit_offsets_kernel's compacted list; "rank" below means a position in that list)
   __shared__ EbGauss s_gs[EB_T];
   __shared__ u32 s_g[EB_T], s_first[EB_T], s_rowoff[EB_T];
   __shared__ uint8_t s_owner[EB_ROWCAP];
   __shared__ u32 s_w[EB_T / 64];
   __shared__ u32 s_flag;
-  if (counters[2] != 0 || counters[8] != 0) return;
-  const u32 R = (u32)counters[1];
-  const int P = counters[10];
+  if (counters[CNT_OVERFLOW] != 0 || counters[CNT_SYNC_ERROR] != 0) return;
+  const u32 R = (u32)counters[CNT_INSTANCES_EFF];
+  const int P = counters[CNT_EMITTERS];
   const u32 o0 = blockIdx.x * eb_out;
   if (o0 >= R) return;
   const u32 o1 = min(o0 + eb_out, R);
@@ -832,7 +832,7 @@ __device__ __forceinline__ void row_compaction_block(const RowCompactionArgs& ra
   const int64_t n = bounded_n(n_host, n_dev);  // flags beyond the instances of this frame are stale
   const int64_t bbase = (int64_t)b * ROWS_CHUNK;
   // (a ticket beyond the grid: the ticket word was not the zero the emission left — corrupted from outside)
-  if (b >= nblocks && threadIdx.x == 0) atomicOr(&counters[8], 1);
+  if (b >= nblocks && threadIdx.x == 0) atomicOr(&counters[CNT_SYNC_ERROR], 1);
   if (b < nblocks && bbase <= n) {  // (the block that holds index n writes the total; later blocks have nothing to do)
     const int64_t base = bbase + (int64_t)threadIdx.x * 16;
     u32 v[16];
@@ -856,7 +856,7 @@ __device__ __forceinline__ void row_compaction_block(const RowCompactionArgs& ra
       total += c;
     }
     __syncthreads();
-    const u32 pre = lb_block_exclusive<ROWS_THREADS>(status, b, total, s_wsum, spin_limit, &counters[8]);
+    const u32 pre = lb_block_exclusive<ROWS_THREADS>(status, b, total, s_wsum, spin_limit, &counters[CNT_SYNC_ERROR]);
     u32 run = pre + wbase + incl - sum;
     // (static indices only: a dynamically indexed private array would be promoted to 64 KB of LDS)
     u32 L = 0;
@@ -881,16 +881,16 @@ __device__ __forceinline__ void row_compaction_block(const RowCompactionArgs& ra
         if (base + k < n) rowbase[base + k] = o[k];
     }
     if (at_n >= 0) {  // the thread whose span holds index n: flags at and beyond n count as zero, so L is the total
-      // a forward that overflowed its instance capacity (counters[2]) emitted nothing: inst_start / rowbase / rows
+      // a forward that overflowed its instance capacity (counters[CNT_OVERFLOW]) emitted nothing: inst_start / rowbase / rows
       // of this frame do not exist, so the backward must not read them — report it like a row-capacity overflow
       // (every later kernel then writes zero gradients)
-      const int32_t ov = ((long long)L > row_capacity || counters[2] != 0) ? 1 : 0;
+      const int32_t ov = ((long long)L > row_capacity || counters[CNT_OVERFLOW] != 0) ? 1 : 0;
       rowbase[n] = L;
-      counters[6] = (int32_t)L;
-      // (a frame whose depth cut-offs hid contributions — counters[9], OLSR_STATUS_CUT_MISS — hands out no gradients either;
+      counters[CNT_LIVE_ROWS] = (int32_t)L;
+      // (a frame whose depth cut-offs hid contributions — counters[CNT_CUT_MISS], OLSR_STATUS_CUT_MISS — hands out no gradients either;
       //  the backward's last kernel reports it as status 3)
-      counters[7] = (ov != 0 || counters[9] != 0) ? 1 : 0;
-      counters[11] = rows_stamp_of(row_capacity);  // "compacted for a scratch of this many rows" (olsr_device.h: frame_unusable)
+      counters[CNT_ROW_OVERFLOW] = (ov != 0 || counters[CNT_CUT_MISS] != 0) ? 1 : 0;
+      counters[CNT_ROWS_STAMP] = rows_stamp_of(row_capacity);  // "compacted for a scratch of this many rows" (olsr_device.h: frame_unusable)
       if (status_dev) {
         status_dev[0] = (int32_t)L;
         status_dev[1] = ov;
@@ -1058,15 +1058,15 @@ __device__ __forceinline__ void tile_order_block(const TileOrderArgs& ta, const 
   if (order_copy != nullptr && hint_slot != nullptr) order_copy += (size_t)hint_slot[0] * (size_t)ntiles;
   dilate_depth_cuts(cd, (int)((by * 8 + bx) * 256 + threadIdx.x),
                     (int)(8 * ny * 256));
-  // the forward's last kernel: a synchronisation error of this frame (olsr_state.h, counters[8]) reaches the caller here.
+  // the forward's last kernel: a synchronisation error of this frame (olsr_state.h, counters[CNT_SYNC_ERROR]) reaches the caller here.
   // (When this launch also compacts the backward's rows — forward_tail_kernel —, an error raised by THOSE blocks, a look-back
   //  of the compaction that gives up, may come after this read: it is then reported by the backward of the frame, through
   //  tau_final_kernel, like any error of a backward-side compaction; a forward that is never followed by a backward uses no
   //  rows, so nothing of what it returned depends on them.  ADVICE round 5.)
-  if (bx == 0 && by == 0 && threadIdx.x == 0 && counters[8] != 0) {
+  if (bx == 0 && by == 0 && threadIdx.x == 0 && counters[CNT_SYNC_ERROR] != 0) {
     if (num_rendered_dev != nullptr) num_rendered_dev[1] = 2;
     if (sticky != nullptr) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  } else if (bx == 0 && by == 0 && threadIdx.x == 0 && counters[9] != 0) {
+  } else if (bx == 0 && by == 0 && threadIdx.x == 0 && counters[CNT_CUT_MISS] != 0) {
     // a tile's depth cut-off may have hidden contributions (OLSR_STATUS_CUT_MISS); an overflow (1) stays
     if (num_rendered_dev != nullptr && num_rendered_dev[1] == 0) num_rendered_dev[1] = 3;
   }
@@ -1146,10 +1146,10 @@ __global__ __launch_bounds__(256) void tile_order_identity_kernel(const u32* __r
   const int i = blockIdx.x * 256 + threadIdx.x;
   if (order_copy != nullptr && hint_slot != nullptr) order_copy += (size_t)hint_slot[0] * (size_t)ntiles;
   dilate_depth_cuts(cd, i, (int)(gridDim.x * 256));
-  if (i == 0 && counters[8] != 0) {
+  if (i == 0 && counters[CNT_SYNC_ERROR] != 0) {
     if (num_rendered_dev != nullptr) num_rendered_dev[1] = 2;
     if (sticky != nullptr) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  } else if (i == 0 && counters[9] != 0) {
+  } else if (i == 0 && counters[CNT_CUT_MISS] != 0) {
     if (num_rendered_dev != nullptr && num_rendered_dev[1] == 0) num_rendered_dev[1] = 3;
   }
   if (i < ntiles) {

@@ -102,7 +102,7 @@ __global__ __launch_bounds__(RR_THREADS) void row_reduce_big_kernel(const float*
   const int lane = threadIdx.x & 63;
   const int wave = (int)(blockIdx.x * (RR_THREADS / 64) + (threadIdx.x >> 6));
   const int nwaves = (int)(gridDim.x * (RR_THREADS / 64));
-  const int nbig = counters[5], count = nbig + counters[4];  // front list, then the medium list from the back
+  const int nbig = counters[CNT_BIG_LIST], count = nbig + counters[CNT_MID_LIST];  // front list, then the medium list from the back
   if (wave >= count || frame_unusable(counters, rows_stamp)) return;
   auto item_at = [&](int i) { return big_list[i < nbig ? i : P - 1 - (i - nbig)]; };
   // Most listed Gaussians lie behind the saturation depth of every tile they cover and have NO row (config 3: 65 k listed,
@@ -930,20 +930,20 @@ __global__ __launch_bounds__(TAU_T) void tau_final_kernel(const float* __restric
                                                          int status_rows) {
   __shared__ float red[TAU_T / 64][6];
   // rows compacted by the forward's last launch (olsr_scene.backward_row_capacity): what launch_row_compaction would have
-  // told the caller — {live rows, row / instance overflow}; a cut-off miss (counters[9], folded into counters[7]) is
+  // told the caller — {live rows, row / instance overflow}; a cut-off miss (counters[CNT_CUT_MISS], folded into counters[CNT_ROW_OVERFLOW]) is
   // reported as 3 below
   // (status_rows = the stamp the rows must carry, olsr_device.h: rows_stamp_of; a forward that did not compact them for this
   //  scratch leaves the backward without rows: zero gradients, reported as an overflow of zero rows)
   if (threadIdx.x == 0 && status_rows != 0 && status_dev != nullptr) {
-    const bool stale = counters[11] != status_rows;
-    status_dev[0] = stale ? 0 : counters[6];
-    status_dev[1] = stale ? 1 : ((counters[7] != 0 && counters[9] == 0) ? 1 : 0);
+    const bool stale = counters[CNT_ROWS_STAMP] != status_rows;
+    status_dev[0] = stale ? 0 : counters[CNT_LIVE_ROWS];
+    status_dev[1] = stale ? 1 : ((counters[CNT_ROW_OVERFLOW] != 0 && counters[CNT_CUT_MISS] == 0) ? 1 : 0);
   }
-  // the backward's last kernel: a synchronisation error of this frame (olsr_state.h, counters[8]) reaches the caller here
-  if (threadIdx.x == 0 && counters[8] != 0) {
+  // the backward's last kernel: a synchronisation error of this frame (olsr_state.h, counters[CNT_SYNC_ERROR]) reaches the caller here
+  if (threadIdx.x == 0 && counters[CNT_SYNC_ERROR] != 0) {
     if (status_dev != nullptr) status_dev[1] = 2;
     if (sticky != nullptr) __hip_atomic_store(sticky, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
-  } else if (threadIdx.x == 0 && counters[9] != 0 && status_dev != nullptr) {
+  } else if (threadIdx.x == 0 && counters[CNT_CUT_MISS] != 0 && status_dev != nullptr) {
     status_dev[1] = 3;  // the forward reported a depth cut-off miss: every gradient of this call is zero (olsr_device.h)
   }
   if (out == nullptr) return;
@@ -990,7 +990,7 @@ static void launch_pb_t(const olsr_scene& s, const FrameDims& d, const GeometryS
   {
     // scratch: the depth sort's key / value buffers are dead once the forward's emission has run (olsr_state.h)
     u32 *act_list = g.key_a, *act_count = g.key_b, *compact = g.val_b;
-    int32_t* total = &g.counters[10];
+    int32_t* total = &g.counters[CNT_EMITTERS];
     preprocess_bwd_kernel<F, true><<<nb, PB_THREADS, bucket_lds, st>>>(
         OLSR_PB_ARGS, nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii, o.bucket_assign, s.activations,
         s.opacities, F_out, o.bucket_row_mask, g.gacc, act_list, act_count, g.blended, rows_stamp_of(s.backward_row_capacity));

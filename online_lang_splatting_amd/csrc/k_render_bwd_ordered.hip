@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void render_bwd_ordered_kernel(
   constexpr int NVP = grad_row(F);  // row stride
   constexpr int FA = F > 0 ? F : 1;
   __shared__ float part[NV][BS];
-  if (frame_unusable(counters) || counters[2] != 0) return;  // (no lists to walk: olsr_state.h)
+  if (frame_unusable(counters) || counters[CNT_OVERFLOW] != 0) return;  // (no lists to walk: olsr_state.h)
   const int t = (int)blockIdx.x;
   const int rank = (int)threadIdx.x;
   const bool lane_ok = rank < BS;  // (blockDim = 256: 31 idle threads on a 15 x 15 tile)
@@ -206,7 +206,7 @@ __global__ __launch_bounds__(256) void gauss_rows_ordered_kernel(int P, int F, i
   float acc[10 + 32];
   const int NV = 10 + F;
   for (int v = 0; v < NV; ++v) acc[v] = 0.f;
-  const bool ok = !(frame_unusable(counters) || counters[2] != 0);
+  const bool ok = !(frame_unusable(counters) || counters[CNT_OVERFLOW] != 0);
   const u32 n = ok ? inst_count[g] : 0u;
   if (n > 0) {
     const u32 u0 = inst_start[g];

@@ -84,9 +84,9 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
 #ifdef OLSR_COMPOSITE_VGPR_FLOOR
   asm volatile("; vgpr floor" ::: OLSR_COMPOSITE_VGPR_FLOOR);  // (experiment: fewer resident waves, room for other frames' kernels)
 #endif
-  // a radix pass of this frame lost a predecessor's counts (olsr_state.h, counters[8]): the lists are garbage and must not be
+  // a radix pass of this frame lost a predecessor's counts (olsr_state.h, counters[CNT_SYNC_ERROR]): the lists are garbage and must not be
   // used as indices — render nothing; the tile-order kernel behind this one reports OLSR_STATUS_SYNC_ERROR
-  if (counters[8] != 0) return;
+  if (counters[CNT_SYNC_ERROR] != 0) return;
   constexpr int BS = TILE * TILE;
   constexpr int FR = feat_row(F);
   constexpr int NA = 4 + F;  // r g b depth lang[F]
@@ -559,7 +559,7 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
   im.ranges, im.ranges, b.inst_gid, b.src, d.W, d.H, d.gx, d.ntiles, g.means2D, g.conic_opacity, g.depths, colors,     \
       s.language_precomp, s.background, im.final_T, im.n_contrib, out_color, out_language, out_depth, out_opacity,     \
       n_touched, b.flags, im.tile_work, order_inout, g.counters, hint_slot,                                             \
-      (s.binning == OLSR_BINNING_ELLIPSE ? s.tile_depth_cut : nullptr), &g.counters[9], g.blended
+      (s.binning == OLSR_BINNING_ELLIPSE ? s.tile_depth_cut : nullptr), &g.counters[CNT_CUT_MISS], g.blended
 
 #if OLSR_FWD_TU_LOSS == 0
 template <int TILE, int F>
@@ -671,14 +671,13 @@ void launch_render_forward_loss(const olsr_scene& s, const FrameDims& d, const G
 void launch_render_forward(const olsr_scene& s, const FrameDims& d, const GeometryState& g, const BinningState& b,
                            const ImageState& im, float* out_color, float* out_language, float* out_depth,
                            float* out_opacity, int32_t* n_touched, uint32_t* tile_order_inout, int32_t* num_rendered_dev,
-                           const olsr_loss_fusion* loss, hipStream_t st) {
-  const RowsMailbox& rm = rows_mailbox_of_this_call();
+                           const olsr_loss_fusion* loss, const ForwardTail& tail, hipStream_t st) {
   if (loss != nullptr)
     launch_render_forward_loss(s, d, g, b, im, out_color, out_language, out_depth, out_opacity, n_touched, tile_order_inout,
-                               rm.hint_slot, *loss, st);
+                               tail.hint_slot, *loss, st);
   else
     launch_render_forward_images(s, d, g, b, im, out_color, out_language, out_depth, out_opacity, n_touched,
-                                 tile_order_inout, rm.hint_slot, st);
+                                 tile_order_inout, tail.hint_slot, st);
   LossFinalArgs lfa{};
   if (loss != nullptr) {
     const olsr_loss_fusion& lf = *loss;
@@ -689,12 +688,12 @@ void launch_render_forward(const olsr_scene& s, const FrameDims& d, const Geomet
     lfa = loss_final_args(reinterpret_cast<const float*>(lf.scratch), d.ntiles, p, lf.tracking != 0, lang_term, use_exposure,
                           lf.loss, lf.dL_dexposure);
   }
-  const ForwardTailRows rows{b.flags, rm.compact_rows_n, &g.counters[1], s.bwd_mode == OLSR_BWD_REFERENCE && s.tile == 15,
-                             b.rowbase, b.row_status, b.tickets + 8, s.backward_row_capacity, g.counters};
-  launch_tile_order(im.tile_work, im.tile_order, tile_order_inout, d.ntiles, im.live_rows, rm.dev, rm.seq, g.counters,
-                    num_rendered_dev, rm.sticky, rm.hint_slot,
+  const ForwardTailRows rows{b.flags, tail.compact_rows_n, &g.counters[CNT_INSTANCES_EFF], s.bwd_mode == OLSR_BWD_REFERENCE && s.tile == 15,
+                             b.rowbase, b.row_status, b.tickets + BT_ROWS, s.backward_row_capacity, g.counters};
+  launch_tile_order(im.tile_work, im.tile_order, tile_order_inout, d.ntiles, im.live_rows, tail.rows_dev, tail.rows_seq, g.counters,
+                    num_rendered_dev, tail.sticky, tail.hint_slot,
                     (s.binning == OLSR_BINNING_ELLIPSE ? s.tile_depth_cut : nullptr), d.gx, d.gy, lfa,
-                    rm.compact_rows_n >= 0 ? &rows : nullptr, st);
+                    tail.compact_rows_n >= 0 ? &rows : nullptr, st);
 }
 #endif
 

@@ -97,7 +97,7 @@ struct FrameHousekeeping {
 };
 
 // One wave: compare the frame's view matrix with the HINT_SLOTS stored ones and name the nearest slot (within HINT_VIEW_TOL per
-// entry), else recycle the least recently used one (olsr_api.hip describes the buffer).  Round 4 ran this as a launch of its
+// entry), else recycle the least recently used one (olsr_dropin.hip describes the buffer).  Round 4 ran this as a launch of its
 // own in front of the forward composite.
 __device__ __forceinline__ void hint_pick_wave(u32* base, const float* __restrict__ view, int lane) {
   float d = __builtin_inff();
@@ -166,17 +166,17 @@ __device__ __forceinline__ void frame_housekeeping(const FrameHousekeeping& hous
       cnt += s_red[1][i];
     }
     const bool ok = (long long)cnt <= house.capacity && cnt <= 0x7FFFFFFFu;
-    house.counters[0] = (int32_t)cnt;
-    house.counters[1] = ok ? (int32_t)cnt : 0;
-    house.counters[2] = ok ? 0 : 1;
-    house.counters[3] = (int32_t)rect;
-    house.counters[4] = 0;
-    house.counters[5] = 0;
-    house.counters[6] = 0;
-    house.counters[7] = 0;
-    house.counters[8] = 0;  // synchronisation error of this frame (olsr_state.h)
-    house.counters[9] = 0;  // a tile with a depth cut-off did not saturate (include/olsr.h, OLSR_STATUS_CUT_MISS)
-    house.counters[11] = 0;  // "the rows of this frame were compacted for a scratch of N rows" (set by the row compaction)
+    house.counters[CNT_INSTANCES] = (int32_t)cnt;
+    house.counters[CNT_INSTANCES_EFF] = ok ? (int32_t)cnt : 0;
+    house.counters[CNT_OVERFLOW] = ok ? 0 : 1;
+    house.counters[CNT_RECT_INSTANCES] = (int32_t)rect;
+    house.counters[CNT_MID_LIST] = 0;
+    house.counters[CNT_BIG_LIST] = 0;
+    house.counters[CNT_LIVE_ROWS] = 0;
+    house.counters[CNT_ROW_OVERFLOW] = 0;
+    house.counters[CNT_SYNC_ERROR] = 0;  // synchronisation error of this frame (olsr_state.h)
+    house.counters[CNT_CUT_MISS] = 0;  // a tile with a depth cut-off did not saturate (include/olsr.h, OLSR_STATUS_CUT_MISS)
+    house.counters[CNT_ROWS_STAMP] = 0;  // "the rows of this frame were compacted for a scratch of N rows" (set by the row compaction)
     if (house.live_rows) {
       house.live_rows[0] = 0;
       house.live_rows[1] = 0;
@@ -186,7 +186,7 @@ __device__ __forceinline__ void frame_housekeeping(const FrameHousekeeping& hous
       house.num_rendered_dev[0] = (int32_t)cnt;
       house.num_rendered_dev[1] = ok ? 0 : 1;
     }
-    if (house.host_mailbox) {  // the drop-in entry's host is polling for the count (olsr_api.hip: PinnedCount)
+    if (house.host_mailbox) {  // the drop-in entry's host is polling for the count (olsr_dropin.hip: PinnedCount)
       __hip_atomic_store(&house.host_mailbox[0], (int32_t)cnt, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       __hip_atomic_store(&house.host_mailbox[1], house.host_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
     }

@@ -10,23 +10,28 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "olsr_state.h"
+
 namespace olsr {
 
 // The backward must not trust this frame's lists / rows: the row scratch was too small, the forward overflowed its instance
-// capacity or a depth cut-off of the forward hid contributions (all three: counters[7], set by the row compaction), or a
-// look-back ran into its spin bound (counters[8], olsr_state.h) — every gradient is then zero.
-// (The cut-off miss, counters[9], is folded into counters[7] by the backward's first kernel instead of being tested here: one
-//  more scalar load in this predicate moved render_bwd_kernel<15,32,...> from 0.502 to 0.52 ms, round 4.)
+// capacity or a depth cut-off of the forward hid contributions (all three: counters[CNT_ROW_OVERFLOW], set by the row
+// compaction), or a look-back ran into its spin bound (counters[CNT_SYNC_ERROR], olsr_state.h) — every gradient is then zero.
+// (The cut-off miss, counters[CNT_CUT_MISS], is folded into counters[CNT_ROW_OVERFLOW] by the backward's first kernel instead
+//  of being tested here: one more scalar load in this predicate moved render_bwd_kernel<15,32,...> from 0.502 to 0.52 ms,
+//  round 4.)
 // rows_stamp (0 = no statement): the backward was told that the FORWARD compacted the gradient rows for a scratch of a given
-// capacity (olsr_scene.backward_row_capacity).  The compaction leaves rows_stamp_of(that capacity) in counters[11], the
-// frame's first kernel clears it: a backward whose expectation does not match — the forward ran without the announcement, or
-// with another capacity, so rowbase / counters[6] / counters[7] are stale or sized for another scratch — reads and writes
-// nothing through them, hands out zero gradients and reports an overflow.
+// capacity (olsr_scene.backward_row_capacity).  The compaction leaves rows_stamp_of(that capacity) in
+// counters[CNT_ROWS_STAMP], the frame's first kernel clears it: a backward whose expectation does not match — the forward ran
+// without the announcement, or with another capacity, so rowbase / counters[CNT_LIVE_ROWS] / counters[CNT_ROW_OVERFLOW] are
+// stale or sized for another scratch — reads and writes nothing through them, hands out zero gradients and reports an
+// overflow.
 __host__ __device__ __forceinline__ int32_t rows_stamp_of(long long row_capacity) {
   return row_capacity > 0 ? (int32_t)((row_capacity & 0x3FFFFFFFll) + 1) : 0;
 }
 __device__ __forceinline__ bool frame_unusable(const int32_t* counters, int32_t rows_stamp = 0) {
-  return (counters[7] | counters[8]) != 0 || (rows_stamp != 0 && counters[11] != rows_stamp);
+  return (counters[CNT_ROW_OVERFLOW] | counters[CNT_SYNC_ERROR]) != 0 ||
+         (rows_stamp != 0 && counters[CNT_ROWS_STAMP] != rows_stamp);
 }
 
 

@@ -1,0 +1,199 @@
+// olsr_diag.hip — diagnostics and test hooks of the C-ABI: profiling marks, composite stamps, the radix passes' knobs and
+// their seeding from the environment, the state buffers' fields by name, and the olsr_debug_* setters.
+#include <hip/hip_runtime.h>
+
+#include <cstdlib>
+#include <cstring>
+#include <vector>
+
+#include "olsr_device.h"
+#include "olsr_host.h"
+
+using namespace olsr;
+
+namespace {
+
+thread_local bool g_profiling = false;
+struct StageMark {
+  const char* name;
+  hipEvent_t ev;
+};
+thread_local std::vector<StageMark> g_marks;
+
+void marks_reset() {
+  for (auto& m : g_marks) (void)hipEventDestroy(m.ev);
+  g_marks.clear();
+}
+
+// Diagnostic (olsr_debug_composite_stamps): one-thread kernels in front of and behind every composite launch write the
+// device's wall clock (100 MHz, common to all XCDs) into a caller's buffer — when did each composite become eligible, when had
+// it finished, on which stream — so that the overlap of several frames in flight can be read without a profiler in the way.
+struct StampState {
+  unsigned long long* buf = nullptr;
+  int capacity = 0;
+  std::atomic<int> next{0};
+} g_stamps;
+__global__ void stamp_kernel(unsigned long long* slot, unsigned long long tag) {
+  slot[0] = wall_clock64();
+  slot[1] = tag;
+}
+
+}  // namespace
+
+namespace olsr {
+
+void mark(const char* name, hipStream_t st) {
+  if (!g_profiling || g_marks.size() >= (1u << 16)) return;
+  StageMark m{name, nullptr};
+  if (hipEventCreate(&m.ev) != hipSuccess) return;
+  (void)hipEventRecord(m.ev, st);
+  g_marks.push_back(m);
+}
+
+void stamp(hipStream_t st, int kind) {
+  if (!g_stamps.buf) return;
+  const int i = g_stamps.next.fetch_add(1);
+  if (i >= g_stamps.capacity) return;
+  stamp_kernel<<<1, 1, 0, st>>>(g_stamps.buf + 2 * (size_t)i, ((unsigned long long)(uintptr_t)st << 8) | (unsigned)kind);
+}
+
+// The radix passes' knobs (olsr_state.h): seeded from the environment once, when the library is loaded
+SortKnobs& sort_knobs() {
+  static SortKnobs k;
+  return k;
+}
+
+}  // namespace olsr
+
+namespace {
+struct SortKnobsFromEnv {
+  SortKnobsFromEnv() {
+    auto num = [](const char* name) {
+      const char* e = std::getenv(name);
+      return e ? std::atoi(e) : 0;
+    };
+    sort_knobs().kpt = num("OLSR_SORT_KPT");
+    sort_knobs().resident = num("OLSR_SORT_RESIDENT");
+    sort_knobs().legacy = num("OLSR_SORT_LEGACY") == 1 ? 1 : 0;
+    if (std::getenv("OLSR_SORT_SMALL")) sort_knobs().small_sort = num("OLSR_SORT_SMALL") != 0 ? 1 : 0;
+    if (std::getenv("OLSR_SORT_COMPACT")) sort_knobs().compact = num("OLSR_SORT_COMPACT") != 0 ? 1 : 0;
+    if (num("OLSR_SORT_THREADS") == 1024 || num("OLSR_SORT_THREADS") == 256) sort_knobs().threads = num("OLSR_SORT_THREADS");
+  }
+} g_sort_knobs_from_env;
+}  // namespace
+
+extern "C" {
+
+const void* olsr_geometry_field(const void* geometry_buffer, int32_t P, int32_t F, const char* name) {
+  const GeometryState g = GeometryState::carve(const_cast<void*>(geometry_buffer), (size_t)P, grad_row(supported_F(F) ? F : 0));
+  if (!std::strcmp(name, "depths")) return g.depths;
+  if (!std::strcmp(name, "means2D")) return g.means2D;
+  if (!std::strcmp(name, "cov3D")) return g.cov3D;
+  if (!std::strcmp(name, "conic_opacity")) return g.conic_opacity;
+  if (!std::strcmp(name, "rgb")) return g.rgb;
+  if (!std::strcmp(name, "clamped")) return g.clamped;
+  if (!std::strcmp(name, "tiles_touched")) return g.tiles_touched;
+  if (!std::strcmp(name, "depth_order")) return g.depth_order;  // (the sort's own buffer: every Gaussian, compaction off)
+  if (!std::strcmp(name, "depth_order_compacted")) return g.gacc;  // u32[counters[CNT_SORTED]]: the emitting Gaussians in depth order
+  if (!std::strcmp(name, "counters")) return g.counters;
+  if (!std::strcmp(name, "emit_totals")) return g.emit_status;
+  if (!std::strcmp(name, "inst_start")) return g.inst_start;
+  if (!std::strcmp(name, "blended")) return g.blended;  // u8[P]: some pixel blended the Gaussian in this frame's forward
+  if (!std::strcmp(name, "carry_miss")) return g.carry_miss;  // u32: != 0 = this frame's carried depth order was not repairable
+  if (!std::strcmp(name, "carry_totals")) return g.carry_totals;
+  if (!std::strcmp(name, "sort_keys")) return g.key_a;  // u32[P] (valid after a forward whose carried order was repaired)
+  return nullptr;
+}
+
+const void* olsr_binning_field(const void* binning_buffer, int64_t num_rendered, int32_t F, const char* name) {
+  (void)F;
+  const BinningState b = BinningState::carve(const_cast<void*>(binning_buffer), (size_t)num_rendered);
+  if (!std::strcmp(name, "inst_gid")) return b.inst_gid;
+  if (!std::strcmp(name, "flags")) return b.flags;
+  if (!std::strcmp(name, "rowbase")) return b.rowbase;
+  if (!std::strcmp(name, "row_sync")) return b.tickets + BT_ROWS;  // {ticket, finished blocks} of the row compaction
+  if (!std::strcmp(name, "key_a")) return b.key_a;
+  if (!std::strcmp(name, "key_b")) return b.key_b;
+  if (!std::strcmp(name, "src")) return b.src;
+  if (!std::strcmp(name, "val_b")) return b.val_b;
+  return nullptr;
+}
+
+const void* olsr_image_field(const void* image_buffer, int32_t width, int32_t height, int32_t tile, const char* name) {
+  const ImageState im =
+      ImageState::carve(const_cast<void*>(image_buffer), (size_t)width * height, tile_count(width, height, tile));
+  if (!std::strcmp(name, "final_T")) return im.final_T;
+  if (!std::strcmp(name, "n_contrib")) return im.n_contrib;
+  if (!std::strcmp(name, "ranges")) return im.ranges;
+  if (!std::strcmp(name, "tile_work")) return im.tile_work;    // [2][tiles]
+  if (!std::strcmp(name, "tile_order")) return im.tile_order;  // [tiles]
+  return nullptr;
+}
+
+void olsr_set_profiling(int enable) {
+  g_profiling = enable != 0;
+  marks_reset();
+}
+
+int olsr_get_stage_times(const char** names, float* ms, int max) {
+  if (g_marks.size() < 2) return 0;
+  (void)hipEventSynchronize(g_marks.back().ev);
+  int n = 0;
+  for (size_t i = 1; i < g_marks.size() && n < max; ++i) {
+    if (!std::strcmp(g_marks[i].name, "begin")) continue;  // interval between two calls
+    float t = 0.f;
+    if (hipEventElapsedTime(&t, g_marks[i - 1].ev, g_marks[i].ev) != hipSuccess) t = -1.f;
+    names[n] = g_marks[i].name;
+    ms[n] = t;
+    ++n;
+  }
+  return n;
+}
+
+void olsr_debug_sort_timing(unsigned long long* device_buffer, int max_blocks, int max_launches) {
+  debug_set_sort_timing(device_buffer, max_blocks, max_launches);
+}
+
+void olsr_debug_sync_fault(int fault_bits, int spin_limit) {
+  if (fault_bits >= 0) sort_knobs().fault = fault_bits & 3;
+  if (spin_limit >= 0) sort_knobs().spin_limit = spin_limit > 0 ? spin_limit : (1 << 22);
+}
+
+void olsr_debug_sort_knobs(int keys_per_thread, int resident_blocks, int legacy) {
+  if (keys_per_thread >= 0) sort_knobs().kpt = keys_per_thread;
+  if (resident_blocks >= 0) sort_knobs().resident = resident_blocks;
+  if (legacy >= 0) sort_knobs().legacy = legacy ? 1 : 0;
+}
+
+void olsr_debug_composite_stamps(unsigned long long* device_buffer, int capacity) {
+  g_stamps.buf = device_buffer;
+  g_stamps.capacity = device_buffer ? capacity : 0;
+  g_stamps.next = 0;
+}
+
+int olsr_debug_sort_threads(int threads) {
+  if (threads == 0 || threads == 256 || threads == 1024) sort_knobs().threads = threads;
+  return sort_knobs().threads.load();
+}
+
+void olsr_debug_sort_compact(int enable) {
+  if (enable >= 0) sort_knobs().compact.store(enable ? 1 : 0, std::memory_order_relaxed);
+}
+
+void olsr_debug_sort_small(int enable) {
+  if (enable >= 0) sort_knobs().small_sort = enable ? 1 : 0;
+}
+
+int olsr_debug_sort_plan(int64_t n, int n_is_capacity, int32_t* keys_per_thread, int32_t* blocks) {
+  const SortPlan p = sort_plan((long long)n, n_is_capacity != 0);
+  if (keys_per_thread) *keys_per_thread = p.kpt;
+  if (blocks) *blocks = p.nblk;
+  return fused_sort_applicable(n, 32) ? 1 : 0;
+}
+
+size_t olsr_debug_backward_ordered_scratch_bytes(int64_t num_rendered, int32_t F) {
+  if (num_rendered < 0 || !supported_F(F)) return 0;
+  return align_up((size_t)num_rendered * (size_t)grad_row(F) * sizeof(float)) + align_up((size_t)num_rendered) + 2 * ALIGN;
+}
+
+}  // extern "C"

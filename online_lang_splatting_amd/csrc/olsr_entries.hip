@@ -1,0 +1,271 @@
+// olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits.
+#include <hip/hip_runtime.h>
+
+#include "olsr_host.h"
+
+using namespace olsr;
+
+namespace {
+
+// The checks and the launch of every Adam entry.  who: the entry's name in its messages, or nullptr for olsr_adam_step, whose
+// one bucket is checked with the parameter arrays; params_error: what is wrong with the entry's own parameter struct, if
+// anything.
+int adam_entry(const char* who, int32_t P, int32_t M, int32_t F, const olsr_adam_params* hp, const char* params_error,
+               int32_t n_flats, const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
+               float* opacities, float* scales, float* rotations, float* language, float* exp_avg, float* exp_avg_sq,
+               void* hip_stream, const int32_t* group_step = nullptr, unsigned skip_mask = 0u) {
+  if (P < 0 || M < 0 || !supported_F(F)) return fail(OLSR_ERR_ARG, "P, M must be >= 0 and F one of 0, 3, 15, 16, 32");
+  if (params_error) return fail(OLSR_ERR_ARG, params_error);
+  if (who) {
+    if (n_flats < 1 || n_flats > OLSR_ADAM_MAX_BUCKETS || !flats)
+      return fail(OLSR_ERR_ARG, std::string(who) + ": between 1 and 8 gradient buckets");
+    for (int b = 0; b < n_flats; ++b)
+      if (!flats[b]) return fail(OLSR_ERR_ARG, std::string(who) + ": a gradient bucket is NULL");
+  }
+  if (P == 0) return OLSR_OK;
+  if ((!who && !flats[0]) || !means3D || !opacities || !scales || !rotations || !exp_avg || !exp_avg_sq || (M > 0 && !shs) ||
+      (F > 0 && !language))
+    return fail(OLSR_ERR_ARG, std::string(who ? "" : "the bucket, ") + "every parameter array and both moment buffers are required");
+  launch_adam_step(P, M, F, *hp, flats, reinterpret_cast<const unsigned long long* const*>(row_masks), n_flats, means3D, shs,
+                   opacities, scales, rotations, language, exp_avg, exp_avg_sq, (hipStream_t)hip_stream, group_step, skip_mask);
+  return launch_check(who ? who : "adam_step");
+}
+
+const char* adam_params_error(const olsr_adam_params* params) {
+  return (!params || params->step < 1) ? "adam params are required and step must be >= 1" : nullptr;
+}
+
+}  // namespace
+
+extern "C" {
+
+int olsr_mark_visible(int32_t P, const float* means3D, const float* viewmatrix, const float* projmatrix,
+                      uint8_t* present, void* hip_stream) {
+  (void)projmatrix;  // the reference computes p_hom and discards it (CR/auxiliary.h:149-151)
+  if (P < 0) return fail(OLSR_ERR_ARG, "P must be >= 0");
+  if (P == 0) return OLSR_OK;
+  if (!means3D || !viewmatrix || !present) return fail(OLSR_ERR_ARG, "means3D, viewmatrix and present are required");
+  launch_mark_visible(P, means3D, viewmatrix, present, (hipStream_t)hip_stream);
+  return launch_check("mark_visible");
+}
+
+int olsr_adam_step(int32_t P, int32_t M, int32_t F, const olsr_adam_params* params, const float* flat, float* means3D,
+                   float* shs, float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
+                   float* exp_avg_sq, void* hip_stream) {
+  const float* one[1] = {flat};
+  return adam_entry(nullptr, P, M, F, params, adam_params_error(params), 1, one, nullptr, means3D, shs, opacities, scales,
+                    rotations, language, exp_avg, exp_avg_sq, hip_stream);
+}
+
+int olsr_adam_step_sum(int32_t P, int32_t M, int32_t F, const olsr_adam_params* params, int32_t n_flats,
+                       const float* const* flats, float* means3D, float* shs, float* opacities, float* scales,
+                       float* rotations, float* language, float* exp_avg, float* exp_avg_sq, void* hip_stream) {
+  return olsr_adam_step_masked(P, M, F, params, n_flats, flats, nullptr, means3D, shs, opacities, scales, rotations, language,
+                               exp_avg, exp_avg_sq, hip_stream);
+}
+
+int olsr_adam_step_masked(int32_t P, int32_t M, int32_t F, const olsr_adam_params* params, int32_t n_flats,
+                          const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
+                          float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
+                          float* exp_avg_sq, void* hip_stream) {
+  return adam_entry("adam_step_sum", P, M, F, params, adam_params_error(params), n_flats, flats, row_masks, means3D, shs,
+                    opacities, scales, rotations, language, exp_avg, exp_avg_sq, hip_stream);
+}
+
+int olsr_adam_step_groups(int32_t P, int32_t M, int32_t F, const olsr_adam_group_params* params, int32_t n_flats,
+                          const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
+                          float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
+                          float* exp_avg_sq, void* hip_stream) {
+  const char* params_error = params ? nullptr : "adam group params are required";
+  for (int g = 0; params && g < OLSR_ADAM_GROUPS; ++g)
+    if (!((params->skip_mask >> g) & 1) && params->group_step[g] < 1)
+      params_error = "adam_step_groups: the step count of every group that steps must be >= 1";
+  return adam_entry("adam_step_groups", P, M, F, params ? &params->base : nullptr, params_error, n_flats, flats, row_masks,
+                    means3D, shs, opacities, scales, rotations, language, exp_avg, exp_avg_sq, hip_stream,
+                    params ? params->group_step : nullptr, params ? (unsigned)params->skip_mask : 0u);
+}
+
+int olsr_pose_step(const olsr_pose_params* params, const float* dL_dtau_sum, const float* dL_dexposure,
+                   const float* projection_matrix, float* state, int32_t* status, void* hip_stream) {
+  return olsr_pose_step_gated(params, dL_dtau_sum, dL_dexposure, projection_matrix, state, status, nullptr, hip_stream);
+}
+
+int olsr_pose_step_gated(const olsr_pose_params* params, const float* dL_dtau_sum, const float* dL_dexposure,
+                         const float* projection_matrix, float* state, int32_t* status, const int32_t* frame_status,
+                         void* hip_stream) {
+  if (!params || !projection_matrix || !state || !status)
+    return fail(OLSR_ERR_ARG, "pose params, projection_matrix, state and status are required");
+  // (step <= 0 with a gradient: the step count is status[1] + 1, kept on the device — see include/olsr.h)
+  if (!dL_dtau_sum && dL_dexposure) return fail(OLSR_ERR_ARG, "an exposure gradient needs a pose gradient (one optimiser step)");
+  launch_pose_step(*params, dL_dtau_sum, dL_dexposure, projection_matrix, state, status, frame_status,
+                   (hipStream_t)hip_stream);
+  return launch_check("pose_step");
+}
+
+size_t olsr_knn_scratch_bytes(int32_t P) { return knn_scratch_bytes(P); }
+
+int olsr_knn_mean_dist2(int32_t P, const float* points, float* mean_dist2, void* scratch, void* hip_stream) {
+  if (P < 0) return fail(OLSR_ERR_ARG, "P must be >= 0");
+  if (P == 0) return OLSR_OK;
+  if (!points || !mean_dist2 || !scratch) return fail(OLSR_ERR_ARG, "points, mean_dist2 and scratch are required");
+  launch_knn(P, points, mean_dist2, scratch, (hipStream_t)hip_stream);
+  return launch_check("knn");
+}
+
+size_t olsr_mapping_loss_scratch_bytes(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0) return ALIGN;
+  return (size_t)loss_blocks(width, height) * 5 * sizeof(float) + ALIGN;
+}
+
+int olsr_mapping_loss(const olsr_loss_params* params, const float* image, const float* depth, const float* language,
+                      const float* gt_image, const float* gt_depth, const float* gt_language, const float* exposure,
+                      float* dL_dimage, float* dL_ddepth, float* dL_dlanguage, float* loss, float* dL_dexposure,
+                      void* scratch, void* hip_stream) {
+  if (!params) return fail(OLSR_ERR_ARG, "loss params are NULL");
+  const olsr_loss_params& p = *params;
+  if (p.width <= 0 || p.height <= 0) return fail(OLSR_ERR_ARG, "image size must be positive");
+  if (!supported_F(p.F)) return fail(OLSR_ERR_ARG, "F (language channels) must be one of 0, 3, 15, 16, 32");
+  if (!image || !depth || !gt_image || !gt_depth || !dL_dimage || !dL_ddepth || !loss || !scratch)
+    return fail(OLSR_ERR_ARG, "image, depth, their targets, their gradient outputs, loss and scratch are required");
+  if (p.F > 0 && (!language || !dL_dlanguage)) return fail(OLSR_ERR_ARG, "language and dL_dlanguage are required when F > 0");
+  if (p.F > 0 && gt_language && (p.lang_width <= 0 || p.lang_height <= 0))
+    return fail(OLSR_ERR_ARG, "the language target size must be positive");
+  hipStream_t st = (hipStream_t)hip_stream;
+  float* partials = align_ptr<float>(scratch);
+  launch_mapping_loss(p, image, depth, language, gt_image, gt_depth, p.F > 0 ? gt_language : nullptr, exposure, nullptr,
+                      nullptr, false, dL_dimage, dL_ddepth, dL_dlanguage, loss, dL_dexposure, partials, st);
+  return launch_check("mapping_loss");
+}
+
+int olsr_tracking_loss(const olsr_loss_params* params, const float* image, const float* depth, const float* opacity,
+                       const float* gt_image, const float* gt_depth, const float* grad_mask, const float* exposure,
+                       float* dL_dimage, float* dL_ddepth, float* loss, float* dL_dexposure, void* scratch,
+                       void* hip_stream) {
+  if (!params) return fail(OLSR_ERR_ARG, "loss params are NULL");
+  const olsr_loss_params& p = *params;
+  if (p.width <= 0 || p.height <= 0) return fail(OLSR_ERR_ARG, "image size must be positive");
+  if (!image || !depth || !opacity || !gt_image || !gt_depth || !dL_dimage || !dL_ddepth || !loss || !scratch)
+    return fail(OLSR_ERR_ARG, "image, depth, opacity, their targets, the gradient outputs, loss and scratch are required");
+  hipStream_t st = (hipStream_t)hip_stream;
+  float* partials = align_ptr<float>(scratch);
+  launch_mapping_loss(p, image, depth, nullptr, gt_image, gt_depth, nullptr, exposure, opacity, grad_mask, true, dL_dimage,
+                      dL_ddepth, nullptr, loss, dL_dexposure, partials, st);
+  return launch_check("tracking_loss");
+}
+
+size_t olsr_refinement_loss_scratch_bytes(int32_t width, int32_t height) {
+  if (width <= 0 || height <= 0) return ALIGN;
+  return refinement_loss_scratch_bytes(width, height);
+}
+
+int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim, const float* image, const float* gt_image,
+                         float* dL_dimage, float* loss, void* scratch, void* hip_stream) {
+  if (width <= 0 || height <= 0) return fail(OLSR_ERR_ARG, "image size must be positive");
+  if (width > 65535 * 32 || height > 65535 * 16) return fail(OLSR_ERR_ARG, "image size beyond 65535 tiles");
+  if (!image || !gt_image || !loss || !scratch) return fail(OLSR_ERR_ARG, "image, gt_image, loss and scratch are required");
+  launch_refinement_loss(width, height, lambda_dssim, image, gt_image, dL_dimage, loss, scratch, (hipStream_t)hip_stream);
+  return launch_check("refinement_loss");
+}
+
+int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
+                              const float* dL_dsh,
+                              const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,
+                              const float* dL_dlanguage, const float* dL_dmeans2D, const int32_t* radii, float* flat,
+                              float* densify, int32_t* max_radii, void* hip_stream) {
+  if (P < 0 || M < 0 || F < 0) return fail(OLSR_ERR_ARG, "P, M, F must be >= 0");
+  if (P == 0) return OLSR_OK;
+  if (!dL_dmeans3D || !dL_dopacity || !dL_dscales || !dL_drotations || !dL_dmeans2D || !radii || !flat || !densify ||
+      !max_radii || (M > 0 && !dL_dsh) || (F > 0 && !dL_dlanguage))
+    return fail(OLSR_ERR_ARG, "gradient, radii and accumulator pointers must not be NULL");
+  launch_accumulate(P, M, F, assign != 0, dL_dmeans3D, dL_dsh, dL_dopacity, dL_dscales, dL_drotations, dL_dlanguage, dL_dmeans2D,
+                    radii, flat, densify, max_radii, (hipStream_t)hip_stream);
+  return launch_check("accumulate");
+}
+
+int olsr_bucket_add(int32_t P, int32_t width, float* dst_flat, float* dst_densify, int32_t* dst_max_radii,
+                    uint64_t* dst_row_mask, const float* src_flat, const float* src_densify, const int32_t* src_max_radii,
+                    const uint64_t* src_row_mask, void* hip_stream) {
+  if (P < 0 || width <= 0) return fail(OLSR_ERR_ARG, "P must be >= 0, width > 0");
+  if (P == 0) return OLSR_OK;
+  if (!dst_flat || !dst_densify || !dst_max_radii || !src_flat || !src_densify || !src_max_radii)
+    return fail(OLSR_ERR_ARG, "bucket_add: flat, densify and max_radii of both buckets are required");
+  launch_bucket_add(P, width, dst_flat, src_flat, reinterpret_cast<unsigned long long*>(dst_row_mask),
+                    reinterpret_cast<const unsigned long long*>(src_row_mask), dst_densify, src_densify, dst_max_radii,
+                    src_max_radii, (hipStream_t)hip_stream);
+  return launch_check("bucket_add");
+}
+
+int olsr_sparse_exchange_mask(int32_t P, int32_t width, const float* flat, const uint64_t* row_mask, const int32_t* max_radii,
+                              int32_t* imax, void* hip_stream) {
+  if (P < 0 || width <= 0) return fail(OLSR_ERR_ARG, "P must be >= 0, width > 0");
+  if (P == 0) return OLSR_OK;
+  if (!flat || !max_radii || !imax) return fail(OLSR_ERR_ARG, "flat, max_radii and imax must not be NULL");
+  launch_exchange_mask(P, width, flat, reinterpret_cast<const unsigned long long*>(row_mask), max_radii, imax,
+                       (hipStream_t)hip_stream);
+  return launch_check("sparse exchange (mask)");
+}
+
+int64_t olsr_sparse_exchange_scratch_ints(int32_t P) { return P <= 0 ? 0 : ((int64_t)P + 1023) / 1024; }
+
+int olsr_sparse_exchange_pack(int32_t P, int32_t width, int32_t capacity, const float* flat, const int32_t* imax,
+                              int32_t* max_radii, uint64_t* row_mask, const float* densify, int32_t* idx, float* fsum,
+                              int32_t* scratch, int32_t* status_dev, void* hip_stream) {
+  if (P < 0 || width <= 0 || capacity <= 0) return fail(OLSR_ERR_ARG, "P must be >= 0, width and capacity > 0");
+  if (P == 0) return OLSR_OK;
+  if (!flat || !imax || !max_radii || !densify || !scratch || !status_dev || ((idx == nullptr) != (fsum == nullptr)))
+    return fail(OLSR_ERR_ARG, "sparse exchange (pack): only row_mask may be NULL, or idx and fsum together (count only)");
+  launch_exchange_pack(P, width, capacity, flat, imax, max_radii, reinterpret_cast<unsigned long long*>(row_mask), densify, idx,
+                       fsum, scratch, status_dev, (hipStream_t)hip_stream);
+  return launch_check("sparse exchange (pack)");
+}
+
+int olsr_sparse_exchange_unpack(int32_t P, int32_t width, int32_t capacity, const int32_t* idx, const float* fsum, float* flat,
+                                float* densify, void* hip_stream) {
+  if (P < 0 || width <= 0 || capacity <= 0) return fail(OLSR_ERR_ARG, "P must be >= 0, width and capacity > 0");
+  if (P == 0) return OLSR_OK;
+  if (!idx || !fsum || !flat || !densify) return fail(OLSR_ERR_ARG, "sparse exchange (unpack): pointers must not be NULL");
+  launch_exchange_unpack(P, width, capacity, idx, fsum, flat, densify, (hipStream_t)hip_stream);
+  return launch_check("sparse exchange (unpack)");
+}
+
+size_t olsr_map_edit_scratch_bytes(int32_t P) { return map_edit_scratch_bytes(P); }
+
+static bool map_buffers_complete(const olsr_map_buffers* b, int32_t M, int32_t F) {
+  return b && b->means3D && b->opacities && b->scales && b->rotations && (M == 0 || b->shs) && (F == 0 || b->language) &&
+         b->exp_avg && b->exp_avg_sq && b->kf_id && b->n_obs && b->stats && b->max_radii;
+}
+
+int olsr_map_edit_plan(int32_t P, const olsr_map_edit_params* params, const olsr_map_buffers* src, const uint8_t* drop_mask,
+                       void* scratch, int32_t* status, void* hip_stream) {
+  if (P < 0 || !params || !src || !scratch || !status) return fail(OLSR_ERR_ARG, "map_edit_plan: P >= 0, params, src, scratch and status are required");
+  if (params->mode != OLSR_MAP_EDIT_DENSIFY && params->mode != OLSR_MAP_EDIT_MASK) return fail(OLSR_ERR_ARG, "map_edit_plan: unknown mode");
+  if (params->n_append < 0) return fail(OLSR_ERR_ARG, "map_edit_plan: n_append must be >= 0");
+  if (params->mode == OLSR_MAP_EDIT_DENSIFY && params->n_append != 0)
+    return fail(OLSR_ERR_ARG, "map_edit_plan: densify mode appends nothing");
+  if (P > 0 && params->mode == OLSR_MAP_EDIT_DENSIFY && (!src->stats || !src->scales || !src->opacities))
+    return fail(OLSR_ERR_ARG, "map_edit_plan: densify mode reads stats, scales and opacities");
+  launch_map_edit_plan(P, *params, *src, drop_mask, scratch, status, (hipStream_t)hip_stream);
+  return launch_check("map_edit_plan");
+}
+
+int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_params* params, const olsr_map_buffers* src,
+                        const float* z, const olsr_map_buffers* append, const void* scratch, const int32_t* status,
+                        int32_t P_new, int32_t dst_capacity, const olsr_map_buffers* dst, int32_t* src_index,
+                        void* hip_stream) {
+  if (P < 0 || M < 0 || !supported_F(F) || !params || !scratch || !status)
+    return fail(OLSR_ERR_ARG, "map_edit_apply: P, M >= 0, F one of 0, 3, 15, 16, 32; params, scratch and status are required");
+  if (P_new > dst_capacity) return fail(OLSR_ERR_CAPACITY, "map_edit_apply: P_new exceeds the destination's capacity");
+  if (P_new == 0) return OLSR_OK;
+  if (!map_buffers_complete(dst, M, F) || !src_index) return fail(OLSR_ERR_ARG, "map_edit_apply: every destination buffer is required");
+  if (P > 0 && !map_buffers_complete(src, M, F)) return fail(OLSR_ERR_ARG, "map_edit_apply: every source buffer is required");
+  if (P > 0 && params->mode == OLSR_MAP_EDIT_DENSIFY && !z) return fail(OLSR_ERR_ARG, "map_edit_apply: densify mode needs z [P,2,3]");
+  if (params->n_append > 0 && (!append || !append->means3D || !append->opacities || !append->scales || !append->rotations ||
+                               (M > 0 && !append->shs)))
+    return fail(OLSR_ERR_ARG, "map_edit_apply: the appended rows need means3D, shs, opacities, scales and rotations");
+  launch_map_edit_apply(P, M, F, *params, *src, z, append, scratch, status, dst_capacity, *dst, src_index,
+                        (hipStream_t)hip_stream);
+  return launch_check("map_edit_apply");
+}
+
+}  // extern "C"

@@ -9,8 +9,8 @@
 namespace olsr {
 
 // Large-footprint Gaussians go through wave-per-Gaussian kernels.  The forward's emission builds two work lists in
-// geometry big_list: listed in more than OLSR_BIG_FOOTPRINT tiles (from the front, count in counters[5]: emission
-// and row sums) and in OLSR_MID_FOOTPRINT+1 .. OLSR_BIG_FOOTPRINT tiles (from the back, count in counters[4]: row
+// geometry big_list: listed in more than OLSR_BIG_FOOTPRINT tiles (from the front, count in counters[CNT_BIG_LIST]: emission
+// and row sums) and in OLSR_MID_FOOTPRINT+1 .. OLSR_BIG_FOOTPRINT tiles (from the back, count in counters[CNT_MID_LIST]: row
 // sums only — a lane still emits 32 instances faster than a wave does, but sums that many gradient rows slower).
 constexpr uint32_t OLSR_BIG_FOOTPRINT = 32;
 constexpr uint32_t OLSR_MID_FOOTPRINT = 12;
@@ -43,10 +43,10 @@ int launch_radix_sort(const SortBuffers& b, int64_t n_host, const int32_t* n_dev
 void launch_emit(const olsr_scene& s, const FrameDims& d, const GeometryState& g, const BinningState& b,
                  int64_t bin_sync_words, int64_t n_host, const uint32_t* order, const uint32_t* alt_totals,
                  const uint32_t* alt_unless, const int32_t* n_order_dev, hipStream_t st);
-// exclusive scan of popcount(flags) over [0, n] -> rowbase[0..n] in one kernel; counters[6] = total live rows,
-// counters[7] = (total > row_capacity) or the forward's instance overflow
+// exclusive scan of popcount(flags) over [0, n] -> rowbase[0..n] in one kernel; counters[CNT_LIVE_ROWS] = total live rows,
+// counters[CNT_ROW_OVERFLOW] = (total > row_capacity) or the forward's instance overflow
 // packed_ref15: rows per instance = packed survivor waves (flag bits 4-5) instead of forward slots (bits 0-3)
-// row_status / sync: BinningState::row_status and tickets + 8 (zeroed by the forward, re-zeroed by the kernel itself)
+// row_status / sync: BinningState::row_status and tickets + BT_ROWS (zeroed by the forward, re-zeroed by the kernel itself)
 void launch_row_compaction(const uint8_t* flags, int64_t n_host, const int32_t* n_dev, bool packed_ref15,
                            uint32_t* rowbase, uint32_t* row_status, uint32_t* sync, int64_t row_capacity,
                            int32_t* counters, int32_t* status_dev, hipStream_t st);
@@ -80,14 +80,6 @@ void launch_tile_order(const uint32_t* tile_work, uint32_t* tile_order, uint32_t
                        uint32_t* live_rows, int32_t* rows_mailbox, int32_t rows_seq, const int32_t* counters,
                        int32_t* num_rendered_dev, int32_t* sticky_error, const uint32_t* hint_slot, float* depth_cut,
                        int gx, int gy, const LossFinalArgs& loss_final, const ForwardTailRows* rows, hipStream_t st);
-struct RowsMailbox {  // set by olsr_forward for the duration of one call (thread-local in olsr_api.hip)
-  int32_t* dev = nullptr;
-  int32_t seq = 0;
-  int32_t* sticky = nullptr;  // device view of the process-wide "a frame had a synchronisation error" host word (may be null)
-  const uint32_t* hint_slot = nullptr;  // word 0 = which of the stream's per-view tile orders this frame uses (olsr_api.hip)
-  int64_t compact_rows_n = -1;  // >= 0: the forward's last launch also compacts the backward's rows (the instance capacity)
-};
-RowsMailbox& rows_mailbox_of_this_call();
 // ranges must have been zeroed (launch_instance_offsets); also clears flags[0, n)
 void launch_tile_ranges(const uint32_t* sorted_keys, int64_t n_host, const int32_t* n_dev, uint32_t* ranges,
                         uint8_t* flags, hipStream_t st);
@@ -105,10 +97,10 @@ struct FusedHouse {  // the frame's bookkeeping done by block 0 of the depth sor
   int32_t* host_mailbox;  // (may be null) device view of two host words: receives {R, host_seq}, in this order
   int32_t host_seq;
   uint32_t* live_rows;    // ImageState::live_rows (zeroed by the kernel)
-  uint32_t* hint_base;    // (may be null) the stream's per-view tile orders (olsr_api.hip: order_hint_of): the kernel picks this
+  uint32_t* hint_base;    // (may be null) the stream's per-view tile orders (olsr_dropin.hip: order_hint_of): the kernel picks this
   const float* view;      //   frame's slot by its view matrix (hint_pick_wave)
 };
-// per-view tile orders of the synchronising entry (olsr_api.hip): [0] chosen slot, [1] use counter, [4, 4 + S) last use of every
+// per-view tile orders of the synchronising entry (olsr_dropin.hip): [0] chosen slot, [1] use counter, [4, 4 + S) last use of every
 // slot, then S x 16 floats (view matrices, NaN = empty), then S x ntiles orders
 constexpr int HINT_SLOTS = 16;
 constexpr int HINT_HDR = 4 + HINT_SLOTS + 16 * HINT_SLOTS;  // words in front of the orders
@@ -157,12 +149,22 @@ void launch_order_repair(int P, uint32_t* carry, const uint32_t* keys, uint32_t*
                          hipStream_t st);
 void launch_emit_totals(const uint32_t* order, int P, const uint32_t* inst_count, uint32_t* emit_totals, hipStream_t st);
 
+// what only the forward's last launch (the tile-order kernel) needs, filled by forward_impl (olsr_api.hip); the defaults are
+// those of the sync-free entries
+struct ForwardTail {
+  int32_t* rows_dev = nullptr;  // device view of the four mapped host words that receive the frame's gradient-row counts, and
+  int32_t rows_seq = 0;         // the sequence number that goes with them (the synchronising entry; olsr_dropin.hip)
+  int32_t* sticky = nullptr;  // device view of the (device, stream)'s "a frame had a synchronisation error" host word (may be null)
+  const uint32_t* hint_slot = nullptr;  // word 0 = which of the stream's per-view tile orders this frame uses (olsr_dropin.hip)
+  int64_t compact_rows_n = -1;  // >= 0: the forward's last launch also compacts the backward's rows (the instance capacity)
+};
+
 // k_render_fwd.hip
 // loss (may be null): evaluate the mapping / tracking loss in the composite's epilogue (olsr_forward_async_loss)
 void launch_render_forward(const olsr_scene& s, const FrameDims& d, const GeometryState& g, const BinningState& b,
                            const ImageState& im, float* out_color, float* out_language, float* out_depth,
                            float* out_opacity, int32_t* n_touched, uint32_t* tile_order_inout, int32_t* num_rendered_dev,
-                           const olsr_loss_fusion* loss, hipStream_t st);
+                           const olsr_loss_fusion* loss, const ForwardTail& tail, hipStream_t st);
 
 // k_render_bwd.hip
 // (two translation units, one per backward mode, so they compile in parallel)
@@ -192,7 +194,7 @@ struct GradOut {
   int bucket_assign = 0;
   unsigned long long* bucket_row_mask = nullptr;  // olsr_grad_bucket.row_mask (include/olsr.h)
   int32_t* status_dev = nullptr;  // olsr_backward's {L, overflow}: the last kernel raises [1] to 2 on a synchronisation error
-  int32_t* sticky_error = nullptr;  // ... and sets this mapped host word (RowsMailbox::sticky), if there is one
+  int32_t* sticky_error = nullptr;  // ... and sets this mapped host word (ForwardTail::sticky), if there is one
   bool status_rows = false;  // the rows were compacted by the forward: the last kernel also writes status_dev = {L, overflow}
 };
 // F_rows: language channels of `rows` (see above); with F_rows == 0 < s.F the language gradients are written as zeros

@@ -24,6 +24,9 @@ namespace olsr {
 
 constexpr size_t ALIGN = 256;
 inline size_t align_up(size_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
+// a caller's buffer rounded up to ALIGN (the *_bytes functions reserve the slack)
+template <typename T = void>
+inline T* align_ptr(const void* p) { return reinterpret_cast<T*>(align_up(reinterpret_cast<uintptr_t>(p))); }
 
 // elements handled by one block of the radix passes / scans
 constexpr int SORT_CHUNK = 4096;
@@ -62,7 +65,7 @@ struct SortKnobs {
   // look-back makes before it gives up and raises the frame's synchronisation error
   std::atomic<int> fault{0}, spin_limit{1 << 22};
 };
-SortKnobs& sort_knobs();  // olsr_api.hip
+SortKnobs& sort_knobs();  // olsr_diag.hip
 inline int sort_plan_resident_blocks() {
   const int x = sort_knobs().resident.load(std::memory_order_relaxed);
   return x > 0 ? x : 256;
@@ -138,7 +141,7 @@ struct Carver {
   char* base;
   size_t off = 0;
   // a non-null base is rounded up to ALIGN (total() reserves the slack)
-  explicit Carver(void* b) : base(b ? (char*)(((uintptr_t)b + ALIGN - 1) / ALIGN * ALIGN) : nullptr) {}
+  explicit Carver(void* b) : base(b ? align_ptr<char>(b) : nullptr) {}
   template <typename T>
   T* take(size_t count) {
     off = align_up(off);
@@ -148,6 +151,39 @@ struct Carver {
   }
   size_t total() const { return align_up(off) + ALIGN; }
 };
+
+// GeometryState::counters: the frame's 32-bit bookkeeping words
+enum Counter {
+  CNT_INSTANCES = 0,       // R: total instances
+  CNT_INSTANCES_EFF = 1,   // R_eff (0 on overflow)
+  CNT_OVERFLOW = 2,        // overflow flag: more instances than the caller's capacity
+  CNT_RECT_INSTANCES = 3,  // instances of the reference's rect binning (== R unless OLSR_BINNING_ELLIPSE)
+  CNT_MID_LIST = 4,        // #large-footprint Gaussians (backward): the medium list, from the back of big_list
+  CNT_BIG_LIST = 5,        // same for the emission (forward): the front list of big_list
+  CNT_LIVE_ROWS = 6,       // live rows L
+  CNT_ROW_OVERFLOW = 7,    // row-capacity overflow
+  CNT_SYNC_ERROR = 8,      // synchronisation error: a look-back of a radix pass or of the row compaction ran into its spin
+                           // bound (a status word corrupted mid-frame).  Reset by the frame's first kernel; the forward
+                           // reports it as num_rendered_dev[1] = 2, the backward writes zero gradients and reports
+                           // status_dev[1] = 2 / OLSR_ERR_DEVICE (include/olsr.h)
+  CNT_CUT_MISS = 9,        // a tile with a depth cut-off did not saturate (OLSR_STATUS_CUT_MISS)
+  CNT_EMITTERS = 10,       // Gaussians that emit instances (the length of the emission's compacted rank list)
+  CNT_ROWS_STAMP = 11,     // the rows were compacted for a scratch of this capacity (olsr_device.h: rows_stamp_of)
+  CNT_SORTED = 12,         // Gaussians the depth sort ordered (the emitting ones) when it compacted its input
+  CNT_WORDS = 16           // [13..15] reserved
+};
+// GeometryState::tickets: dynamic block ids and flags among the zeroed synchronisation words
+enum GeometryTicket {
+  GT_DEPTH_PASS = 0,   // [0..3] one per depth pass
+  GT_EMIT = 4,         // scan + emit
+  GT_CARRY_MISS = 12,  // GeometryState::carry_miss
+};
+// BinningState::tickets
+enum BinningTicket {
+  BT_TILE_PASS = 0,  // [0..3] one per tile-sort pass
+  BT_ROWS = 8,       // row compaction: its ticket, then [9] its done counter
+};
+constexpr int TICKET_WORDS = 16;  // of either tickets array
 
 struct GeometryState {
   float* depths;          // [P]
@@ -169,26 +205,15 @@ struct GeometryState {
   uint32_t* inst_start;   // [P] Gaussian id -> emission index of its first instance
   uint32_t* radix_table;  // [256 * sort_blocks(P)]
   uint32_t* scan_partials;  // [scan_blocks(max(P, table))]
-  int32_t* counters;      // [16]: 0 = R (total instances), 1 = R_eff (0 on overflow), 2 = overflow flag,
-                          //      3 = instances of the reference's rect binning (== R unless OLSR_BINNING_ELLIPSE),
-                          //      4 = #large-footprint Gaussians (backward), 5 = same for the emission (forward),
-                          //      6 = live rows L, 7 = row-capacity overflow,
-                          //      8 = synchronisation error: a look-back of a radix pass or of the row compaction ran into its
-                          //          spin bound (a status word corrupted mid-frame).  Reset by the frame's first kernel; the
-                          //          forward reports it as num_rendered_dev[1] = 2, the backward writes zero gradients and
-                          //          reports status_dev[1] = 2 / OLSR_ERR_DEVICE (include/olsr.h),
-                          //      9 = a tile with a depth cut-off did not saturate (OLSR_STATUS_CUT_MISS),
-                          //      10 = Gaussians that emit instances (the length of the emission's compacted rank list),
-                          //      11 = the rows were compacted for a scratch of this capacity (olsr_device.h: rows_stamp_of),
-                          //      12 = Gaussians the depth sort ordered (the emitting ones) when it compacted its input.  [13..15] reserved
+  int32_t* counters;      // [CNT_WORDS], indexed by Counter
   float* tau_partials;    // [6 * ceil(P/128)] scratch of the backward's deterministic dL_dtau reduction
   float* gacc;            // [P][grad_row(F)] backward scratch: per-Gaussian sum of its instance rows
   uint4* big_list;        // [P] work lists {id, first instance, #instances} built by the emission: large footprints from
-                          //     the front (count: counters[5]), medium ones from the back (count: counters[4])
+                          //     the front (count: CNT_BIG_LIST), medium ones from the back (count: CNT_MID_LIST)
   // ---- words the fused kernels synchronise through; zeroed by preprocess at the start of every forward
   uint32_t* sync_words;   // start of the zeroed region
   size_t sync_count;      // its length in 32-bit words
-  uint32_t* tickets;      // [16] dynamic block ids: 0-3 depth passes, 4 scan+emit; [12] = carry_miss (below)
+  uint32_t* tickets;      // [TICKET_WORDS], indexed by GeometryTicket
   uint32_t* sort_hist;    // [4][256] digit totals of the four depth passes
   uint32_t* sort_status;  // [4][blocks][256] per-block digit counts of the depth passes (bit 31 = published)
   uint32_t* emit_status;  // [ceil(P / EMIT_CHUNK)] x 64 bit: per-block totals for the emission (emit_total_pack above)
@@ -196,8 +221,8 @@ struct GeometryState {
   uint32_t* part_count;   // [ceil(P / 256)] ... and instances this frame emits
   uint32_t* part_vis;     // [ceil(P / 256)] ... and Gaussians that emit any (the depth sort orders only those, k_sort.hip)
   uint32_t* carry_totals; // [ceil(P / EMIT_CHUNK) + 1] x 64 bit: the same totals for a REPAIRED carried depth order (k_order_carry.hip)
-  uint32_t* carry_miss;   // one of the zeroed words (tickets[12]): != 0 = the carried order could not be repaired, the radix passes run
-  static GeometryState carve(void* buf, size_t P, int grad_row_floats, size_t& bytes) {
+  uint32_t* carry_miss;   // one of the zeroed words (GT_CARRY_MISS): != 0 = the carried order could not be repaired, the radix passes run
+  static GeometryState carve(void* buf, size_t P, int grad_row_floats, size_t* bytes = nullptr) {
     Carver c(buf);
     GeometryState g;
     g.depths = c.take<float>(P);
@@ -218,18 +243,18 @@ struct GeometryState {
     const size_t table = 256 * (size_t)sort_blocks((long long)P);
     g.radix_table = c.take<uint32_t>(table);
     g.scan_partials = c.take<uint32_t>((size_t)scan_blocks((long long)(table > P ? table : P)) + 1);
-    g.counters = c.take<int32_t>(16);
+    g.counters = c.take<int32_t>(CNT_WORDS);
     g.tau_partials = c.take<float>(6 * ((P + 127) / 128) + 6);
     g.gacc = c.take<float>(P * (size_t)grad_row_floats);
     g.big_list = c.take<uint4>(P);
     {
       const size_t st_words = fused_status_words((long long)P, 4);
       const size_t emit_blocks = 2 * ((P + EMIT_CHUNK - 1) / EMIT_CHUNK + 1);  // 64-bit look-back words
-      g.sync_count = 16 + 4 * 256 + st_words + emit_blocks;
+      g.sync_count = TICKET_WORDS + 4 * 256 + st_words + emit_blocks;
       g.sync_count = (g.sync_count + 3) / 4 * 4;  // zeroed with 16-byte stores
       g.sync_words = c.take<uint32_t>(g.sync_count);
       g.tickets = g.sync_words;
-      g.sort_hist = g.tickets + 16;
+      g.sort_hist = g.tickets + TICKET_WORDS;
       g.emit_status = g.sort_hist + 4 * 256;
       g.sort_status = g.emit_status + emit_blocks;
     }
@@ -237,8 +262,8 @@ struct GeometryState {
     g.part_count = c.take<uint32_t>((P + 255) / 256 + 1);
     g.part_vis = c.take<uint32_t>((P + 255) / 256 + 1);
     g.carry_totals = c.take<uint32_t>(2 * ((P + EMIT_CHUNK - 1) / EMIT_CHUNK + 1));
-    g.carry_miss = g.tickets + 12;
-    bytes = c.total();
+    g.carry_miss = g.tickets + GT_CARRY_MISS;
+    if (bytes) *bytes = c.total();
     return g;
   }
 };
@@ -253,7 +278,7 @@ struct ImageState {
   uint32_t* live_rows;  // [4] {live (instance, slot) pairs, live (instance, packed survivor wave) pairs, -, blocks done} of
                         //     the frame: the backward's gradient-row count in its two row layouts, summed from tile_work
                         //     by the tile-order kernel when a host mailbox wants them
-  static ImageState carve(void* buf, size_t N, size_t tiles, size_t& bytes) {
+  static ImageState carve(void* buf, size_t N, size_t tiles, size_t* bytes = nullptr) {
     Carver c(buf);
     ImageState s;
     s.final_T = c.take<float>(N);
@@ -262,7 +287,7 @@ struct ImageState {
     s.tile_work = c.take<uint32_t>(2 * tiles);
     s.tile_order = c.take<uint32_t>(tiles);
     s.live_rows = c.take<uint32_t>(4);
-    bytes = c.total();
+    if (bytes) *bytes = c.total();
     return s;
   }
 };
@@ -280,11 +305,11 @@ struct BinningState {
   // ---- words the fused kernels synchronise through; zeroed by the emission at the start of every forward
   uint32_t* sync_words;
   size_t sync_count;
-  uint32_t* tickets;     // [16]: 0-3 tile-sort passes, 8 row compaction, 9 its done counter
+  uint32_t* tickets;     // [TICKET_WORDS], indexed by BinningTicket
   uint32_t* tile_hist;   // [4][256] digit totals of the tile-sort passes
   uint32_t* tile_status; // [4][blocks][256]
   uint32_t* row_status;  // [ceil((R + 1) / ROWS_CHUNK)] x 64 bit: per-block live-row totals of the row compaction
-  static BinningState carve(void* buf, size_t R, size_t& bytes) {
+  static BinningState carve(void* buf, size_t R, size_t* bytes = nullptr) {
     Carver c(buf);
     BinningState b;
     b.key_a = c.take<uint32_t>(R);
@@ -300,15 +325,15 @@ struct BinningState {
     {
       const size_t st_words = fused_status_words((long long)R, 4);
       const size_t row_blocks = 2 * ((R + 1 + ROWS_CHUNK - 1) / ROWS_CHUNK + 1);  // 64-bit look-back words
-      b.sync_count = 16 + 4 * 256 + st_words + row_blocks;
+      b.sync_count = TICKET_WORDS + 4 * 256 + st_words + row_blocks;
       b.sync_count = (b.sync_count + 3) / 4 * 4;
       b.sync_words = c.take<uint32_t>(b.sync_count);
       b.tickets = b.sync_words;
-      b.tile_hist = b.tickets + 16;
+      b.tile_hist = b.tickets + TICKET_WORDS;
       b.row_status = b.tile_hist + 4 * 256;
       b.tile_status = b.row_status + row_blocks;  // last: only the part a frame's passes use is zeroed
     }
-    bytes = c.total();
+    if (bytes) *bytes = c.total();
     return b;
   }
 };

@@ -315,3 +315,188 @@ def test_weak_scaling_poses_are_side_by_side_and_centred():
         assert len(cams) == n and all(torch.equal(c.R, ident.R) for c in cams)
         assert abs(float(tx.sum())) < 1e-6 and torch.allclose(tx[1:] - tx[:-1], torch.full((n - 1,), 0.015), atol=1e-6)
         assert float(tx.abs().max()) <= 0.015 * 3.5 + 1e-6
+
+
+def _argument_error_table(L):
+    """(label, call, return code, olsr_last_error()) of every argument check that several entries share.  Pointers that
+    only have to be non-NULL are a made-up address: each call returns before anything could follow it."""
+    import ctypes as C
+    from online_lang_splatting_amd import _abi
+    ARG, CAP = _abi.OLSR_ERR_ARG, _abi.OLSR_ERR_CAPACITY
+    X = 0x1000
+    nine = [X] * 9                                  # the parameter arrays and both moment buffers
+    ok, step0 = _abi.OlsrAdamParams(), _abi.OlsrAdamParams()
+    ok.step, step0.step = 1, 0
+    gok, gstep0 = _abi.OlsrAdamGroupParams(), _abi.OlsrAdamGroupParams()
+    for g in range(7):
+        gok.group_step[g] = gstep0.group_step[g] = 1
+    gstep0.group_step[3] = 0
+    one, hole = (C.c_void_p * 1)(X), (C.c_void_p * 2)(X, None)
+    bad_F = "P, M must be >= 0 and F one of 0, 3, 15, 16, 32"
+    bad_step = "adam params are required and step must be >= 1"
+    no_params = "every parameter array and both moment buffers are required"
+    rows = [
+        ("adam_step F", lambda: L.olsr_adam_step(10, 16, 7, ok, X, *nine, None), ARG, bad_F),
+        ("adam_step step", lambda: L.olsr_adam_step(10, 16, 15, step0, X, *nine, None), ARG, bad_step),
+        ("adam_step no params", lambda: L.olsr_adam_step(10, 16, 15, None, X, *nine, None), ARG, bad_step),
+        ("adam_step NULL bucket", lambda: L.olsr_adam_step(10, 16, 15, ok, None, *nine, None), ARG,
+         "the bucket, " + no_params),
+        ("adam_step NULL parameters", lambda: L.olsr_adam_step(10, 16, 15, ok, X, *([None] * 9), None), ARG,
+         "the bucket, " + no_params),
+        ("adam_step NULL language", lambda: L.olsr_adam_step(10, 0, 15, ok, X, X, None, X, X, X, None, X, X, None), ARG,
+         "the bucket, " + no_params),
+    ]
+    for name, prefix, fn, extra in (
+            ("adam_step_sum", "adam_step_sum", L.olsr_adam_step_sum, ()),
+            ("adam_step_masked", "adam_step_sum", L.olsr_adam_step_masked, (None,)),
+            ("adam_step_groups", "adam_step_groups", L.olsr_adam_step_groups, (None,))):
+        groups = fn is L.olsr_adam_step_groups
+        p, p0 = (gok, gstep0) if groups else (ok, step0)
+        call = lambda P, M, F, par, n, flats, arrays, fn=fn, extra=extra: fn(P, M, F, par, n, flats, *extra, *arrays, None)
+        rows += [
+            (name + " F", lambda c=call, p=p: c(10, 16, 7, p, 1, one, nine), ARG, bad_F),
+            (name + " M", lambda c=call, p=p: c(10, -1, 15, p, 1, one, nine), ARG, bad_F),
+            (name + " step", lambda c=call, p0=p0: c(10, 16, 15, p0, 1, one, nine), ARG,
+             "adam_step_groups: the step count of every group that steps must be >= 1" if groups else bad_step),
+            (name + " no params", lambda c=call: c(10, 16, 15, None, 1, one, nine), ARG,
+             "adam group params are required" if groups else bad_step),
+            (name + " no buckets", lambda c=call, p=p: c(10, 16, 15, p, 0, one, nine), ARG,
+             prefix + ": between 1 and 8 gradient buckets"),
+            (name + " nine buckets", lambda c=call, p=p: c(10, 16, 15, p, 9, one, nine), ARG,
+             prefix + ": between 1 and 8 gradient buckets"),
+            (name + " NULL bucket list", lambda c=call, p=p: c(10, 16, 15, p, 1, None, nine), ARG,
+             prefix + ": between 1 and 8 gradient buckets"),
+            (name + " NULL bucket", lambda c=call, p=p: c(10, 16, 15, p, 2, hole, nine), ARG,
+             prefix + ": a gradient bucket is NULL"),
+            (name + " NULL parameters", lambda c=call, p=p: c(10, 16, 15, p, 1, one, [None] * 9), ARG, no_params),
+            (name + " NULL shs", lambda c=call, p=p: c(10, 16, 0, p, 1, one, [X, None] + [X] * 7), ARG, no_params),
+        ]
+
+    # the sync-free forwards (an empty scene passes the scene check with no array at all)
+    s = _abi.OlsrScene()
+    s.P, s.width, s.height, s.tile, s.F, s.binning = 0, 64, 48, 15, 15, 0
+    lf = _abi.OlsrLossFusion()
+    lf.params.width, lf.params.height = 64, 48
+    no_state = "state buffers and a non-negative capacity are required"
+    tail = [None] * 8
+    for name, call in (
+            ("forward_async", lambda g, b, cap, i: L.olsr_forward_async(s, g, b, cap, i, *tail, None)),
+            ("forward_async_loss", lambda g, b, cap, i: L.olsr_forward_async_loss(s, g, b, cap, i, *tail, lf, None)),
+            ("forward_async_loss (no loss)", lambda g, b, cap, i: L.olsr_forward_async_loss(s, g, b, cap, i, *tail, None, None))):
+        rows += [
+            (name + " NULL geometry", lambda c=call: c(None, X, 16, X), ARG, no_state),
+            (name + " NULL binning", lambda c=call: c(X, None, 16, X), ARG, no_state),
+            (name + " NULL image", lambda c=call: c(X, X, 16, None), ARG, no_state),
+            (name + " capacity", lambda c=call: c(X, X, -1, X), ARG, no_state),
+        ]
+    wide, tall = _abi.OlsrLossFusion(), _abi.OlsrLossFusion()
+    wide.params.width, wide.params.height = 65, 48
+    tall.params.width, tall.params.height = 64, 47
+    for name, f in (("width", wide), ("height", tall)):
+        rows.append(("fused loss " + name, lambda f=f: L.olsr_forward_async_loss(s, X, X, 16, X, *tail, f, None), ARG,
+                     "fused loss: params.width / height must equal the scene's"))
+
+    # the stand-alone losses
+    lp, lp0 = _abi.OlsrLossParams(), _abi.OlsrLossParams()
+    lp.width, lp.height, lp.F = 64, 48, 15
+    lp0.width, lp0.height, lp0.F = 64, 48, 0
+    m_need = "image, depth, their targets, their gradient outputs, loss and scratch are required"
+    t_need = "image, depth, opacity, their targets, the gradient outputs, loss and scratch are required"
+
+    def mapping(p, **null):
+        a = dict(image=X, depth=X, language=X, gt_image=X, gt_depth=X, gt_language=None, exposure=None, dL_dimage=X,
+                 dL_ddepth=X, dL_dlanguage=X, loss=X, dL_dexposure=None, scratch=X)
+        a.update(null)
+        return L.olsr_mapping_loss(p, *a.values(), None)
+
+    def tracking(p, **null):
+        a = dict(image=X, depth=X, opacity=X, gt_image=X, gt_depth=X, grad_mask=None, exposure=None, dL_dimage=X,
+                 dL_ddepth=X, loss=X, dL_dexposure=None, scratch=X)
+        a.update(null)
+        return L.olsr_tracking_loss(p, *a.values(), None)
+
+    rows += [("mapping_loss no params", lambda: mapping(None), ARG, "loss params are NULL"),
+             ("tracking_loss no params", lambda: tracking(None), ARG, "loss params are NULL")]
+    for k in ("image", "depth", "gt_image", "gt_depth", "dL_dimage", "dL_ddepth", "loss", "scratch"):
+        rows.append(("mapping_loss NULL " + k, lambda k=k: mapping(lp0, **{k: None}), ARG, m_need))
+    for k in ("language", "dL_dlanguage"):
+        rows.append(("mapping_loss NULL " + k, lambda k=k: mapping(lp, **{k: None}), ARG,
+                     "language and dL_dlanguage are required when F > 0"))
+    for k in ("image", "depth", "opacity", "gt_image", "gt_depth", "dL_dimage", "dL_ddepth", "loss", "scratch"):
+        rows.append(("tracking_loss NULL " + k, lambda k=k: tracking(lp0, **{k: None}), ARG, t_need))
+    for i, k in enumerate(("image", "gt_image", "dL_dimage", "loss", "scratch")):
+        if k == "dL_dimage":
+            continue                                # (optional: values only)
+        a = [X] * 5
+        a[i] = None
+        rows.append(("refinement_loss NULL " + k, lambda a=a: L.olsr_refinement_loss(64, 48, 0.2, *a, None), ARG,
+                     "image, gt_image, loss and scratch are required"))
+    rows.append(("refinement_loss size", lambda: L.olsr_refinement_loss(0, 48, 0.2, X, X, X, X, X, None), ARG,
+                 "image size must be positive"))
+
+    # map edits
+    def params(mode, n_append=0):
+        p = _abi.OlsrMapEditParams()
+        p.mode, p.n_append = mode, n_append
+        return p
+
+    def buffers(**null):
+        b = _abi.OlsrMapBuffers()
+        for f, _ in _abi.OlsrMapBuffers._fields_:
+            setattr(b, f, None if f in null else X)
+        return b
+    full, empty = buffers(), _abi.OlsrMapBuffers()
+    dens, mask = params(_abi.MAP_EDIT_DENSIFY), params(_abi.MAP_EDIT_MASK)
+    plan_need = "map_edit_plan: P >= 0, params, src, scratch and status are required"
+    apply_need = "map_edit_apply: P, M >= 0, F one of 0, 3, 15, 16, 32; params, scratch and status are required"
+    plan, apply = L.olsr_map_edit_plan, L.olsr_map_edit_apply
+    rows += [
+        ("map_edit_plan P", lambda: plan(-1, mask, full, None, X, X, None), ARG, plan_need),
+        ("map_edit_plan no params", lambda: plan(10, None, full, None, X, X, None), ARG, plan_need),
+        ("map_edit_plan no src", lambda: plan(10, mask, None, None, X, X, None), ARG, plan_need),
+        ("map_edit_plan no scratch", lambda: plan(10, mask, full, None, None, X, None), ARG, plan_need),
+        ("map_edit_plan no status", lambda: plan(10, mask, full, None, X, None, None), ARG, plan_need),
+        ("map_edit_plan mode", lambda: plan(10, params(2), full, None, X, X, None), ARG, "map_edit_plan: unknown mode"),
+        ("map_edit_plan n_append", lambda: plan(10, params(1, -1), full, None, X, X, None), ARG,
+         "map_edit_plan: n_append must be >= 0"),
+        ("map_edit_plan densify appends", lambda: plan(10, params(0, 3), full, None, X, X, None), ARG,
+         "map_edit_plan: densify mode appends nothing"),
+        ("map_edit_plan densify stats", lambda: plan(10, dens, buffers(stats=1), None, X, X, None), ARG,
+         "map_edit_plan: densify mode reads stats, scales and opacities"),
+        ("map_edit_apply F", lambda: apply(10, 16, 7, mask, full, None, None, X, X, 10, 16, full, X, None), ARG, apply_need),
+        ("map_edit_apply no status", lambda: apply(10, 16, 15, mask, full, None, None, X, None, 10, 16, full, X, None), ARG,
+         apply_need),
+        ("map_edit_apply capacity", lambda: apply(10, 16, 15, mask, full, None, None, X, X, 17, 16, full, X, None), CAP,
+         "map_edit_apply: P_new exceeds the destination's capacity"),
+        ("map_edit_apply dst", lambda: apply(10, 16, 15, mask, full, None, None, X, X, 10, 16, buffers(n_obs=1), X, None), ARG,
+         "map_edit_apply: every destination buffer is required"),
+        ("map_edit_apply no dst", lambda: apply(10, 16, 15, mask, full, None, None, X, X, 10, 16, None, X, None), ARG,
+         "map_edit_apply: every destination buffer is required"),
+        ("map_edit_apply src_index", lambda: apply(10, 16, 15, mask, full, None, None, X, X, 10, 16, full, None, None), ARG,
+         "map_edit_apply: every destination buffer is required"),
+        ("map_edit_apply src", lambda: apply(10, 16, 15, mask, empty, None, None, X, X, 10, 16, full, X, None), ARG,
+         "map_edit_apply: every source buffer is required"),
+        ("map_edit_apply z", lambda: apply(10, 16, 15, dens, full, None, None, X, X, 10, 16, full, X, None), ARG,
+         "map_edit_apply: densify mode needs z [P,2,3]"),
+        ("map_edit_apply append", lambda: apply(10, 16, 15, params(1, 2), full, None, buffers(shs=1), X, X, 12, 16, full, X, None),
+         ARG, "map_edit_apply: the appended rows need means3D, shs, opacities, scales and rotations"),
+        ("map_edit_apply no append", lambda: apply(10, 16, 15, params(1, 2), full, None, None, X, X, 12, 16, full, X, None),
+         ARG, "map_edit_apply: the appended rows need means3D, shs, opacities, scales and rotations"),
+    ]
+    return rows
+
+
+def test_shared_argument_checks_keep_their_codes_and_messages(L):
+    """The argument checks that several C-ABI entries share — the four Adam entries, the sync-free forwards' state buffers and
+    capacity, the fused loss's size, the stand-alone losses' pointers, the map edits — return the code and leave the
+    olsr_last_error() text listed here, whichever entry they are reached through.  Every one of them returns before the
+    first HIP call, so no GPU is involved."""
+    rows = _argument_error_table(L)
+    assert len(rows) >= 90
+    wrong = []
+    for label, call, code, message in rows:
+        rc = call()
+        got = L.olsr_last_error().decode()
+        if rc != code or got != message:
+            wrong.append((label, rc, got))
+    assert not wrong, wrong
