@@ -610,6 +610,54 @@ int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim,
                          const float *image, const float *gt_image, float *dL_dimage, float *loss,
                          void *scratch, void *hip_stream);
 
+/* ---- the online language autoencoder (back end, utils/slam_backend.py:266-323) ------------------------------------------
+ * BackEnd.train_online_autoencoder trains EncoderDecoderOnline (language/autoencoder/model.py:314-354) on a keyframe's
+ * N x 32 language feature rows and hands the codes back as the keyframe's language target (viewpoint.gt_lang_feat, :562-576):
+ *   encode(x) = z / |z|,  z = W2 relu(W1 x + b1) + b2        32 -> 24 -> 15
+ *   decode(c) = y / |y|,  y = W4 relu(W3 c + b3) + b4        15 -> 24 -> 32
+ *   loss = mean_{N 32}|r - x| + 0.6 (1 - mean_N cos(r, x)),  r = decode(encode(x)),  cos = F.cosine_similarity(dim=1, eps=1e-8)
+ * followed by autograd's backward and torch.optim.Adam.step (defaults: betas 0.9 / 0.999, eps 1e-8, no weight decay) — several
+ * dozen launches of microsecond kernels and a loss.item() host read in the reference, two launches here (one more for codes of
+ * the updated parameters), no host read, no atomics: a step is bit-reproducible.  Neither norm has an epsilon, as in the
+ * reference: a row whose z or y is exactly zero gives NaN there and here.  relu'(0) = 0 and sgn(0) = 0, as autograd has them.
+ * The sizes 32 / 24 / 15 are compiled in; params->in_dim / hidden_dim / code_dim must name them (anything else: OLSR_ERR_ARG).
+ *   params        device float[2351], state_dict order: encoder.0.weight [24,32], encoder.0.bias [24], encoder.2.weight [15,24],
+ *                 encoder.2.bias [15], decoder.0.weight [24,15], decoder.0.bias [24], decoder.2.weight [32,24], decoder.2.bias [32]
+ *   exp_avg, exp_avg_sq   device float[2351], Adam's moments in the same order; zero before the first step
+ *   features      device float[N,32] rows, a constant
+ *   step_dev      device int32[1], the number of steps done; every call adds one.  params->step is the 1-based Adam step count
+ *                 of this call; step <= 0: the count is step_dev[0] kept on the device (required then), so that a loop of steps is
+ *                 enqueued without a synchronisation or replayed from a HIP graph; zero it to restart the optimiser
+ *   loss          device float[4]: {total, L1 term, 0.6 (1 - mean cos) term, mean cos}, of the parameters BEFORE the update
+ *   codes         device float[N,15] (OLSR_LANG_AE_CODES_ROWS) or [15,N] (OLSR_LANG_AE_CODES_CHANNELS: low_dim.T.view(15,h,w),
+ *                 the language target olsr_mapping_loss reads, without a transpose pass) of the parameters BEFORE the update, or
+ *                 NULL; follow with olsr_lang_ae_encode for the codes of the updated parameters (the reference's viz=True)
+ *   grad_out      device float[2351] or NULL: the gradient Adam was given (a test instrument)
+ *   scratch       olsr_lang_ae_scratch_bytes(N) bytes: per 256 rows one float32 partial gradient; they are added in double */
+#define OLSR_LANG_AE_IN 32
+#define OLSR_LANG_AE_HIDDEN 24
+#define OLSR_LANG_AE_CODE 15
+#define OLSR_LANG_AE_PARAMS 2351
+#define OLSR_LANG_AE_CODES_ROWS 0
+#define OLSR_LANG_AE_CODES_CHANNELS 1
+typedef struct olsr_lang_ae_params {
+  double lr;                 /* the reference: 1e-3 during initialisation, 1e-4 in map(); its scheduler is never stepped */
+  double beta1, beta2, eps;  /* 0.9, 0.999, 1e-8 */
+  int32_t step;
+  int32_t code_layout;       /* OLSR_LANG_AE_CODES_* (checked even when codes is NULL) */
+  int32_t in_dim, hidden_dim, code_dim;
+  int32_t _pad0;
+} olsr_lang_ae_params;
+size_t olsr_lang_ae_scratch_bytes(int32_t N);
+int olsr_lang_ae_train_step(const olsr_lang_ae_params *params_struct, int32_t N, const float *features,
+                            float *params, float *exp_avg, float *exp_avg_sq, int32_t *step_dev,
+                            float *loss, float *codes, float *grad_out, void *scratch, void *hip_stream);
+/* codes = encode(features) and recon [N,32] = decode(codes), one launch each; code_layout as above, N >= 1. */
+int olsr_lang_ae_encode(int32_t N, const float *features, const float *params, int32_t code_layout,
+                        float *codes, void *hip_stream);
+int olsr_lang_ae_decode(int32_t N, const float *codes, const float *params, int32_t code_layout,
+                        float *recon, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

@@ -119,6 +119,21 @@ class OlsrPoseParams(C.Structure):
                                            "converged_threshold")] + [("step", C.c_int32), ("_pad0", C.c_int32)]
 
 
+# the online language autoencoder (OLSR_LANG_AE_*): compiled-in sizes, the flat parameter array in state_dict order
+LANG_AE_IN, LANG_AE_HIDDEN, LANG_AE_CODE, LANG_AE_PARAMS = 32, 24, 15, 2351
+LANG_AE_CODES_ROWS, LANG_AE_CODES_CHANNELS = 0, 1   # codes as [N,15] rows / as [15,N] = low_dim.T
+LANG_AE_STATE = (("encoder.0.weight", (24, 32)), ("encoder.0.bias", (24,)), ("encoder.2.weight", (15, 24)),
+                 ("encoder.2.bias", (15,)), ("decoder.0.weight", (24, 15)), ("decoder.0.bias", (24,)),
+                 ("decoder.2.weight", (32, 24)), ("decoder.2.bias", (32,)))
+
+
+class OlsrLangAeParams(C.Structure):
+    """struct olsr_lang_ae_params, include/olsr.h."""
+
+    _fields_ = [(n, C.c_double) for n in ("lr", "beta1", "beta2", "eps")] + [
+        (n, C.c_int32) for n in ("step", "code_layout", "in_dim", "hidden_dim", "code_dim", "_pad0")]
+
+
 class OlsrLossParams(C.Structure):
     """struct olsr_loss_params, include/olsr.h."""
 

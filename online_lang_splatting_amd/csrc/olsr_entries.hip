@@ -168,6 +168,46 @@ int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim, cons
   return launch_check("refinement_loss");
 }
 
+size_t olsr_lang_ae_scratch_bytes(int32_t N) { return N <= 0 ? ALIGN : lang_ae_scratch_bytes(N); }
+
+static bool lang_ae_layout_ok(int32_t layout) {
+  return layout == OLSR_LANG_AE_CODES_ROWS || layout == OLSR_LANG_AE_CODES_CHANNELS;
+}
+
+int olsr_lang_ae_train_step(const olsr_lang_ae_params* p, int32_t N, const float* features, float* params, float* exp_avg,
+                            float* exp_avg_sq, int32_t* step_dev, float* loss, float* codes, float* grad_out, void* scratch,
+                            void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "lang_ae_train_step: the parameter struct is NULL");
+  if (p->in_dim != OLSR_LANG_AE_IN || p->hidden_dim != OLSR_LANG_AE_HIDDEN || p->code_dim != OLSR_LANG_AE_CODE)
+    return fail(OLSR_ERR_ARG, "lang_ae_train_step: the sizes 32 / 24 / 15 are compiled in");
+  if (N <= 0) return fail(OLSR_ERR_ARG, "lang_ae_train_step: N must be positive");
+  if (!lang_ae_layout_ok(p->code_layout)) return fail(OLSR_ERR_ARG, "lang_ae_train_step: unknown code layout");
+  if (!features || !params || !exp_avg || !exp_avg_sq || !loss || !scratch)
+    return fail(OLSR_ERR_ARG, "lang_ae_train_step: features, params, both moments, loss and scratch are required");
+  if (p->step <= 0 && !step_dev) return fail(OLSR_ERR_ARG, "lang_ae_train_step: step <= 0 needs the device step counter");
+  launch_lang_ae_train_step(*p, N, features, params, exp_avg, exp_avg_sq, step_dev, loss, codes, grad_out, scratch,
+                            (hipStream_t)hip_stream);
+  return launch_check("lang_ae_train_step");
+}
+
+int olsr_lang_ae_encode(int32_t N, const float* features, const float* params, int32_t code_layout, float* codes,
+                        void* hip_stream) {
+  if (N <= 0) return fail(OLSR_ERR_ARG, "lang_ae_encode: N must be positive");
+  if (!lang_ae_layout_ok(code_layout)) return fail(OLSR_ERR_ARG, "lang_ae_encode: unknown code layout");
+  if (!features || !params || !codes) return fail(OLSR_ERR_ARG, "lang_ae_encode: features, params and codes are required");
+  launch_lang_ae_encode(N, features, params, code_layout, codes, (hipStream_t)hip_stream);
+  return launch_check("lang_ae_encode");
+}
+
+int olsr_lang_ae_decode(int32_t N, const float* codes, const float* params, int32_t code_layout, float* recon,
+                        void* hip_stream) {
+  if (N <= 0) return fail(OLSR_ERR_ARG, "lang_ae_decode: N must be positive");
+  if (!lang_ae_layout_ok(code_layout)) return fail(OLSR_ERR_ARG, "lang_ae_decode: unknown code layout");
+  if (!codes || !params || !recon) return fail(OLSR_ERR_ARG, "lang_ae_decode: codes, params and recon are required");
+  launch_lang_ae_decode(N, codes, params, code_layout, recon, (hipStream_t)hip_stream);
+  return launch_check("lang_ae_decode");
+}
+
 int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
                               const float* dL_dsh,
                               const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,

@@ -259,4 +259,12 @@ size_t refinement_loss_scratch_bytes(int W, int H);
 void launch_refinement_loss(int W, int H, float lambda, const float* image, const float* gt_image, float* dL_dimage,
                             float* loss, void* scratch, hipStream_t st);
 
+// k_lang_ae.hip: the online language autoencoder (include/olsr.h)
+size_t lang_ae_scratch_bytes(int N);
+void launch_lang_ae_train_step(const olsr_lang_ae_params& p, int N, const float* features, float* params, float* exp_avg,
+                               float* exp_avg_sq, int32_t* step_dev, float* loss, float* codes, float* grad_out, void* scratch,
+                               hipStream_t st);
+void launch_lang_ae_encode(int N, const float* features, const float* params, int code_layout, float* codes, hipStream_t st);
+void launch_lang_ae_decode(int N, const float* codes, const float* params, int code_layout, float* recon, hipStream_t st);
+
 }  // namespace olsr

@@ -10,12 +10,15 @@ TrackingLoop   front end, utils/slam_frontend.py:tracking() (:160-275): up to 10
 MappingStep    back end, utils/slam_backend.py:map() (:499-760): 12 views of the same Gaussians (10 window keyframes +
                2 random), mapping loss incl. the language L1 (:579-597), gradients summed over the views, ONE Adam step.
 
+OnlineLanguageTargets  back end, the language targets of map(): train_online_autoencoder (:266-323) once per new keyframe
+               (:562-576, the returned codes are the keyframe's gt_lang_feat) and once per rehearsal view (:640-648).
+
 RefinementStep back end, utils/slam_backend.py:color_refinement() (:769-819): 26 000 DEPENDENT iterations of one random
                keyframe -> (1 - lambda) L1 + lambda (1 - SSIM) on the colour image -> backward -> Adam on every group ->
                position learning-rate decay.  No densification, pruning or pose update.
 
 Everything numerical happens in libolsr.so (olsr_forward_async, olsr_tracking_loss / olsr_mapping_loss /
-olsr_refinement_loss, olsr_backward, olsr_pose_step, olsr_adam_step); this module only sequences the calls, like the
+olsr_refinement_loss, olsr_lang_ae_train_step, olsr_backward, olsr_pose_step, olsr_adam_step); this module only sequences the calls, like the
 reference's Python does.
 """
 import ctypes as C
@@ -561,3 +564,50 @@ class RefinementStep:
         for i in range(n):
             self.iteration(None if views is None else views[i])
         return self.last_loss
+
+
+class OnlineLanguageTargets:
+    """The language targets of the mapping loop, produced the way the reference's map() produces them: the online autoencoder
+    (lang_codec.OnlineLanguageCodec) takes one training step on a new keyframe's 32-channel features and the codes of that
+    step's forward pass become the keyframe's [15,h,w] target (utils/slam_backend.py:562-576); the two random rehearsal views of
+    every mapping iteration train it once more each and keep the targets they have (:640-648).  Features and targets stay on
+    the device (the reference keeps gt_lang_feat on the CPU and uploads it every iteration)."""
+
+    def __init__(self, codec, lr: float = 1e-4, hw=(192, 192)):
+        """lr: 1e-4 in map(), 1e-3 during initialize_map."""
+        self.codec, self.lr, self.hw = codec, float(lr), (int(hw[0]), int(hw[1]))
+        self.features: Dict = {}
+        self.targets: Dict = {}
+        self.steps = 0
+        self.last_loss = None   # loss[4] of the last step, a copy (the codec's own loss buffer is overwritten by every step)
+
+    def add_keyframe(self, view_id, features32: torch.Tensor) -> torch.Tensor:
+        """features32 [h*w,32] (or [h,w,32]) float32 on the codec's device: one train step, the codes of its forward pass are
+        stored as the view's [15,h,w] target.  The features are copied: the caller may reuse its buffer.  -> that target."""
+        h, w = self.hw
+        if isinstance(features32, torch.Tensor) and features32.dim() == 3:
+            features32 = features32.reshape(-1, features32.shape[-1])
+        if not isinstance(features32, torch.Tensor) or features32.dim() != 2 or features32.shape[0] != h * w:
+            raise RuntimeError(f"add_keyframe: features must be [{h * w},32] for hw = {self.hw}")
+        loss, codes = self.codec.train_step(features32, self.lr, codes="pre", layout="channels")
+        self.features[view_id] = features32.detach().clone()
+        self.targets[view_id] = codes.clone().view(codes.shape[0], h, w)
+        self.steps += 1
+        self.last_loss = loss.clone()
+        return self.targets[view_id]
+
+    def rehearse(self, view_ids: Sequence) -> None:
+        """One train step on the stored features of each id; their targets stay as they are."""
+        for v in view_ids:
+            if v not in self.features:
+                raise KeyError(f"rehearse: view {v!r} was never added")
+        loss = None
+        for v in view_ids:
+            loss, _ = self.codec.train_step(self.features[v], self.lr, codes=None)
+            self.steps += 1
+        if loss is not None:
+            self.last_loss = loss.clone()
+
+    def targets_for(self, view_ids: Sequence):
+        """The third slot of MappingStep.targets for these views, in order."""
+        return [self.targets[v] for v in view_ids]
