@@ -658,6 +658,62 @@ int olsr_lang_ae_encode(int32_t N, const float *features, const float *params, i
 int olsr_lang_ae_decode(int32_t N, const float *codes, const float *params, int32_t code_layout,
                         float *recon, void *hip_stream);
 
+/* ---- open-vocabulary text queries on a rendered language map (eval/evaluate_onlinelangslam.py:266-287) -------------------
+ * The reference answers "where is the table?" from a rendered 15-channel code map with
+ *   codes -> model_online.decode (15 -> 24 -> 32, the decoder half of olsr_lang_ae_*) -> AutoencoderMLP.decode (32 -> 192 ->
+ *   256 -> 384 -> 512 -> 768, ReLU between layers, x / |x|) -> embed @ phrases.T -> softmax(10 [s_pos, s_neg])[0], smallest
+ *   over the canonical negatives (eval/openclip_encoder.py:44-107) -> 30 x 30 mean (cv2.filter2D defaults) -> max point, mask
+ * in torch ops that write the [N,768] feature image (2.5 GB at 1200 x 680).  Here stage A, olsr_lang_query_sims, goes from the
+ * codes to the K similarities of every pixel in one launch on the fp32 matrix cores and stores nothing wider than K per pixel;
+ * stage B, olsr_lang_query_relevancy, goes from the similarities to every per-phrase output on the device, without a host read
+ * and without atomics: both are bit-reproducible.  Arithmetic is float32 (v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain),
+ * norms and window sums are accumulated in double.
+ *   widths        the layer widths of the general decoder, input first.  This build has kernels for the two-stage chain
+ *                 {32, 192, 256, 384, 512, 768} behind the online decoder; any other list is OLSR_ERR_ARG
+ *   phrases       device float[K,768], unit rows, 16-byte aligned: [n_pos positives | n_labels labels | negatives], 1 <= K <= 64
+ *   codes         device float[15,in_height,in_width], channel-major: what the rasteriser returns.  When (dec_width,
+ *                 dec_height) differs they are resampled first, as F.interpolate(mode="bilinear", align_corners=False) (:270)
+ *   online_params device float[2351], the layout of olsr_lang_ae_* (its decoder half is read)
+ *   decoder_params device float[745536], 16-byte aligned: AutoencoderMLP.decoder in state_dict order (decoder.0.weight [192,32],
+ *                 decoder.0.bias [192], decoder.2.weight [256,192], ... decoder.8.bias [768])
+ *   sims          device float[K,dec_height,dec_width]: <decode(codes) , phrase>
+ * olsr_lang_query_relevancy reads sims and writes at (out_width, out_height); when that differs from the decode size the
+ * similarity planes are up-sampled bilinearly first (the dot product is linear, so this is the reference's up-sampling of the
+ * 768-channel features at :274 followed by the product).
+ *   relevancy     float[n_pos,H,W]: get_relevancy + get_max_across' [..., 0:1]
+ *   smoothed      float[n_pos,H,W]: the 30 x 30 mean (correlation, anchor (15,15): window -15 .. +14, border reflect-101)
+ *   blended       float[n_pos,H,W]: 0.5 (smoothed + relevancy)
+ *   score         float[n_pos]: max of smoothed;  coord int32[n_pos,2]: its (x, y), the first in row-major order among equals
+ *   minmax        float[n_pos,2]: min and max of blended
+ *   mask          uint8[n_pos,H,W] or NULL (required with OLSR_LANG_QUERY_WANT_MASK): clip(2 (b - min) / (max - min + 1e-9) - 1,
+ *                 0, 1) > thresh (:146-152)
+ *   labels        int32[H,W] or NULL (required with OLSR_LANG_QUERY_WANT_LABELS, which needs n_labels >= 1): get_semantic_map,
+ *                 the argmax over label and negative similarities, an index >= n_labels written as -1
+ *   scratch       olsr_lang_query_scratch_bytes(params) bytes: 16 bytes per positive and 32 x 32 output tile
+ * n_pos = 0 (labels only) is allowed in olsr_lang_query_relevancy; at least one negative is required there. */
+#define OLSR_LANG_QUERY_MAX_LAYERS 8
+#define OLSR_LANG_QUERY_MAX_PHRASES 64
+#define OLSR_LANG_QUERY_FEATURE_DIM 768
+#define OLSR_LANG_QUERY_DECODER_PARAMS 745536
+#define OLSR_LANG_QUERY_WANT_MASK 1u
+#define OLSR_LANG_QUERY_WANT_LABELS 2u
+typedef struct olsr_lang_query_params {
+  int32_t n_widths;
+  int32_t widths[OLSR_LANG_QUERY_MAX_LAYERS];
+  int32_t K, n_pos, n_labels;
+  int32_t in_width, in_height;    /* the code map */
+  int32_t dec_width, dec_height;  /* the size the decoder runs at (the reference's evaluation: 480 x 640) */
+  int32_t out_width, out_height;  /* the size of every output of olsr_lang_query_relevancy */
+  float thresh;                   /* the reference: mask_thresh = 0.4 */
+  uint32_t flags;                 /* OLSR_LANG_QUERY_WANT_* */
+} olsr_lang_query_params;
+size_t olsr_lang_query_scratch_bytes(const olsr_lang_query_params *params);
+int olsr_lang_query_sims(const olsr_lang_query_params *params, const float *codes, const float *online_params,
+                         const float *decoder_params, const float *phrases, float *sims, void *hip_stream);
+int olsr_lang_query_relevancy(const olsr_lang_query_params *params, const float *sims, float *relevancy,
+                              float *smoothed, float *blended, float *score, int32_t *coord, float *minmax,
+                              uint8_t *mask, int32_t *labels, void *scratch, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

@@ -134,6 +134,22 @@ class OlsrLangAeParams(C.Structure):
         (n, C.c_int32) for n in ("step", "code_layout", "in_dim", "hidden_dim", "code_dim", "_pad0")]
 
 
+# text queries on a rendered language map (OLSR_LANG_QUERY_*): the general decoder AutoencoderMLP.decoder in state_dict order
+LANG_QUERY_MAX_LAYERS, LANG_QUERY_MAX_PHRASES, LANG_QUERY_FEATURE_DIM, LANG_QUERY_DECODER_PARAMS = 8, 64, 768, 745536
+LANG_QUERY_WANT_MASK, LANG_QUERY_WANT_LABELS = 1, 2
+LANG_QUERY_WIDTHS = (32, 192, 256, 384, 512, 768)
+LANG_QUERY_STATE = tuple(e for k, (i, o) in enumerate(zip(LANG_QUERY_WIDTHS, LANG_QUERY_WIDTHS[1:]))
+                         for e in ((f"decoder.{2 * k}.weight", (o, i)), (f"decoder.{2 * k}.bias", (o,))))
+
+
+class OlsrLangQueryParams(C.Structure):
+    """struct olsr_lang_query_params, include/olsr.h."""
+
+    _fields_ = [("n_widths", C.c_int32), ("widths", C.c_int32 * LANG_QUERY_MAX_LAYERS)] + [
+        (n, C.c_int32) for n in ("K", "n_pos", "n_labels", "in_width", "in_height", "dec_width", "dec_height", "out_width",
+                                 "out_height")] + [("thresh", C.c_float), ("flags", C.c_uint32)]
+
+
 class OlsrLossParams(C.Structure):
     """struct olsr_loss_params, include/olsr.h."""
 

@@ -39,6 +39,7 @@ UNITS = [
     ("k_loss.hip", "k_loss.o", []),
     ("k_ssim.hip", "k_ssim.o", []),
     ("k_lang_ae.hip", "k_lang_ae.o", []),
+    ("k_lang_query.hip", "k_lang_query.o", []),
     ("k_knn.hip", "k_knn.o", []),
     ("k_adam.hip", "k_adam.o", []),
     ("k_map_edit.hip", "k_map_edit.o", []),

@@ -208,6 +208,59 @@ int olsr_lang_ae_decode(int32_t N, const float* codes, const float* params, int3
   return launch_check("lang_ae_decode");
 }
 
+// what is wrong with the sizes of a language query, or nullptr
+static const char* lang_query_params_error(const olsr_lang_query_params* p) {
+  static const int32_t built[6] = {OLSR_LANG_AE_IN, 192, 256, 384, 512, OLSR_LANG_QUERY_FEATURE_DIM};
+  if (!p) return "the parameter struct is NULL";
+  if (p->n_widths != 6) return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
+  for (int k = 0; k < 6; ++k)
+    if (p->widths[k] != built[k]) return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
+  if (p->K < 1 || p->K > OLSR_LANG_QUERY_MAX_PHRASES) return "K must be between 1 and 64";
+  if (p->n_pos < 0 || p->n_labels < 0 || p->n_pos + p->n_labels > p->K) return "n_pos and n_labels must be >= 0 and sum to at most K";
+  if (p->in_width < 1 || p->in_height < 1 || p->dec_width < 1 || p->dec_height < 1 || p->out_width < 1 || p->out_height < 1)
+    return "every width and height must be positive";
+  if ((int64_t)p->in_width * p->in_height > (1 << 28) || (int64_t)p->dec_width * p->dec_height > (1 << 28) ||
+      (int64_t)p->out_width * p->out_height > (1 << 28))
+    return "a map has at most 2^28 pixels";
+  if (p->flags & ~(OLSR_LANG_QUERY_WANT_MASK | OLSR_LANG_QUERY_WANT_LABELS)) return "flags holds unknown OLSR_LANG_QUERY_* bits";
+  return nullptr;
+}
+
+size_t olsr_lang_query_scratch_bytes(const olsr_lang_query_params* p) {
+  return (!p || p->out_width < 1 || p->out_height < 1) ? ALIGN : lang_query_scratch_bytes(*p);
+}
+
+int olsr_lang_query_sims(const olsr_lang_query_params* p, const float* codes, const float* online_params,
+                         const float* decoder_params, const float* phrases, float* sims, void* hip_stream) {
+  if (const char* e = lang_query_params_error(p)) return fail(OLSR_ERR_ARG, std::string("lang_query_sims: ") + e);
+  if (!codes || !online_params || !decoder_params || !phrases || !sims)
+    return fail(OLSR_ERR_ARG, "lang_query_sims: codes, both parameter arrays, phrases and sims are required");
+  if (((uintptr_t)decoder_params & 15u) || ((uintptr_t)phrases & 15u))
+    return fail(OLSR_ERR_ARG, "lang_query_sims: decoder_params and phrases must be 16-byte aligned");
+  const hipError_t e = launch_lang_query_sims(*p, codes, online_params, decoder_params, phrases, sims, (hipStream_t)hip_stream);
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("lang_query_sims: ") + hipGetErrorString(e));
+  return launch_check("lang_query_sims");
+}
+
+int olsr_lang_query_relevancy(const olsr_lang_query_params* p, const float* sims, float* relevancy, float* smoothed,
+                              float* blended, float* score, int32_t* coord, float* minmax, uint8_t* mask, int32_t* labels,
+                              void* scratch, void* hip_stream) {
+  if (const char* e = lang_query_params_error(p)) return fail(OLSR_ERR_ARG, std::string("lang_query_relevancy: ") + e);
+  if (p->K - p->n_pos - p->n_labels < 1) return fail(OLSR_ERR_ARG, "lang_query_relevancy: at least one negative phrase is required");
+  const bool want_mask = p->flags & OLSR_LANG_QUERY_WANT_MASK, want_labels = p->flags & OLSR_LANG_QUERY_WANT_LABELS;
+  if (p->n_pos < 1 && !want_labels) return fail(OLSR_ERR_ARG, "lang_query_relevancy: nothing to do without positives or labels");
+  if (want_labels && p->n_labels < 1) return fail(OLSR_ERR_ARG, "lang_query_relevancy: the label map needs n_labels >= 1");
+  if (!(p->thresh == p->thresh)) return fail(OLSR_ERR_ARG, "lang_query_relevancy: thresh is NaN");
+  if (!sims) return fail(OLSR_ERR_ARG, "lang_query_relevancy: sims is required");
+  if (p->n_pos > 0 && (!relevancy || !smoothed || !blended || !score || !coord || !minmax || !scratch))
+    return fail(OLSR_ERR_ARG, "lang_query_relevancy: relevancy, smoothed, blended, score, coord, minmax and scratch are required");
+  if (want_mask && (!mask || p->n_pos < 1)) return fail(OLSR_ERR_ARG, "lang_query_relevancy: the mask needs its array and a positive");
+  if (want_labels && !labels) return fail(OLSR_ERR_ARG, "lang_query_relevancy: the label map needs its array");
+  launch_lang_query_relevancy(*p, sims, relevancy, smoothed, blended, score, coord, minmax, want_mask ? mask : nullptr,
+                              want_labels ? labels : nullptr, scratch, (hipStream_t)hip_stream);
+  return launch_check("lang_query_relevancy");
+}
+
 int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
                               const float* dL_dsh,
                               const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,

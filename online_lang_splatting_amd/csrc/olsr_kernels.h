@@ -267,4 +267,12 @@ void launch_lang_ae_train_step(const olsr_lang_ae_params& p, int N, const float*
 void launch_lang_ae_encode(int N, const float* features, const float* params, int code_layout, float* codes, hipStream_t st);
 void launch_lang_ae_decode(int N, const float* codes, const float* params, int code_layout, float* recon, hipStream_t st);
 
+// k_lang_query.hip: text queries on a rendered language map (include/olsr.h)
+size_t lang_query_scratch_bytes(const olsr_lang_query_params& p);
+hipError_t launch_lang_query_sims(const olsr_lang_query_params& p, const float* codes, const float* online, const float* dec,
+                                  const float* phrases, float* sims, hipStream_t st);
+void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* sims, float* relevancy, float* smoothed,
+                                 float* blended, float* score, int32_t* coord, float* minmax, uint8_t* mask, int32_t* labels,
+                                 void* scratch, hipStream_t st);
+
 }  // namespace olsr
