@@ -714,6 +714,85 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params *params, const float 
                               float *smoothed, float *blended, float *score, int32_t *coord, float *minmax,
                               uint8_t *mask, int32_t *labels, void *scratch, void *hip_stream);
 
+/* ---- TSDF fusion of depth and language maps into a 3-D map (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) ---------------
+ * The reference's 3-D evaluation fuses, per keyframe, a depth image and a feature image (packed 8-bit colour in fusion.py, 3
+ * float channels in fusion2.py, 15 in fusion3.py) into a truncated signed distance volume with one CUDA launch per frame, 16
+ * image uploads per frame and 15 separate feature volumes, and takes the surface points of that volume from skimage's marching
+ * cubes on the host.  Here the volume stays on the device:
+ *   tsdf   float[X,Y,Z] (z fastest), 1 where nothing was observed;  weight float[X,Y,Z], 0 there
+ *   feat   OLSR_TSDF_FEAT_FLOAT: float[F,X,Y,Z], planar (the running mean of every channel; F = 0: geometry only, feat unused)
+ *          OLSR_TSDF_FEAT_PACKED_RGB: float[X,Y,Z], one float b * 65536 + g * 256 + r per voxel as in fusion.py (F must be 1)
+ * olsr_tsdf_init fills tsdf with 1 and weight and feat with 0 (one launch).
+ * olsr_tsdf_integrate fuses 1 <= n_views <= OLSR_TSDF_MAX_VIEWS views in ONE launch.  A thread owns a voxel, applies the views
+ * in index order, loads the voxel's state at the first view that reaches it, keeps it in registers, and stores it once: the
+ * result equals n_views single-view calls bit for bit, the volume is read and written once per batch instead of once per
+ * view, and a voxel that no view reaches is never written.  Per voxel and view the expressions and their order are those of
+ * the reference kernel (fusion.py:93-139, fusion3.py:181-290) in float32, without FMA contraction and with IEEE division:
+ *   pt = origin + voxel * voxel_size;  tmp = pt - pose[:,3];  cam = pose[:,:3]^T tmp (three-term sums left to right);
+ *   pixel = roundf(fx * (cam_x / cam_z) + cx), roundf(fy * (cam_y / cam_z) + cy);  skip outside the image, at depth == 0 and
+ *   at depth - cam_z < -trunc_margin;  dist = fminf(1, (depth - cam_z) / trunc_margin);  w_new = w_old + obs_weight;
+ *   tsdf = (tsdf * w_old + obs_weight * dist) / w_new;  feat_c = (feat_c * w_old + obs_weight * new_c) / w_new, or for the packed
+ *   colour the floor / round / min statements of fusion.py:128-139 (roundf: half away from zero).
+ * Divergences from the reference kernel, on purpose:
+ *   - voxel coordinates are integer quotients and remainders of the linear index, exact at any size (the reference divides
+ *     (float)voxel_idx, which is wrong above 2^24 voxels);
+ *   - the index bound is idx < X*Y*Z (the reference's `voxel_idx > N` lets idx == N through);
+ *   - a voxel with !(cam_z > 0) is skipped (the reference kernel skips only cam_z < 0 and converts a NaN or infinite pixel
+ *     coordinate to int at cam_z == 0; its CPU path tests pix_z > 0);
+ *   - the rounded pixel coordinate is range-checked as a float, then converted (no undefined float -> int conversion);
+ *   - rounding is roundf as in the reference kernel, where its CPU path rounds half to even (np.round);
+ *   - a view may carry an opacity plane: a pixel with opacity < min_opacity counts as invalid depth (rendered maps have pixels
+ *     no Gaussian covers; the reference fuses sensor depth, where 0 marks them).
+ * olsr_tsdf_view (passed by value in the kernel arguments, 128 bytes):
+ *   fx, fy, cx, cy  the pinhole intrinsics;  pose  camera-to-world, row-major [4,4];  obs_weight as in the reference
+ *   depth         device float[H,W]
+ *   feat          device float: OLSR_TSDF_IMAGE_CHANNELS [F,H,W] (what the rasteriser returns) or OLSR_TSDF_IMAGE_ROWS [H,W,F];
+ *                 packed mode: float[H,W] of b * 65536 + g * 256 + r;  NULL only with F = 0
+ *   opacity       device float[H,W] or NULL
+ * olsr_tsdf_surface_plan / olsr_tsdf_surface_emit extract the surface point cloud: plan counts, per voxel, the grid edges it
+ * owns that cross zero, prefixes the per-block counts in block order (no atomics: the output order is deterministic) and
+ * writes status[0] = N; the caller reads those 4 bytes, allocates, and emit writes the points.
+ *   - the edge from voxel v to v + e_a (a = x, y, z; inside the grid) is owned by v and crosses when (t0 < 0) != (t1 < 0);
+ *     with min_weight > 0 both ends must also have weight >= min_weight (0, the default, is the reference, where an
+ *     unobserved voxel counts as +1);
+ *   - pos = v + e_a * (t0 / (t0 - t1)) in float32;  point = pos * voxel_size + origin (two roundings);
+ *   - its features are those of the voxel rintf(pos) (the reference's np.round(verts).astype(int)); packed mode emits r, g, b;
+ *   - order: voxel linear index, then axis.
+ *   points float[N,3];  feats float[N,F] (packed: [N,3]; F = 0: may be NULL);  voxel_index int32[N] or NULL: the owner's linear index
+ * These are the edge vertices of marching cubes at level 0.  Faces, normals and the interior vertices Lewiner's variant adds in
+ * ambiguous cells are not produced: this is a point cloud, and no parity with skimage's mesh is claimed.
+ * Limits: X * Y * Z < 2^31 for integrate and init, 3 * X * Y * Z < 2^31 for the extraction. */
+#define OLSR_TSDF_MAX_VIEWS 16
+#define OLSR_TSDF_FEAT_FLOAT 0
+#define OLSR_TSDF_FEAT_PACKED_RGB 1
+#define OLSR_TSDF_IMAGE_CHANNELS 0
+#define OLSR_TSDF_IMAGE_ROWS 1
+typedef struct olsr_tsdf_volume {
+  int32_t X, Y, Z;
+  int32_t F;             /* OLSR_TSDF_FEAT_FLOAT: 0, 3, 15, 16 or 32; OLSR_TSDF_FEAT_PACKED_RGB: 1 */
+  int32_t feat_mode;     /* OLSR_TSDF_FEAT_* */
+  float voxel_size, trunc_margin;
+  float origin[3];
+  float *tsdf, *weight, *feat;
+} olsr_tsdf_volume;
+typedef struct olsr_tsdf_view {
+  float fx, fy, cx, cy;
+  float pose[16];
+  float obs_weight;
+  float min_opacity;
+  int32_t H, W;
+  int32_t feat_layout;   /* OLSR_TSDF_IMAGE_* */
+  int32_t _pad0;
+  const float *depth, *feat, *opacity;
+} olsr_tsdf_view;
+int olsr_tsdf_init(const olsr_tsdf_volume *volume, void *hip_stream);
+int olsr_tsdf_integrate(const olsr_tsdf_volume *volume, int32_t n_views, const olsr_tsdf_view *views, void *hip_stream);
+size_t olsr_tsdf_surface_scratch_bytes(int32_t X, int32_t Y, int32_t Z);
+int olsr_tsdf_surface_plan(const olsr_tsdf_volume *volume, float min_weight, void *scratch, int32_t *status,
+                           void *hip_stream);
+int olsr_tsdf_surface_emit(const olsr_tsdf_volume *volume, float min_weight, const void *scratch, int32_t capacity,
+                           float *points, float *feats, int32_t *voxel_index, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

@@ -13,8 +13,9 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # n
 
 from .renderer import render  # noqa: F401,E402  (the caller-side façade: gaussian_renderer.render)
 from .lang_query import LanguageDecoder, LanguageQuery  # noqa: F401,E402  (text queries on a rendered language map)
+from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and language maps into a 3-D map)
 
-__all__ = ["render", "LanguageDecoder", "LanguageQuery", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
+__all__ = ["render", "LanguageDecoder", "LanguageQuery", "TSDFVolume", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]
 

@@ -150,6 +150,28 @@ class OlsrLangQueryParams(C.Structure):
                                  "out_height")] + [("thresh", C.c_float), ("flags", C.c_uint32)]
 
 
+# TSDF fusion (OLSR_TSDF_*)
+TSDF_MAX_VIEWS = 16
+TSDF_FEAT_FLOAT, TSDF_FEAT_PACKED_RGB = 0, 1
+TSDF_IMAGE_CHANNELS, TSDF_IMAGE_ROWS = 0, 1   # a view's features as [F,H,W] (what the rasteriser returns) / as [H,W,F]
+
+
+class OlsrTsdfVolume(C.Structure):
+    """struct olsr_tsdf_volume, include/olsr.h."""
+
+    _fields_ = [(n, C.c_int32) for n in ("X", "Y", "Z", "F", "feat_mode")] + [
+        ("voxel_size", C.c_float), ("trunc_margin", C.c_float), ("origin", C.c_float * 3),
+        ("tsdf", _fp), ("weight", _fp), ("feat", _fp)]
+
+
+class OlsrTsdfView(C.Structure):
+    """struct olsr_tsdf_view, include/olsr.h."""
+
+    _fields_ = [(n, C.c_float) for n in ("fx", "fy", "cx", "cy")] + [("pose", C.c_float * 16), ("obs_weight", C.c_float),
+                ("min_opacity", C.c_float), ("H", C.c_int32), ("W", C.c_int32), ("feat_layout", C.c_int32), ("_pad0", C.c_int32),
+                ("depth", _fp), ("feat", _fp), ("opacity", _fp)]
+
+
 class OlsrLossParams(C.Structure):
     """struct olsr_loss_params, include/olsr.h."""
 

@@ -1,0 +1,324 @@
+// k_tsdf.hip — TSDF fusion of depth and feature images into a voxel volume, and its surface point cloud (include/olsr.h,
+// "TSDF fusion").
+//
+// The reference (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) launches one `integrate` kernel per frame after uploading the
+// depth image and up to 15 feature images from the host, keeps 15 separate feature volumes, and extracts the surface on the
+// host.  Here
+//
+//   tsdf_integrate<F, PACKED>  one launch for up to OLSR_TSDF_MAX_VIEWS views.  A thread owns a voxel (z fastest: consecutive
+//                              lanes are consecutive addresses of every plane of the volume), walks the views in index order
+//                              and keeps tsdf, weight and the F feature means in registers from the first view that reaches
+//                              the voxel to one store at the end.  The views (intrinsics, pose, image pointers) are kernel
+//                              arguments: scalar loads, no device-side table.
+//   tsdf_surface_count / tsdf_surface_prefix / tsdf_surface_emit
+//                              count the zero crossings each voxel owns, prefix the block counts in block order, write the
+//                              points: the pattern of k_map_edit.hip, no atomics, output in voxel order then axis.
+//
+// Per voxel and view the float32 expressions are the reference kernel's, in its order (fusion.py:93-139, fusion3.py:181-290);
+// the translation unit is compiled without FMA contraction (build.py) and float division is correctly rounded, so the volume
+// equals a float32 restatement of those statements (tests/tsdf_ref.py) bit for bit.  Divergences from the reference kernel,
+// each on purpose (include/olsr.h lists them for callers):
+//   - voxel coordinates come from integer division of the linear index (the reference divides (float)voxel_idx: wrong above
+//     2^24 voxels);
+//   - the bound is idx < N (the reference tests voxel_idx > N);
+//   - !(cam_z > 0) skips the voxel (the reference kernel skips cam_z < 0 only and converts the pixel coordinate of a voxel in
+//     the camera plane, an infinity or a NaN, to int; its CPU path tests pix_z > 0);
+//   - the rounded pixel coordinate is compared with the image size as a float, then converted;
+//   - rounding is roundf, half away from zero, as in the reference kernel (its CPU path: np.round, half to even);
+//   - an optional opacity plane masks pixels no Gaussian covers.
+//
+// HBM-bound.  Per batch the volume traffic is one read and one write of (2 + F) floats per touched voxel, whatever the number
+// of views; the image gathers of neighbouring voxels fall on neighbouring pixels and are served by the caches.
+#include "olsr_device.h"
+#include "olsr_kernels.h"
+
+namespace olsr {
+
+constexpr int TS_THREADS = 256;
+constexpr int TS_WAVES = TS_THREADS / 64;
+constexpr int TS_MAX_BLOCKS = 256 * 8;  // integrate and init walk the volume with a grid stride beyond this
+constexpr int TS_PREFIX_THREADS = 1024;
+
+struct TsdfViews {
+  olsr_tsdf_view v[OLSR_TSDF_MAX_VIEWS];
+};
+
+__global__ __launch_bounds__(TS_THREADS) void tsdf_init(olsr_tsdf_volume vol, int planes) {
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  for (size_t i = (size_t)blockIdx.x * TS_THREADS + threadIdx.x; i < N; i += (size_t)gridDim.x * TS_THREADS) {
+    vol.tsdf[i] = 1.0f;
+    vol.weight[i] = 0.0f;
+    for (int c = 0; c < planes; ++c) vol.feat[(size_t)c * N + i] = 0.0f;
+  }
+}
+
+template <int F, bool PACKED>
+__global__ __launch_bounds__(TS_THREADS) void tsdf_integrate(olsr_tsdf_volume vol, int n_views, TsdfViews vs) {
+  constexpr int PLANES = PACKED ? 1 : F;
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int YZ = vol.Y * vol.Z;
+  for (size_t idx = (size_t)blockIdx.x * TS_THREADS + threadIdx.x; idx < N; idx += (size_t)gridDim.x * TS_THREADS) {
+    const int i = (int)idx;
+    const int x = i / YZ, rem = i - x * YZ;
+    const int y = rem / vol.Z, z = rem - y * vol.Z;
+    // voxel grid coordinates to world coordinates
+    const float pt_x = vol.origin[0] + (float)x * vol.voxel_size;
+    const float pt_y = vol.origin[1] + (float)y * vol.voxel_size;
+    const float pt_z = vol.origin[2] + (float)z * vol.voxel_size;
+    bool loaded = false;
+    float tsdf = 0.0f, w = 0.0f;
+    float feat[PLANES > 0 ? PLANES : 1];
+    for (int v = 0; v < n_views; ++v) {
+      const olsr_tsdf_view& c = vs.v[v];
+      // world coordinates to camera coordinates
+      const float tmp_x = pt_x - c.pose[0 * 4 + 3];
+      const float tmp_y = pt_y - c.pose[1 * 4 + 3];
+      const float tmp_z = pt_z - c.pose[2 * 4 + 3];
+      const float cam_x = c.pose[0 * 4 + 0] * tmp_x + c.pose[1 * 4 + 0] * tmp_y + c.pose[2 * 4 + 0] * tmp_z;
+      const float cam_y = c.pose[0 * 4 + 1] * tmp_x + c.pose[1 * 4 + 1] * tmp_y + c.pose[2 * 4 + 1] * tmp_z;
+      const float cam_z = c.pose[0 * 4 + 2] * tmp_x + c.pose[1 * 4 + 2] * tmp_y + c.pose[2 * 4 + 2] * tmp_z;
+      if (!(cam_z > 0.0f)) continue;
+      // camera coordinates to image pixels
+      const float px = roundf(c.fx * (cam_x / cam_z) + c.cx);
+      const float py = roundf(c.fy * (cam_y / cam_z) + c.cy);
+      if (!(px >= 0.0f && px < (float)c.W && py >= 0.0f && py < (float)c.H)) continue;  // (a NaN fails every comparison)
+      const int pix = (int)py * c.W + (int)px;
+      const float depth_value = c.depth[pix];
+      if (depth_value == 0.0f) continue;
+      if (c.opacity && c.opacity[pix] < c.min_opacity) continue;
+      const float depth_diff = depth_value - cam_z;
+      if (depth_diff < -vol.trunc_margin) continue;
+      const float dist = fminf(1.0f, depth_diff / vol.trunc_margin);
+      if (!loaded) {
+        loaded = true;
+        tsdf = vol.tsdf[idx];
+        w = vol.weight[idx];
+#pragma unroll
+        for (int k = 0; k < PLANES; ++k) feat[k] = vol.feat[(size_t)k * N + idx];
+      }
+      const float w_old = w, obs_weight = c.obs_weight;
+      const float w_new = w_old + obs_weight;
+      w = w_new;
+      tsdf = (tsdf * w_old + obs_weight * dist) / w_new;
+      if constexpr (PACKED) {
+        const float old_color = feat[0];
+        const float old_b = floorf(old_color / 65536.0f);
+        const float old_g = floorf((old_color - old_b * 65536.0f) / 256.0f);
+        const float old_r = old_color - old_b * 65536.0f - old_g * 256.0f;
+        const float new_color = c.feat[pix];
+        float new_b = floorf(new_color / 65536.0f);
+        float new_g = floorf((new_color - new_b * 65536.0f) / 256.0f);
+        float new_r = new_color - new_b * 65536.0f - new_g * 256.0f;
+        new_b = fminf(roundf((old_b * w_old + obs_weight * new_b) / w_new), 255.0f);
+        new_g = fminf(roundf((old_g * w_old + obs_weight * new_g) / w_new), 255.0f);
+        new_r = fminf(roundf((old_r * w_old + obs_weight * new_r) / w_new), 255.0f);
+        feat[0] = new_b * 65536.0f + new_g * 256.0f + new_r;
+      } else if constexpr (F > 0) {
+        const bool rows = c.feat_layout == OLSR_TSDF_IMAGE_ROWS;
+        const size_t base = rows ? (size_t)pix * F : (size_t)pix;
+        const size_t step = rows ? (size_t)1 : (size_t)c.H * c.W;
+#pragma unroll
+        for (int k = 0; k < F; ++k) feat[k] = (feat[k] * w_old + obs_weight * c.feat[base + k * step]) / w_new;
+      }
+    }
+    if (loaded) {
+      vol.tsdf[idx] = tsdf;
+      vol.weight[idx] = w;
+#pragma unroll
+      for (int k = 0; k < PLANES; ++k) vol.feat[(size_t)k * N + idx] = feat[k];
+    }
+  }
+}
+
+// ---- the surface point cloud -----------------------------------------------------------------------------------------------
+// scratch: [block counts int32 nb] [block offsets int32 nb], nb = blocks of TS_THREADS voxels
+__host__ __device__ inline size_t ts_blocks(size_t N) { return (N + TS_THREADS - 1) / TS_THREADS; }
+
+size_t tsdf_surface_scratch_bytes(int X, int Y, int Z) {
+  const size_t N = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
+  return 2 * ts_blocks(N) * sizeof(int32_t) + 16;
+}
+
+// bit a of the result: the edge from voxel i = (x, y, z) along axis a (0 x, 1 y, 2 z) is owned by it and crosses zero
+__device__ inline int ts_crossings(const olsr_tsdf_volume& vol, float min_weight, int i, int x, int y, int z, float t0) {
+  const int YZ = vol.Y * vol.Z;
+  const bool use_w = min_weight > 0.0f;
+  if (use_w && !(vol.weight[i] >= min_weight)) return 0;
+  const bool neg0 = t0 < 0.0f;
+  int bits = 0;
+  const int stride[3] = {YZ, vol.Z, 1};
+  const bool inside[3] = {x + 1 < vol.X, y + 1 < vol.Y, z + 1 < vol.Z};
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    if (!inside[a]) continue;
+    const int j = i + stride[a];
+    if ((vol.tsdf[j] < 0.0f) != neg0 && (!use_w || vol.weight[j] >= min_weight)) bits |= 1 << a;
+  }
+  return bits;
+}
+
+// exclusive prefix of v over the block's threads (thread order); total: the block's sum
+__device__ inline int ts_block_scan(int v, int32_t* wave_sums, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int x = v;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) {
+    const int y = __shfl_up(x, d, 64);
+    if (lane >= d) x += y;
+  }
+  if (lane == 63) wave_sums[wave] = x;
+  __syncthreads();
+  int before = 0;
+  total = 0;
+#pragma unroll
+  for (int k = 0; k < TS_WAVES; ++k) {
+    const int s = wave_sums[k];
+    if (k < wave) before += s;
+    total += s;
+  }
+  return before + x - v;
+}
+
+template <bool EMIT>
+__global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol, float min_weight, int32_t* __restrict__ counts,
+                                                           const int32_t* __restrict__ offsets, int capacity,
+                                                           float* __restrict__ points, float* __restrict__ feats,
+                                                           int32_t* __restrict__ voxel_index) {
+  __shared__ int32_t wave_sums[TS_WAVES];
+  const int N = vol.X * vol.Y * vol.Z;
+  const int YZ = vol.Y * vol.Z;
+  const int i = blockIdx.x * TS_THREADS + threadIdx.x;
+  int x = 0, y = 0, z = 0, bits = 0;
+  float t0 = 0.0f;
+  if (i < N) {
+    x = i / YZ;
+    const int rem = i - x * YZ;
+    y = rem / vol.Z;
+    z = rem - y * vol.Z;
+    t0 = vol.tsdf[i];
+    bits = ts_crossings(vol, min_weight, i, x, y, z, t0);
+  }
+  int total;
+  const int rank = ts_block_scan(__popc(bits), wave_sums, total);
+  if constexpr (!EMIT) {
+    if (threadIdx.x == 0) counts[blockIdx.x] = total;
+    return;
+  } else {
+    if (!bits) return;
+    int k = offsets[blockIdx.x] + rank;
+    const int stride[3] = {YZ, vol.Z, 1};
+    const int planes = vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB ? 3 : vol.F;
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (!(bits & (1 << a))) continue;
+      if (k >= capacity) return;
+      const float t1 = vol.tsdf[i + stride[a]];
+      const float v[3] = {(float)x, (float)y, (float)z};
+      float pos[3] = {v[0], v[1], v[2]};
+      pos[a] = v[a] + t0 / (t0 - t1);
+      // the voxel the reference reads the vertex's colour from: np.round(verts).astype(int) — the owner or its neighbour
+      // (a NaN position, from a NaN or infinite distance, stays with the owner)
+      const int nearest = rintf(pos[a]) == v[a] + 1.0f ? i + stride[a] : i;
+#pragma unroll
+      for (int d = 0; d < 3; ++d) points[(size_t)3 * k + d] = pos[d] * vol.voxel_size + vol.origin[d];
+      if (voxel_index) voxel_index[k] = i;
+      if (feats) {
+        if (vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB) {
+          const float rgb_val = vol.feat[nearest];
+          const float b = floorf(rgb_val / 65536.0f);
+          const float g = floorf((rgb_val - b * 65536.0f) / 256.0f);
+          const float r = rgb_val - b * 65536.0f - g * 256.0f;
+          feats[(size_t)3 * k] = r;
+          feats[(size_t)3 * k + 1] = g;
+          feats[(size_t)3 * k + 2] = b;
+        } else {
+          for (int c = 0; c < planes; ++c) feats[(size_t)planes * k + c] = vol.feat[(size_t)c * N + nearest];
+        }
+      }
+      ++k;
+    }
+  }
+}
+
+// exclusive prefix of the block counts in block order; status = {N, 0}
+__global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_surface_prefix(int nb, const int32_t* __restrict__ counts,
+                                                                          int32_t* __restrict__ offsets,
+                                                                          int32_t* __restrict__ status) {
+  __shared__ int32_t part[TS_PREFIX_THREADS / 64];
+  __shared__ int32_t carry_sh;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int32_t carry = 0;
+  for (int base = 0; base < nb; base += TS_PREFIX_THREADS) {
+    const int i = base + threadIdx.x;
+    const int32_t v = i < nb ? counts[i] : 0;
+    int32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+      const int32_t y = __shfl_up(x, d, 64);
+      if (lane >= d) x += y;
+    }
+    if (lane == 63) part[wave] = x;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      int32_t acc = 0;
+      for (int k = 0; k < TS_PREFIX_THREADS / 64; ++k) {
+        const int32_t t = part[k];
+        part[k] = acc;
+        acc += t;
+      }
+      carry_sh = acc;
+    }
+    __syncthreads();
+    if (i < nb) offsets[i] = carry + part[wave] + x - v;
+    carry += carry_sh;
+    __syncthreads();
+  }
+  if (threadIdx.x == 0) {
+    status[0] = carry;
+    status[1] = 0;
+  }
+}
+
+// ---- launchers ---------------------------------------------------------------------------------------------------------------
+static int ts_grid(size_t N) {
+  const size_t nb = ts_blocks(N);
+  return (int)(nb < (size_t)TS_MAX_BLOCKS ? nb : (size_t)TS_MAX_BLOCKS);
+}
+
+void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st) {
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int planes = vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB ? 1 : vol.F;
+  tsdf_init<<<ts_grid(N), TS_THREADS, 0, st>>>(vol, planes);
+}
+
+void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_tsdf_view* views, hipStream_t st) {
+  TsdfViews vs{};
+  for (int v = 0; v < n_views; ++v) vs.v[v] = views[v];
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int grid = ts_grid(N);
+#define OLSR_TSDF_LAUNCH(F_, PACKED_) tsdf_integrate<F_, PACKED_><<<grid, TS_THREADS, 0, st>>>(vol, n_views, vs)
+  if (vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB) OLSR_TSDF_LAUNCH(1, true);
+  else if (vol.F == 0) OLSR_TSDF_LAUNCH(0, false);
+  else if (vol.F == 3) OLSR_TSDF_LAUNCH(3, false);
+  else if (vol.F == 15) OLSR_TSDF_LAUNCH(15, false);
+  else if (vol.F == 16) OLSR_TSDF_LAUNCH(16, false);
+  else OLSR_TSDF_LAUNCH(32, false);
+#undef OLSR_TSDF_LAUNCH
+}
+
+void launch_tsdf_surface_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st) {
+  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
+  int32_t* counts = reinterpret_cast<int32_t*>(scratch);
+  int32_t* offsets = counts + nb;
+  tsdf_surface<false><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, counts, nullptr, 0, nullptr, nullptr, nullptr);
+  tsdf_surface_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, counts, offsets, status);
+}
+
+void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, const void* scratch, int capacity, float* points,
+                              float* feats, int32_t* voxel_index, hipStream_t st) {
+  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
+  const int32_t* offsets = reinterpret_cast<const int32_t*>(scratch) + nb;
+  tsdf_surface<true><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, nullptr, offsets, capacity, points, feats, voxel_index);
+}
+
+}  // namespace olsr

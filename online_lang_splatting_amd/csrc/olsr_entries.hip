@@ -1,5 +1,5 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, TSDF fusion.
 #include <hip/hip_runtime.h>
 
 #include "olsr_host.h"
@@ -359,6 +359,67 @@ int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_par
   launch_map_edit_apply(P, M, F, *params, *src, z, append, scratch, status, dst_capacity, *dst, src_index,
                         (hipStream_t)hip_stream);
   return launch_check("map_edit_apply");
+}
+
+// what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)
+static const char* tsdf_volume_error(const olsr_tsdf_volume* v, bool surface) {
+  if (!v) return "volume is required";
+  if (v->X < 1 || v->Y < 1 || v->Z < 1) return "volume: X, Y, Z must be >= 1";
+  const int64_t limit = surface ? (((int64_t)1 << 31) - 1) / 3 : ((int64_t)1 << 31) - 1;
+  if ((int64_t)v->X * v->Y > limit || (int64_t)v->X * v->Y * v->Z > limit)
+    return surface ? "volume: 3 X Y Z must be below 2^31" : "volume: X Y Z must be below 2^31";
+  if (v->feat_mode == OLSR_TSDF_FEAT_PACKED_RGB) {
+    if (v->F != 1) return "volume: F must be 1 with OLSR_TSDF_FEAT_PACKED_RGB";
+  } else if (v->feat_mode != OLSR_TSDF_FEAT_FLOAT) {
+    return "volume: unknown feat_mode";
+  } else if (!supported_F(v->F)) {
+    return "volume: F must be one of 0, 3, 15, 16, 32";
+  }
+  if (!(v->voxel_size > 0.0f) || !(v->trunc_margin > 0.0f)) return "volume: voxel_size and trunc_margin must be > 0";
+  if (!v->tsdf || !v->weight || (v->F > 0 && !v->feat)) return "volume: tsdf, weight and (F > 0) feat are required";
+  return nullptr;
+}
+
+int olsr_tsdf_init(const olsr_tsdf_volume* volume, void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, false)) return fail(OLSR_ERR_ARG, std::string("tsdf_init: ") + e);
+  launch_tsdf_init(*volume, (hipStream_t)hip_stream);
+  return launch_check("tsdf_init");
+}
+
+int olsr_tsdf_integrate(const olsr_tsdf_volume* volume, int32_t n_views, const olsr_tsdf_view* views, void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, false)) return fail(OLSR_ERR_ARG, std::string("tsdf_integrate: ") + e);
+  if (n_views < 1 || n_views > OLSR_TSDF_MAX_VIEWS || !views)
+    return fail(OLSR_ERR_ARG, "tsdf_integrate: between 1 and 16 views");
+  for (int v = 0; v < n_views; ++v) {
+    const olsr_tsdf_view& c = views[v];
+    if (c.H < 1 || c.W < 1 || (int64_t)c.H * c.W > (((int64_t)1 << 31) - 1) / 32)
+      return fail(OLSR_ERR_ARG, "tsdf_integrate: a view's H, W must be >= 1 and 32 H W below 2^31");
+    if (!c.depth || (volume->F > 0 && !c.feat)) return fail(OLSR_ERR_ARG, "tsdf_integrate: a view's depth and (F > 0) feat are required");
+    if (c.feat_layout != OLSR_TSDF_IMAGE_CHANNELS && c.feat_layout != OLSR_TSDF_IMAGE_ROWS)
+      return fail(OLSR_ERR_ARG, "tsdf_integrate: unknown feat_layout");
+  }
+  launch_tsdf_integrate(*volume, n_views, views, (hipStream_t)hip_stream);
+  return launch_check("tsdf_integrate");
+}
+
+size_t olsr_tsdf_surface_scratch_bytes(int32_t X, int32_t Y, int32_t Z) { return tsdf_surface_scratch_bytes(X, Y, Z); }
+
+int olsr_tsdf_surface_plan(const olsr_tsdf_volume* volume, float min_weight, void* scratch, int32_t* status, void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, true)) return fail(OLSR_ERR_ARG, std::string("tsdf_surface_plan: ") + e);
+  if (!scratch || !status) return fail(OLSR_ERR_ARG, "tsdf_surface_plan: scratch and status are required");
+  launch_tsdf_surface_plan(*volume, min_weight, scratch, status, (hipStream_t)hip_stream);
+  return launch_check("tsdf_surface_plan");
+}
+
+int olsr_tsdf_surface_emit(const olsr_tsdf_volume* volume, float min_weight, const void* scratch, int32_t capacity,
+                           float* points, float* feats, int32_t* voxel_index, void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, true)) return fail(OLSR_ERR_ARG, std::string("tsdf_surface_emit: ") + e);
+  if (capacity < 0 || !scratch) return fail(OLSR_ERR_ARG, "tsdf_surface_emit: scratch and capacity >= 0 are required");
+  if (capacity == 0) return OLSR_OK;
+  if (!points || (volume->F > 0 && !feats)) return fail(OLSR_ERR_ARG, "tsdf_surface_emit: points and (F > 0) feats are required");
+  launch_tsdf_surface_emit(*volume, min_weight, scratch, capacity, points, volume->F > 0 ? feats : nullptr, voxel_index,
+                           (hipStream_t)hip_stream);
+  return launch_check("tsdf_surface_emit");
 }
 
 }  // extern "C"

@@ -275,4 +275,12 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
                                  float* blended, float* score, int32_t* coord, float* minmax, uint8_t* mask, int32_t* labels,
                                  void* scratch, hipStream_t st);
 
+// k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface point cloud (include/olsr.h)
+void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st);
+void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_tsdf_view* views, hipStream_t st);
+size_t tsdf_surface_scratch_bytes(int X, int Y, int Z);
+void launch_tsdf_surface_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st);
+void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, const void* scratch, int capacity, float* points,
+                              float* feats, int32_t* voxel_index, hipStream_t st);
+
 }  // namespace olsr
