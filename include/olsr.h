@@ -991,6 +991,14 @@ int olsr_debug_backward_ordered(const olsr_scene *scene, const void *geometry_bu
  * Returns the value in force. */
 int olsr_debug_sort_threads(int threads);
 
+/* Test instrument: the composites' exp (csrc/olsr_device.h, pinned_expf and its packed form) against the sequence it replaced
+ * (pinned_expf_ref), bit for bit, on the GPU.  For each of the `count` float32 bit patterns from first_bits on (first_bits +
+ * count <= 2^32) it evaluates both forms scalar, packed with the pattern in lane x and ANOTHER pattern of the range in lane y,
+ * and packed with the lanes swapped; both lanes of a packed result are compared.  out (host memory): [0] / [1] / [2] the number
+ * of patterns whose scalar / packed / swapped results differ, [3] the lowest differing pattern, or ~0 if there is none.
+ * Synchronous, on the null stream. */
+int olsr_debug_exp_sweep(uint32_t first_bits, uint64_t count, uint64_t out[4]);
+
 const char *olsr_last_error(void);
 const char *olsr_version(void);
 

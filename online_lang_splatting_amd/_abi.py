@@ -25,6 +25,11 @@ FLAG_FWD_ACCUM_MFMA = 2      # OLSR_FLAG_FWD_ACCUM_MFMA: the forward's feature a
 BINNING_RECT = 0     # every tile of the reference's bounding square (bit-identical instance lists)
 BINNING_ELLIPSE = 1  # only tiles the alpha >= 1/255 ellipse reaches (identical outputs, shorter lists)
 
+# olsr_debug_exp_sweep: the arguments the composites' exp can be handed and consume — float32 bit patterns, inclusive:
+# -0 ... -90 (below the -87 clamp) and +0 ... +88 — and the specials every form must agree on as well
+EXP_SWEEP_RANGES = ((0x80000000, 0xC2B40000), (0x00000000, 0x42B00000))
+EXP_SWEEP_SPECIALS = (0x7F800000, 0xFF800000, 0x7FC00000, 0xFFC00000, 0xFFFFFFFF, 0xF149F2CA)  # +-inf, NaNs, -1e30
+
 SUPPORTED_F = (0, 3, 15, 16, 32)
 SUPPORTED_TILES = (15, 16)
 

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("OLSR_LIB") or os.path.join(_HERE, "libolsr.so")
 EXPORTS = (
     "olsr_geometry_bytes", "olsr_image_bytes", "olsr_binning_bytes", "olsr_backward_scratch_bytes", "olsr_last_forward_token", "olsr_live_rows", "olsr_forward", "olsr_forward_async", "olsr_forward_async_loss", "olsr_fused_loss_scratch_bytes",
     "olsr_backward", "olsr_accumulate_gradients", "olsr_sparse_exchange_mask", "olsr_sparse_exchange_scratch_ints", "olsr_sparse_exchange_pack", "olsr_sparse_exchange_unpack", "olsr_mapping_loss", "olsr_mapping_loss_scratch_bytes", "olsr_tracking_loss", "olsr_refinement_loss", "olsr_refinement_loss_scratch_bytes", "olsr_lang_ae_scratch_bytes", "olsr_lang_ae_train_step", "olsr_lang_ae_encode", "olsr_lang_ae_decode", "olsr_lang_query_scratch_bytes", "olsr_lang_query_sims", "olsr_lang_query_relevancy", "olsr_tsdf_init", "olsr_tsdf_integrate", "olsr_tsdf_surface_scratch_bytes", "olsr_tsdf_surface_plan", "olsr_tsdf_surface_emit", "olsr_pose_step", "olsr_pose_step_gated", "olsr_knn_mean_dist2", "olsr_knn_scratch_bytes", "olsr_adam_step", "olsr_adam_step_sum", "olsr_adam_step_masked", "olsr_adam_step_groups", "olsr_map_edit_scratch_bytes", "olsr_map_edit_plan", "olsr_map_edit_apply", "olsr_bucket_add", "olsr_mark_visible", "olsr_geometry_field", "olsr_binning_field", "olsr_image_field",
-    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
+    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_debug_exp_sweep", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
 )
 
 _lib = None
@@ -131,6 +131,7 @@ def lib():
     L.olsr_debug_backward_ordered_scratch_bytes.argtypes, L.olsr_debug_backward_ordered_scratch_bytes.restype = [i64, i32], sz
     L.olsr_debug_backward_ordered.argtypes = [scene_p, vp, i32, vp, vp] + [vp] * 3 + [vp] + [vp] * 6 + [i32, vp]
     L.olsr_debug_backward_ordered.restype = C.c_int
+    L.olsr_debug_exp_sweep.argtypes, L.olsr_debug_exp_sweep.restype = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int
     L.olsr_last_error.argtypes, L.olsr_last_error.restype = [], C.c_char_p
     L.olsr_version.argtypes, L.olsr_version.restype = [], C.c_char_p
     _lib = L
@@ -149,6 +150,13 @@ def stage_times(max_entries=1 << 16):
     ms = (C.c_float * max_entries)()
     n = lib().olsr_get_stage_times(names, ms, max_entries)
     return [(names[i].decode(), float(ms[i])) for i in range(n)]
+
+
+def exp_sweep(first_bits, count):
+    """olsr_debug_exp_sweep: (scalar, packed, swapped) mismatch counts and the lowest mismatching pattern (None: none)."""
+    out = (C.c_uint64 * 4)()
+    check(lib().olsr_debug_exp_sweep(first_bits, count, out))
+    return int(out[0]), int(out[1]), int(out[2]), (None if out[3] == 2**64 - 1 else int(out[3]))
 
 
 def set_profiling(enable):

@@ -72,12 +72,27 @@ __device__ __forceinline__ int oc_count_leq_back(const u64* __restrict__ A, int 
 
 // Stable merge sort of the OC_W pairs in `a` (LDS), ping-pong with `b`; returns the buffer that holds the result.
 // Thread t owns elements t, t + T, ... of every level (consecutive lanes -> consecutive 8-byte words: conflict-free).
+// ADAPTIVE: a stable merge of two runs with !(right[0] < left[run - 1]) is the concatenation it started from, so a level whose
+// sibling runs all stand like that leaves the array as it is and is skipped (no writes, no swap of the buffers), and a window
+// that ascends already — every window of a repeated view, most windows after an optimiser step — skips all eleven after one
+// pass over its neighbours.  Both tests are block-uniform (__syncthreads_and), so every thread takes the same levels; the
+// result is what the full merges leave, pair for pair.
 template <int T>
 __device__ __forceinline__ u64* oc_window_sort(u64* a, u64* b) {
   constexpr int E = OC_W / T;
   const int tid = threadIdx.x;
+  bool asc = true;
+#pragma unroll
+  for (int k = 0; k < E; ++k) {
+    const int i = tid + k * T;
+    if (i > 0) asc &= !(a[i] < a[i - 1]);
+  }
+  if (__syncthreads_and(asc)) return a;
 #pragma unroll 1
   for (int run = 1; run < OC_W; run <<= 1) {
+    bool in_order = true;  // every right run starts at or above the end of its left sibling
+    for (int h = run + tid * 2 * run; h < OC_W; h += T * 2 * run) in_order &= !(a[h] < a[h - 1]);
+    if (__syncthreads_and(in_order)) continue;
     u64 x[E];
     int dest[E];
 #pragma unroll

@@ -215,7 +215,61 @@ __device__ __forceinline__ float max_m87(float x) {
   asm("v_max_f32 %0, 0xc2ae0000, %1" : "=v"(r) : "v"(x));
   return r;
 }
+// pinned_expf / pinned_expf2 are what the composites call.  They return the bits of the sequence above (kept verbatim below
+// as pinned_expf_ref / pinned_expf2_ref: TEST INSTRUMENT ONLY, olsr_debug_exp_sweep compares the two over every consumed
+// argument) with three exact substitutions that take the half-rate v_rndne / v_cvt_i32 and one multiply out of the visit
+// (DESIGN.md section 5):
+//   n = rint(t)          ->  tm = t + 1.5 * 2^23, n = tm - 1.5 * 2^23: the add rounds to nearest-even at unit spacing (|t| < 2^22),
+//                            the subtraction is exact
+//   (int)n + 127 << 23   ->  (bits(tm) << 23) + 0x3F800000: the low mantissa bits of tm ARE n in two's complement, the shift drops
+//                            the rest
+//   (q + 1) * 2^n        ->  fma(q, 2^n, 2^n): scaling by a power of two commutes with the rounding while the result is normal,
+//                            which the -87 clamp guarantees
+constexpr float EXP_MAGIC = 12582912.0f;  // 1.5 * 2^23
 __device__ __forceinline__ float pinned_expf(float x) {
+  x = max_m87(x);
+  const float tm = x * 1.44269504088896341f + EXP_MAGIC;
+  const float n = tm - EXP_MAGIC;
+  float r = __builtin_fmaf(n, -0.693359375f, x);
+  r = __builtin_fmaf(n, 2.12194440e-4f, r);
+  float p = 1.9875691500e-4f;
+  p = __builtin_fmaf(p, r, 1.3981999507e-3f);
+  p = __builtin_fmaf(p, r, 8.3334519073e-3f);
+  p = __builtin_fmaf(p, r, 4.1665795894e-2f);
+  p = __builtin_fmaf(p, r, 1.6666665459e-1f);
+  p = __builtin_fmaf(p, r, 5.0000001201e-1f);
+  const float q = __builtin_fmaf(p, r * r, r);
+  const float sc = bits2f((f2bits(tm) << 23) + 0x3F800000u);
+  return __builtin_fmaf(q, sc, sc);
+}
+
+// the same routine on two values at once (packed fp32: every component is the IEEE operation of pinned_expf).
+// The scale is computed on an INTEGER vector: written per component from the float vector ({bits2f(f2bits(tm.x) << 23 ...),
+// bits2f(f2bits(tm.y) << 23 ...)}) this toolchain emits one shift and gives lane y lane x's scale.
+typedef float v2f_ __attribute__((ext_vector_type(2)));
+typedef u32 v2u_ __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ v2f_ pinned_expf2(v2f_ x) {
+  x.x = max_m87(x.x);
+  x.y = max_m87(x.y);
+  const v2f_ tm = x * v2f_{1.44269504088896341f, 1.44269504088896341f} + v2f_{EXP_MAGIC, EXP_MAGIC};
+  const v2f_ n = tm - v2f_{EXP_MAGIC, EXP_MAGIC};
+  v2f_ r = __builtin_elementwise_fma(n, v2f_{-0.693359375f, -0.693359375f}, x);
+  r = __builtin_elementwise_fma(n, v2f_{2.12194440e-4f, 2.12194440e-4f}, r);
+  v2f_ p = {1.9875691500e-4f, 1.9875691500e-4f};
+  p = __builtin_elementwise_fma(p, r, v2f_{1.3981999507e-3f, 1.3981999507e-3f});
+  p = __builtin_elementwise_fma(p, r, v2f_{8.3334519073e-3f, 8.3334519073e-3f});
+  p = __builtin_elementwise_fma(p, r, v2f_{4.1665795894e-2f, 4.1665795894e-2f});
+  p = __builtin_elementwise_fma(p, r, v2f_{1.6666665459e-1f, 1.6666665459e-1f});
+  p = __builtin_elementwise_fma(p, r, v2f_{5.0000001201e-1f, 5.0000001201e-1f});
+  const v2f_ q = __builtin_elementwise_fma(p, r * r, r);
+  const v2u_ sb = (__builtin_bit_cast(v2u_, tm) << 23) + v2u_{0x3F800000u, 0x3F800000u};
+  const v2f_ sc = __builtin_bit_cast(v2f_, sb);
+  return __builtin_elementwise_fma(q, sc, sc);
+}
+
+// ---- the textbook sequence (rint, float -> int, multiply), verbatim as the composites ran it before: TEST INSTRUMENT ONLY
+// (olsr_debug_exp_sweep), never on a product path ----
+__device__ __forceinline__ float pinned_expf_ref(float x) {
   x = max_m87(x);
   float n = __builtin_rintf(x * 1.44269504088896341f);
   float r = __builtin_fmaf(n, -0.693359375f, x);
@@ -231,9 +285,8 @@ __device__ __forceinline__ float pinned_expf(float x) {
   return e * bits2f((u32)(ni + 127) << 23);
 }
 
-// the same routine on two values at once (packed fp32: every component is the IEEE operation of pinned_expf)
-typedef float v2f_ __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ v2f_ pinned_expf2(v2f_ x) {
+// the same routine on two values at once (packed fp32: every component is the IEEE operation of pinned_expf_ref)
+__device__ __forceinline__ v2f_ pinned_expf2_ref(v2f_ x) {
   x.x = max_m87(x.x);
   x.y = max_m87(x.y);
   const v2f_ t = x * v2f_{1.44269504088896341f, 1.44269504088896341f};

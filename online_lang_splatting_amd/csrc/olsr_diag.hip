@@ -38,6 +38,37 @@ __global__ void stamp_kernel(unsigned long long* slot, unsigned long long tag) {
   slot[1] = tag;
 }
 
+// olsr_debug_exp_sweep: the composites' exp (pinned_expf / pinned_expf2) against the sequence it replaced, bit for bit, over
+// a range of argument bit patterns.  acc = {scalar mismatches, packed mismatches with the pattern in lane x, packed mismatches
+// with the pattern in lane y, first (lowest) mismatching pattern or ~0}.  The other lane holds ANOTHER pattern of the range
+// (half the range further on, wrapping), so a scale that leaks from one lane to the other shows.
+__global__ __launch_bounds__(256) void exp_sweep_kernel(u32 first, unsigned long long count, unsigned long long* acc) {
+  const unsigned long long stride = (unsigned long long)gridDim.x * blockDim.x;
+  const unsigned long long shift = (count + 1) / 2;
+  unsigned long long bad_s = 0, bad_x = 0, bad_y = 0, first_bad = ~0ull;
+  for (unsigned long long i = (unsigned long long)blockIdx.x * blockDim.x + threadIdx.x; i < count; i += stride) {
+    const u32 pat = first + (u32)i;
+    unsigned long long j = i + shift;
+    if (j >= count) j -= count;
+    const u32 other = count > 1 ? first + (u32)j : (pat == 0xC1200000u ? 0xC1A00000u : 0xC1200000u);  // (one pattern: -10 / -20)
+    const float a = bits2f(pat), b = bits2f(other);
+    const u32 ra = f2bits(pinned_expf_ref(a)), rb = f2bits(pinned_expf_ref(b));
+    const bool ms = f2bits(pinned_expf(a)) != ra;
+    const v2f_ nx = pinned_expf2(v2f_{a, b}), ox = pinned_expf2_ref(v2f_{a, b});
+    const bool mx = f2bits(nx.x) != f2bits(ox.x) || f2bits(nx.y) != f2bits(ox.y) || f2bits(nx.x) != ra || f2bits(nx.y) != rb;
+    const v2f_ ny = pinned_expf2(v2f_{b, a}), oy = pinned_expf2_ref(v2f_{b, a});
+    const bool my = f2bits(ny.x) != f2bits(oy.x) || f2bits(ny.y) != f2bits(oy.y) || f2bits(ny.x) != rb || f2bits(ny.y) != ra;
+    bad_s += ms;
+    bad_x += mx;
+    bad_y += my;
+    if ((ms || mx || my) && (unsigned long long)pat < first_bad) first_bad = pat;
+  }
+  if (bad_s) atomicAdd(acc + 0, bad_s);
+  if (bad_x) atomicAdd(acc + 1, bad_x);
+  if (bad_y) atomicAdd(acc + 2, bad_y);
+  if (first_bad != ~0ull) atomicMin(acc + 3, first_bad);
+}
+
 }  // namespace
 
 namespace olsr {
@@ -189,6 +220,24 @@ int olsr_debug_sort_plan(int64_t n, int n_is_capacity, int32_t* keys_per_thread,
   if (keys_per_thread) *keys_per_thread = p.kpt;
   if (blocks) *blocks = p.nblk;
   return fused_sort_applicable(n, 32) ? 1 : 0;
+}
+
+int olsr_debug_exp_sweep(uint32_t first_bits, uint64_t count, uint64_t* out) {
+  if (out == nullptr || count > (1ull << 32) || (unsigned long long)first_bits + count > (1ull << 32)) return OLSR_ERR_ARG;
+  unsigned long long host[4] = {0ull, 0ull, 0ull, ~0ull};
+  unsigned long long* dev = nullptr;
+  if (hipMalloc(&dev, sizeof(host)) != hipSuccess) return OLSR_ERR_ALLOC;
+  bool ok = hipMemcpy(dev, host, sizeof(host), hipMemcpyHostToDevice) == hipSuccess;
+  if (ok && count > 0) {
+    const unsigned long long want = (count + 255) / 256;
+    exp_sweep_kernel<<<(unsigned)(want < 16384 ? want : 16384), 256>>>(first_bits, count, dev);
+    ok = hipGetLastError() == hipSuccess;
+  }
+  ok = ok && hipMemcpy(host, dev, sizeof(host), hipMemcpyDeviceToHost) == hipSuccess;
+  (void)hipFree(dev);
+  if (!ok) return OLSR_ERR_DEVICE;
+  for (int i = 0; i < 4; ++i) out[i] = host[i];
+  return OLSR_OK;
 }
 
 size_t olsr_debug_backward_ordered_scratch_bytes(int64_t num_rendered, int32_t F) {
