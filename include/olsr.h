@@ -793,6 +793,53 @@ int olsr_tsdf_surface_plan(const olsr_tsdf_volume *volume, float min_weight, voi
 int olsr_tsdf_surface_emit(const olsr_tsdf_volume *volume, float min_weight, const void *scratch, int32_t capacity,
                            float *points, float *feats, int32_t *voxel_index, void *hip_stream);
 
+/* ---- point-cloud metrics: approximate earth mover's distance and Chamfer distance (the reference's 3-D evaluation) ----------
+ * The two numbers tsdf-fusion/3d_evaluation_and_visualize_langslam_dim15.py:396-423 reports per queried class, for ragged
+ * batches of cloud pairs (one pair per class) in the same launches.
+ *   B             1 <= B <= OLSR_CLOUD_MAX_SEGMENTS pairs ("segments")
+ *   off1, off2    int32[B+1], non-decreasing, off[0] >= 0: segment b of cloud 1 is rows off1[b] .. off1[b+1]-1 of xyz1 (n_b
+ *                 points), likewise cloud 2 (m_b points).  total = off[B] < 2^31 / 3.  Device memory or host memory, each table
+ *                 on its own.  The tables are checked on the host before anything is launched: device tables
+ *                 cost one 4 (B + 1)-byte read and a synchronisation of the stream, host tables one small upload into the scratch.
+ *   max_n1/2      at least the longest segment of the cloud (sizes the grid); a longer segment is OLSR_ERR_ARG
+ *   xyz1, xyz2    device float[total,3], packed
+ *   scratch       device, olsr_*_scratch_bytes(B, off1[B], off2[B]) bytes, 256-byte aligned inside; contents need not survive
+ *                 between calls.  EMD: per point 8 (the row's cost, double) + 12 (remain x 2, ratio) + 3 x 16 x 4 (cloud 1; 16 x 4
+ *                 for cloud 2) bytes of partial sums: O(n + m), no match matrix.  Chamfer: 16 x 8 bytes per point.
+ * An empty segment on either side is legal: its outputs are NaN (nn: -1), valid[b] = 0.  Non-finite coordinates make that
+ * segment's outputs unspecified and touch no other segment.  A segment's outputs depend on its own points only, bit for bit:
+ * the batch equals B single calls, and a repeated call repeats its bits (fixed-order sums, no floating-point atomics).
+ *
+ * olsr_emd_cost: PyTorchEMD's approxmatch + matchcost (tsdf-fusion/PyTorchEMD/cuda/emd_kernel.cu) without the match matrix.
+ * With d_kl = (dx dx + dy dy) + dz dz (squared), multiL, multiR = (1, n / m) if n >= m else (m / n, 1) in integer division,
+ * remainL = multiL, remainR = multiR, for j = 7 .. -2 (level = -4^j, 0 at j = -2) and e_kl = exp(level d_kl):
+ *   1. ratioL[k] = remainL[k] / (1e-9 + sum_l e_kl remainR[l])
+ *   2. sumr[l] = (sum_k e_kl ratioL[k]) remainR[l];  ratioR[l] = min(remainR[l] / (sumr[l] + 1e-9), 1) remainR[l];
+ *      remainR[l] = max(0, remainR[l] - sumr[l])
+ *   3. w_kl = e_kl ratioL[k] ratioR[l];  cost += sum_kl d_kl w_kl;  remainL[k] = max(0, remainL[k] - sum_l w_kl)
+ * in float32; exp is the hardware's 2^x on (level log2 e) d, as the reference uses __expf.  Sums over the other cloud are
+ * float32 partials over at most 16 chunks of it, added in chunk order; d w is summed in float32 per row, chunk and level and
+ * in double over those.  cost[b] is sum d w, NOT divided by n (the reference's earth_mover_distance divides by n afterwards).
+ *   residual      float[B,2] or NULL: sum remainL, sum remainR after the last level — the mass the approximate matching left
+ *                 unassigned, which the reference drops silently
+ * 23 launches for any B and any sizes (1 + 1 + 2 per level + 1), nothing read back in between.  No backward: the evaluation's
+ * copy of emd.py saves nothing for one either.
+ *
+ * olsr_chamfer: per point the squared distance to its nearest point of the other cloud of its segment (d as above, not
+ * contracted) and that point's segment-local index, the lowest index on ties; mean[b] = {mean over cloud 1 of sqrt(min_d2_1),
+ * mean over cloud 2 of sqrt(min_d2_2)} in double — chamfer_distance's 'x_to_y' and 'y_to_x' with x = cloud 1; 'bi' is their
+ * sum.  Brute force, n m pairs per segment; two launches. */
+#define OLSR_CLOUD_MAX_SEGMENTS 32767
+size_t olsr_emd_scratch_bytes(int32_t B, int64_t total1, int64_t total2);
+int olsr_emd_cost(int32_t B, const int32_t *off1, const int32_t *off2, int32_t max_n1, int32_t max_n2,
+                  const float *xyz1, const float *xyz2, double *cost /*[B], sum d w, undivided*/,
+                  float *residual /*[B,2] = sum remainL, sum remainR after the last level; may be NULL*/,
+                  int32_t *valid /*[B]*/, void *scratch, void *hip_stream);
+size_t olsr_chamfer_scratch_bytes(int32_t B, int64_t total1, int64_t total2);
+int olsr_chamfer(int32_t B, const int32_t *off1, const int32_t *off2, int32_t max_n1, int32_t max_n2,
+                 const float *xyz1, const float *xyz2, float *min_d2_1, int32_t *nn_1, float *min_d2_2, int32_t *nn_2,
+                 double *mean /*[B,2]: x->y, y->x*/, int32_t *valid, void *scratch, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

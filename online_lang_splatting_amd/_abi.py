@@ -155,6 +155,9 @@ class OlsrLangQueryParams(C.Structure):
                                  "out_height")] + [("thresh", C.c_float), ("flags", C.c_uint32)]
 
 
+# point-cloud metrics (OLSR_CLOUD_*)
+CLOUD_MAX_SEGMENTS = 32767
+
 # TSDF fusion (OLSR_TSDF_*)
 TSDF_MAX_VIEWS = 16
 TSDF_FEAT_FLOAT, TSDF_FEAT_PACKED_RGB = 0, 1

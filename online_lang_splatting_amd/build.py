@@ -45,6 +45,7 @@ UNITS = [
     ("k_map_edit.hip", "k_map_edit.o", []),
     ("k_pose.hip", "k_pose.o", []),
     ("k_tsdf.hip", "k_tsdf.o", []),
+    ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),
 ]
 HEADERS = ["olsr_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", os.path.join("..", "..", "include", "olsr.h")]
 

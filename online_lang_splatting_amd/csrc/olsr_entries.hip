@@ -1,6 +1,10 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, TSDF fusion.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, TSDF fusion, point-cloud metrics.
 #include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <cstring>
+#include <vector>
 
 #include "olsr_host.h"
 
@@ -34,6 +38,73 @@ int adam_entry(const char* who, int32_t P, int32_t M, int32_t F, const olsr_adam
 
 const char* adam_params_error(const olsr_adam_params* params) {
   return (!params || params->step < 1) ? "adam params are required and step must be >= 1" : nullptr;
+}
+
+// The segment tables of olsr_emd_cost / olsr_chamfer.  The offsets are read on the host — from device memory with one copy
+// and a synchronisation of the stream, from host memory directly — and checked.  dev1 / dev2: what the kernels read, the
+// caller's device pointers or, when the offsets arrived in host memory, the copies parked in the scratch.
+struct CloudSegments {
+  long long total1 = 0, total2 = 0;
+  const int32_t *dev1 = nullptr, *dev2 = nullptr;
+};
+// reads and checks one table; on_device: where it lives
+int cloud_offsets(const std::string& who, const char* name, int32_t B, const int32_t* off, int32_t max_n, hipStream_t st,
+                  std::vector<int32_t>& h, bool* on_device) {
+  h.resize((size_t)B + 1);
+  hipPointerAttribute_t at;
+  *on_device = hipPointerGetAttributes(&at, off) == hipSuccess && at.type == hipMemoryTypeDevice;
+  (void)hipGetLastError();   // (a plain host pointer, or no device at all, is an error to the query)
+  if (*on_device) {
+    HIP_TRY(hipMemcpyAsync(h.data(), off, h.size() * sizeof(int32_t), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+  } else {
+    std::memcpy(h.data(), off, h.size() * sizeof(int32_t));
+  }
+  if (h[0] < 0) return fail(OLSR_ERR_ARG, who + ": " + name + "[0] must be >= 0");
+  int32_t longest = 0;
+  for (int32_t b = 0; b < B; ++b) {
+    if (h[b + 1] < h[b]) return fail(OLSR_ERR_ARG, who + ": " + name + " must be non-decreasing");
+    longest = std::max(longest, h[b + 1] - h[b]);
+  }
+  if ((long long)h[B] >= (1ll << 31) / 3) return fail(OLSR_ERR_ARG, who + ": " + name + "[B] must be below 2^31 / 3");
+  if (longest > max_n) return fail(OLSR_ERR_ARG, who + ": a segment of " + name + " is longer than its max_n");
+  return OLSR_OK;
+}
+// the checks both entries share; scratch_offsets: emd_scratch_offsets or chamfer_scratch_offsets (the parking places are at
+// the front of the scratch: they depend on B only).  Nothing is written before every check has passed.
+int cloud_segments(const char* who_c, int32_t B, const int32_t* off1, const int32_t* off2, int32_t max_n1, int32_t max_n2,
+                   const float* xyz1, const float* xyz2, bool outputs, bool per_point1, bool per_point2, void* scratch,
+                   int32_t* (*scratch_offsets)(void*, int, long long, long long, int), hipStream_t st, CloudSegments* out) {
+  const std::string who(who_c);
+  if (B < 1 || B > OLSR_CLOUD_MAX_SEGMENTS) return fail(OLSR_ERR_ARG, who + ": B must be between 1 and 32767");
+  if (!off1 || !off2) return fail(OLSR_ERR_ARG, who + ": off1 and off2 are required");
+  if (max_n1 < 0 || max_n2 < 0) return fail(OLSR_ERR_ARG, who + ": max_n1 and max_n2 must be >= 0");
+  if (!outputs) return fail(OLSR_ERR_ARG, who + ": every output is required");
+  if (!scratch) return fail(OLSR_ERR_ARG, who + ": scratch is required");
+  std::vector<int32_t> h[2];
+  bool on_device[2];
+  OLSR_TRY(cloud_offsets(who, "off1", B, off1, max_n1, st, h[0], &on_device[0]));
+  OLSR_TRY(cloud_offsets(who, "off2", B, off2, max_n2, st, h[1], &on_device[1]));
+  out->total1 = h[0][B];
+  out->total2 = h[1][B];
+  if ((out->total1 > 0 && !xyz1) || (out->total2 > 0 && !xyz2)) return fail(OLSR_ERR_ARG, who + ": xyz1 and xyz2 are required");
+  // (per_point: the entry's per-point outputs of that cloud are all there; they may be NULL only for an empty cloud)
+  if ((out->total1 > 0 && !per_point1) || (out->total2 > 0 && !per_point2)) return fail(OLSR_ERR_ARG, who + ": every output is required");
+  const int32_t* given[2] = {off1, off2};
+  const int32_t* dev[2];
+  bool parked = false;
+  for (int w = 0; w < 2; ++w) {
+    dev[w] = given[w];
+    if (on_device[w]) continue;
+    int32_t* park = scratch_offsets(scratch, B, 0, 0, w);
+    HIP_TRY(hipMemcpyAsync(park, h[w].data(), h[w].size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    dev[w] = park;
+    parked = true;
+  }
+  if (parked) HIP_TRY(hipStreamSynchronize(st));   // h goes away
+  out->dev1 = dev[0];
+  out->dev2 = dev[1];
+  return OLSR_OK;
 }
 
 }  // namespace
@@ -420,6 +491,34 @@ int olsr_tsdf_surface_emit(const olsr_tsdf_volume* volume, float min_weight, con
   launch_tsdf_surface_emit(*volume, min_weight, scratch, capacity, points, volume->F > 0 ? feats : nullptr, voxel_index,
                            (hipStream_t)hip_stream);
   return launch_check("tsdf_surface_emit");
+}
+
+size_t olsr_emd_scratch_bytes(int32_t B, int64_t total1, int64_t total2) { return emd_scratch_bytes(B, total1, total2); }
+
+int olsr_emd_cost(int32_t B, const int32_t* off1, const int32_t* off2, int32_t max_n1, int32_t max_n2, const float* xyz1,
+                  const float* xyz2, double* cost, float* residual, int32_t* valid, void* scratch, void* hip_stream) {
+  CloudSegments seg;
+  OLSR_TRY(cloud_segments("emd_cost", B, off1, off2, max_n1, max_n2, xyz1, xyz2, cost && valid, true, true, scratch,
+                          emd_scratch_offsets, (hipStream_t)hip_stream, &seg));
+  launch_emd_cost(B, seg.dev1, seg.dev2, seg.total1, seg.total2, max_n1, max_n2, xyz1, xyz2, cost, residual, valid, scratch,
+                  (hipStream_t)hip_stream);
+  return launch_check("emd_cost");
+}
+
+size_t olsr_chamfer_scratch_bytes(int32_t B, int64_t total1, int64_t total2) {
+  return chamfer_scratch_bytes(B, total1, total2);
+}
+
+int olsr_chamfer(int32_t B, const int32_t* off1, const int32_t* off2, int32_t max_n1, int32_t max_n2, const float* xyz1,
+                 const float* xyz2, float* min_d2_1, int32_t* nn_1, float* min_d2_2, int32_t* nn_2, double* mean,
+                 int32_t* valid, void* scratch, void* hip_stream) {
+  CloudSegments seg;
+  OLSR_TRY(cloud_segments("chamfer", B, off1, off2, max_n1, max_n2, xyz1, xyz2, mean && valid, min_d2_1 && nn_1,
+                          min_d2_2 && nn_2, scratch,
+                          chamfer_scratch_offsets, (hipStream_t)hip_stream, &seg));
+  launch_chamfer(B, seg.dev1, seg.dev2, seg.total1, seg.total2, max_n1, max_n2, xyz1, xyz2, min_d2_1, nn_1, min_d2_2, nn_2,
+                 mean, valid, scratch, (hipStream_t)hip_stream);
+  return launch_check("chamfer");
 }
 
 }  // extern "C"

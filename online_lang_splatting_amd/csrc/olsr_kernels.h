@@ -283,4 +283,18 @@ void launch_tsdf_surface_plan(const olsr_tsdf_volume& vol, float min_weight, voi
 void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, const void* scratch, int capacity, float* points,
                               float* feats, int32_t* voxel_index, hipStream_t st);
 
+// k_cloud_metrics.hip: approximate earth mover's distance and Chamfer distance of ragged batches of point clouds
+// (include/olsr.h).  off1 / off2 are device pointers here; *_scratch_offsets: where in the scratch the entries park offsets
+// that arrived in host memory (which: 0 / 1).
+size_t emd_scratch_bytes(int B, long long total1, long long total2);
+int32_t* emd_scratch_offsets(void* scratch, int B, long long total1, long long total2, int which);
+void launch_emd_cost(int B, const int32_t* off1, const int32_t* off2, long long total1, long long total2, int max_n1,
+                     int max_n2, const float* xyz1, const float* xyz2, double* cost, float* residual, int32_t* valid,
+                     void* scratch, hipStream_t st);
+size_t chamfer_scratch_bytes(int B, long long total1, long long total2);
+int32_t* chamfer_scratch_offsets(void* scratch, int B, long long total1, long long total2, int which);
+void launch_chamfer(int B, const int32_t* off1, const int32_t* off2, long long total1, long long total2, int max_n1, int max_n2,
+                    const float* xyz1, const float* xyz2, float* min_d2_1, int32_t* nn_1, float* min_d2_2, int32_t* nn_2,
+                    double* mean, int32_t* valid, void* scratch, hipStream_t st);
+
 }  // namespace olsr

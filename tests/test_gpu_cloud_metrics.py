@@ -1,0 +1,378 @@
+"""olsr_emd_cost / olsr_chamfer (HIP) and online_lang_splatting_amd.cloud_metrics on the GPU.
+
+Yardsticks: tests/cloud_metrics_ref.py (numpy) and tests/golden/cloud_metrics.npz (Chamfer from the reference's own function).
+
+EMD.  The truth is the float64 restatement.  A float32 implementation is held to
+    |cost - truth| <= max(4 * max over the four float32 variants of |variant - truth|, 16 * 2^-24 * |truth|)
+(two summation orders x two exps; the factor 4 is tests/lang_query_ref.tolerance's: the kernel's order — float32 partials over
+chunks of 256 .. 512 points, added in chunk order — is none of the modelled ones), and the residuals to the same rule on the
+absolute scale max(n, m).  The variants' deviations are computed here and printed with the kernel's, per case.
+Every case prints its ratio |error| / tolerance (run with -s).
+Chamfer.  The per-point squared distances and indices equal the float32 brute force bit for bit (the kernel's expression, no
+contraction, lowest index on ties); the means are held to max(4 |float32 brute force - golden|, 4 * 2^-24 |golden|).
+"""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import pytest
+import torch
+
+import cloud_metrics_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CASES = R.cases()
+NAMES = sorted(CASES)
+ULP = 2.0 ** -24
+
+
+def _M():
+    from online_lang_splatting_amd import cloud_metrics
+    return cloud_metrics
+
+
+def _t(a):
+    return torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+
+
+@functools.lru_cache(maxsize=None)
+def _yardstick(name):
+    return R.emd_yardstick(*CASES[name])
+
+
+@functools.lru_cache(maxsize=None)
+def _golden():
+    g = np.load(os.path.join(ROOT, "tests", "golden", "cloud_metrics.npz"))
+    return {str(n): i for i, n in enumerate(g["names"])}, g
+
+
+def _single(x, y):
+    """One pair through the ragged entry -> (cost float64 undivided, residual float32 [2]) as host arrays."""
+    emd, res = _M().emd_segments(_t(x), [0, len(x)], _t(y), [0, len(y)], return_residual=True)
+    return emd.cpu().numpy()[0] * max(len(x), 1), res.cpu().numpy()[0]
+
+
+def _pack(pairs):
+    xs, ys = [p[0].reshape(-1, 3) for p in pairs], [p[1].reshape(-1, 3) for p in pairs]
+    off1 = np.concatenate([[0], np.cumsum([len(a) for a in xs])])
+    off2 = np.concatenate([[0], np.cumsum([len(a) for a in ys])])
+    return _t(np.concatenate(xs).astype(np.float32)), off1, _t(np.concatenate(ys).astype(np.float32)), off2
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_emd_against_the_truth(name):
+    x, y = CASES[name]
+    truth, dev_c, dev_r = _yardstick(name)
+    cost, res = _single(x, y)
+    tol_c = max(4.0 * dev_c, 16 * ULP * abs(truth["cost"]))
+    tol_r = max(4.0 * dev_r, 16 * ULP * max(len(x), len(y)))
+    err_c = abs(cost - truth["cost"])
+    err_r = max(abs(float(res[0]) - truth["residual"][0]), abs(float(res[1]) - truth["residual"][1]))
+    print(f"\n{name}: truth {truth['cost']:.9g} kernel {cost:.9g}  |err| {err_c:.3e}  variants {dev_c:.3e}  tol {tol_c:.3e}  "
+          f"ratio {err_c / tol_c:.3f};  residual truth {truth['residual'][0]:.6g} {truth['residual'][1]:.6g} kernel {res[0]:.6g} "
+          f"{res[1]:.6g}  |err| {err_r:.3e}  variants {dev_r:.3e}  tol {tol_r:.3e}  ratio {err_r / tol_r:.3f}")
+    assert err_c <= tol_c
+    assert err_r <= tol_r
+
+
+def test_hand_case_of_the_reference():
+    # PyTorchEMD/test_emd_loss.py: two points against two, a batch of three; 0.71 / 2 per item by hand
+    p1, p2 = _t(np.repeat(R.HAND_P1[None], 3, 0)), _t(np.repeat(R.HAND_P2[None], 3, 0))
+    M = _M()
+    d = M.earth_mover_distance(p1, p2, transpose=False)
+    assert d.shape == (3,) and d.dtype == torch.float32
+    assert all(abs(float(v) - R.HAND_EMD) <= 1e-6 for v in d.cpu()), d
+    # (b, 3, n) with the transpose, and the 2-D form
+    assert torch.equal(M.earth_mover_distance(p1.transpose(1, 2).contiguous(), p2.transpose(1, 2).contiguous()), d)
+    assert torch.equal(M.earth_mover_distance(p1[0], p2[0], transpose=False), d[:1])
+
+
+def _torch_emd(x1, x2, dtype, exp):
+    """cloud_metrics_ref.emd_ref in torch on the device (for a size numpy needs minutes for): -> cost, residuals."""
+    a, b = x1.to(dtype)[:, None, :], x2.to(dtype)[None, :, :]
+    dx, dy, dz = b[..., 0] - a[..., 0], b[..., 1] - a[..., 1], b[..., 2] - a[..., 2]
+    d = (dx * dx + dy * dy) + dz * dz
+    n, m = d.shape
+    multiL, multiR = (1, n // m) if n >= m else (m // n, 1)
+    remainL = torch.full((n,), multiL, dtype=dtype, device=d.device)
+    remainR = torch.full((m,), multiR, dtype=dtype, device=d.device)
+    cost = 0.0
+    for level in R.LEVELS:
+        e = torch.exp(level * d) if exp == "libm" else torch.exp2((level * d) * R.LOG2E)
+        ratioL = remainL / (1e-9 + (e * remainR[None, :]).sum(1))
+        sumr = (e * ratioL[:, None]).sum(0) * remainR
+        ratioR = torch.clamp(remainR / (sumr + 1e-9), max=1.0) * remainR
+        remainR = torch.clamp(remainR - sumr, min=0.0)
+        w = e * ratioL[:, None] * ratioR[None, :]
+        cost += float((d * w).sum(1).double().sum())
+        remainL = torch.clamp(remainL - w.sum(1), min=0.0)
+    return cost, float(remainL.double().sum()), float(remainR.double().sum())
+
+
+def test_emd_beyond_sixteen_tiles():
+    """More than 16 LDS tiles per axis: a chunk is then two tiles long, on both axes, with a ragged last chunk (4 100 = 8
+    chunks of 512 + 4; 4 609 = 9 x 512 + 1).  numpy needs a minute for the variants here, so the same statements run in torch
+    on the device, after that restatement is checked against the numpy one; the variants are float32 with two exps (torch's
+    reduction order only), which can only make the bound tighter than the four-variant one."""
+    x, y = CASES["uniform_65_63"]
+    want = R.emd_ref(x, y)
+    got = _torch_emd(_t(x), _t(y), torch.float64, "libm")
+    assert abs(got[0] - want["cost"]) <= 1e-11 * want["cost"] and abs(got[1] - want["residual"][0]) <= 1e-9
+    rng = np.random.default_rng(5)
+    a, b = _t(rng.random((4100, 3), dtype=np.float32)), _t(rng.random((4609, 3), dtype=np.float32) + np.float32(0.05))
+    truth = _torch_emd(a, b, torch.float64, "libm")
+    variants = [_torch_emd(a, b, torch.float32, e) for e in ("libm", "exp2")]
+    dev_c = max(abs(v[0] - truth[0]) for v in variants)
+    dev_r = max(max(abs(v[1] - truth[1]), abs(v[2] - truth[2])) for v in variants)
+    emd, res = _M().emd_segments(a, [0, 4100], b, [0, 4609], return_residual=True)
+    cost, res = float(emd[0]) * 4100, res.cpu().numpy()[0]
+    tol_c, tol_r = max(4 * dev_c, 16 * ULP * abs(truth[0])), max(4 * dev_r, 16 * ULP * 4609)
+    err_c, err_r = abs(cost - truth[0]), max(abs(float(res[0]) - truth[1]), abs(float(res[1]) - truth[2]))
+    print(f"\n4100 x 4609: truth {truth[0]:.9g} kernel {cost:.9g} |err| {err_c:.3e} variants {dev_c:.3e} ratio {err_c / tol_c:.3f}; "
+          f"residual truth {truth[1]:.6g} {truth[2]:.6g} kernel {res[0]:.6g} {res[1]:.6g} ratio {err_r / tol_r:.3f}")
+    assert err_c <= tol_c and err_r <= tol_r
+
+
+BATCH = ["uniform_5_3", "uniform_65_63", None, "uniform_255_257", "gauss_513_1025", None, "wall_2500_2115"]
+
+
+def _batch_pairs():
+    """Seven segments; the third is empty on the left, the sixth on the right."""
+    pairs = [CASES[n] if n else None for n in BATCH]
+    pairs[2] = (np.zeros((0, 3), np.float32), CASES["uniform_64_64"][1])
+    pairs[5] = (CASES["uniform_64_64"][0], np.zeros((0, 3), np.float32))
+    return pairs
+
+
+def _bits(t):
+    return t.cpu().numpy().view(np.uint64 if t.dtype == torch.float64 else np.uint32)
+
+
+def test_batch_equals_single_calls_bit_for_bit():
+    M = _M()
+    pairs = _batch_pairs()
+    xyz1, off1, xyz2, off2 = _pack(pairs)
+    emd, res = M.emd_segments(xyz1, off1, xyz2, off2, return_residual=True)
+    mean, d1, i1, d2, i2 = M.chamfer_segments(xyz1, off1, xyz2, off2)
+    again = M.emd_segments(xyz1, off1, xyz2, off2, return_residual=True)
+    assert np.array_equal(_bits(emd), _bits(again[0])) and np.array_equal(_bits(res), _bits(again[1]))   # determinism
+    for first, second in zip((mean, d1, i1, d2, i2), M.chamfer_segments(xyz1, off1, xyz2, off2)):
+        assert torch.equal(first.view(torch.int64 if first.dtype == torch.float64 else torch.int32),
+                           second.view(torch.int64 if second.dtype == torch.float64 else torch.int32))
+    for b, (x, y) in enumerate(pairs):
+        if len(x) == 0 or len(y) == 0:
+            assert bool(torch.isnan(emd[b])) and bool(torch.isnan(res[b]).all()) and bool(torch.isnan(mean[b]).all())
+            assert bool(torch.isnan(d1[off1[b]:off1[b + 1]]).all()) and bool((i1[off1[b]:off1[b + 1]] == -1).all())
+            assert bool(torch.isnan(d2[off2[b]:off2[b + 1]]).all()) and bool((i2[off2[b]:off2[b + 1]] == -1).all())
+            continue
+        e1, r1 = M.emd_segments(_t(x), [0, len(x)], _t(y), [0, len(y)], return_residual=True)
+        assert np.array_equal(_bits(emd[b:b + 1]), _bits(e1)) and np.array_equal(_bits(res[b:b + 1]), _bits(r1)), BATCH[b]
+        m1, a1, j1, a2, j2 = M.chamfer_segments(_t(x), [0, len(x)], _t(y), [0, len(y)])
+        assert np.array_equal(_bits(mean[b:b + 1]), _bits(m1)), BATCH[b]
+        assert np.array_equal(_bits(d1[off1[b]:off1[b + 1]]), _bits(a1)) and torch.equal(i1[off1[b]:off1[b + 1]], j1)
+        assert np.array_equal(_bits(d2[off2[b]:off2[b + 1]]), _bits(a2)) and torch.equal(i2[off2[b]:off2[b + 1]], j2)
+
+
+def _uneven_pairs():
+    """Segments whose chunk counts do NOT grow with their sizes: 4 500 and 4 400 points make 9 chunks of two tiles, 4 000
+    make 16 chunks of one, 3 000 make 12, 4 096 make 16, 300 make 2, 5 000 make 10 — the longest segment of the batch has fewer
+    chunks than shorter ones, on both axes."""
+    rng = np.random.default_rng(23)
+    sizes = [(4500, 4400), (4000, 3000), (3000, 4096), (300, 5000)]
+    return [(rng.random((n, 3), dtype=np.float32), rng.random((m, 3), dtype=np.float32) + np.float32(0.03)) for n, m in sizes]
+
+
+def test_batch_whose_longest_segment_has_fewer_chunks_than_a_shorter_one():
+    M = _M()
+    pairs = _uneven_pairs()
+    xyz1, off1, xyz2, off2 = _pack(pairs)
+    emd, res = M.emd_segments(xyz1, off1, xyz2, off2, return_residual=True)
+    mean, d1, i1, d2, i2 = M.chamfer_segments(xyz1, off1, xyz2, off2)
+    for b, (x, y) in enumerate(pairs):
+        e1, r1 = M.emd_segments(_t(x), [0, len(x)], _t(y), [0, len(y)], return_residual=True)
+        assert np.array_equal(_bits(emd[b:b + 1]), _bits(e1)) and np.array_equal(_bits(res[b:b + 1]), _bits(r1)), b
+        m1, a1, j1, a2, j2 = M.chamfer_segments(_t(x), [0, len(x)], _t(y), [0, len(y)])
+        assert np.array_equal(_bits(mean[b:b + 1]), _bits(m1)), b
+        assert np.array_equal(_bits(d1[off1[b]:off1[b + 1]]), _bits(a1)) and torch.equal(i1[off1[b]:off1[b + 1]], j1), b
+        assert np.array_equal(_bits(d2[off2[b]:off2[b + 1]]), _bits(a2)) and torch.equal(i2[off2[b]:off2[b + 1]], j2), b
+    # and the batch's Chamfer points are the brute force's, segment by segment
+    for b, (x, y) in enumerate(pairs):
+        want = R.chamfer_ref(x, y, np.float32)
+        assert np.array_equal(d1[off1[b]:off1[b + 1]].cpu().numpy().view(np.uint32), want["min_d2_x"].view(np.uint32)), b
+        assert np.array_equal(d2[off2[b]:off2[b + 1]].cpu().numpy().view(np.uint32), want["min_d2_y"].view(np.uint32)), b
+        assert np.array_equal(i1[off1[b]:off1[b + 1]].cpu().numpy(), want["nn_x"]), b
+        assert np.array_equal(i2[off2[b]:off2[b + 1]].cpu().numpy(), want["nn_y"]), b
+
+
+def test_a_max_n_beyond_the_segment_changes_no_bit():
+    """The header asks for max_n "at least the longest segment": a 4 000 x 3 000 pair (16 and 12 chunks) with max_n = 4 500
+    (9 chunks by its own size) and other values gives the bits of the exact max_n, for both entries."""
+    from online_lang_splatting_amd._lib import check, lib
+    L = lib()
+    x, y = _uneven_pairs()[1]
+    n, m = len(x), len(y)
+    xd, yd = _t(x), _t(y)
+    h1, h2 = np.array([0, n], np.int32), np.array([0, m], np.int32)
+    stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+    es = torch.empty(L.olsr_emd_scratch_bytes(1, n, m), dtype=torch.uint8, device=DEV)
+    cs = torch.empty(L.olsr_chamfer_scratch_bytes(1, n, m), dtype=torch.uint8, device=DEV)
+    got = []
+    for max1, max2 in ((n, m), (4500, 4500), (4500, m), (n, 8200), (100000, 4100)):
+        cost = torch.empty(1, dtype=torch.float64, device=DEV)
+        res = torch.empty((1, 2), dtype=torch.float32, device=DEV)
+        valid = torch.empty(1, dtype=torch.int32, device=DEV)
+        check(L.olsr_emd_cost(1, h1.ctypes.data, h2.ctypes.data, max1, max2, xd.data_ptr(), yd.data_ptr(), cost.data_ptr(),
+                              res.data_ptr(), valid.data_ptr(), es.data_ptr(), stream))
+        mean = torch.empty((1, 2), dtype=torch.float64, device=DEV)
+        dx, dy = torch.empty(n, dtype=torch.float32, device=DEV), torch.empty(m, dtype=torch.float32, device=DEV)
+        ix, iy = torch.empty(n, dtype=torch.int32, device=DEV), torch.empty(m, dtype=torch.int32, device=DEV)
+        check(L.olsr_chamfer(1, h1.ctypes.data, h2.ctypes.data, max1, max2, xd.data_ptr(), yd.data_ptr(), dx.data_ptr(),
+                             ix.data_ptr(), dy.data_ptr(), iy.data_ptr(), mean.data_ptr(), valid.data_ptr(), cs.data_ptr(), stream))
+        got.append([_bits(cost), _bits(res), _bits(mean), _bits(dx), ix.cpu().numpy(), _bits(dy), iy.cpu().numpy()])
+    for other in got[1:]:
+        assert all(np.array_equal(a, b) for a, b in zip(got[0], other))
+    want = R.chamfer_ref(x, y, np.float32)
+    assert np.array_equal(got[0][3], want["min_d2_x"].view(np.uint32)) and np.array_equal(got[0][4], want["nn_x"])
+
+
+def test_valid_flags_and_device_offsets_through_the_c_abi():
+    """The entries themselves: valid = 0 exactly for the empty segments, and offset tables in device memory (read back and
+    checked by the entry) give the bits of tables in host memory (uploaded by the entry)."""
+    from online_lang_splatting_amd._lib import check, lib
+    L = lib()
+    xyz1, off1, xyz2, off2 = _pack(_batch_pairs())
+    B = len(off1) - 1
+    h1, h2 = off1.astype(np.int32), off2.astype(np.int32)
+    d1, d2 = _t(h1), _t(h2)
+    scratch = torch.empty(L.olsr_emd_scratch_bytes(B, int(h1[-1]), int(h2[-1])), dtype=torch.uint8, device=DEV)
+    max1, max2 = int(np.diff(h1).max()), int(np.diff(h2).max())
+    out = []
+    for o1, o2 in ((h1.ctypes.data, h2.ctypes.data), (d1.data_ptr(), d2.data_ptr()), (h1.ctypes.data, d2.data_ptr())):
+        cost = torch.empty(B, dtype=torch.float64, device=DEV)
+        valid = torch.empty(B, dtype=torch.int32, device=DEV)
+        stream = C.c_void_p(torch.cuda.current_stream().cuda_stream)
+        check(L.olsr_emd_cost(B, o1, o2, max1, max2, xyz1.data_ptr(), xyz2.data_ptr(), cost.data_ptr(), None, valid.data_ptr(),
+                              scratch.data_ptr(), stream))   # (residual may be NULL)
+        out.append((cost, valid))
+    assert out[0][1].tolist() == [1, 1, 0, 1, 1, 0, 1]
+    for cost, valid in out[1:]:
+        assert np.array_equal(_bits(cost), _bits(out[0][0])) and torch.equal(valid, out[0][1])
+    # a decreasing table in device memory is refused on the host as well
+    bad = _t(np.array([0, 5, 4, 9, 9, 9, 9, 9], np.int32))
+    rc = L.olsr_emd_cost(B, bad.data_ptr(), d2.data_ptr(), 4000, 4000, xyz1.data_ptr(), xyz2.data_ptr(), out[0][0].data_ptr(), None,
+                         out[0][1].data_ptr(), scratch.data_ptr(), None)
+    assert rc == -1 and L.olsr_last_error().decode() == "emd_cost: off1 must be non-decreasing"
+
+
+def test_a_nan_touches_its_own_segment_only():
+    M = _M()
+    pairs = _batch_pairs()
+    xyz1, off1, xyz2, off2 = _pack(pairs)
+    emd, res = M.emd_segments(xyz1, off1, xyz2, off2, return_residual=True)
+    mean = M.chamfer_segments(xyz1, off1, xyz2, off2)[0]
+    poisoned = xyz1.clone()
+    poisoned[int(off1[3]) + 100, 1] = float("nan")   # inside segment 3
+    emd_n, res_n = M.emd_segments(poisoned, off1, xyz2, off2, return_residual=True)
+    mean_n = M.chamfer_segments(poisoned, off1, xyz2, off2)[0]
+    keep = [b for b in range(len(pairs)) if b != 3]
+    assert np.array_equal(_bits(emd[keep]), _bits(emd_n[keep])) and np.array_equal(_bits(res[keep]), _bits(res_n[keep]))
+    assert np.array_equal(_bits(mean[keep]), _bits(mean_n[keep]))
+
+
+def _duplicated():
+    """Clouds with repeated points on both sides, so that ties decide the index: every point of y appears three times, x holds
+    copies of y's points too (distance exactly 0 to three candidates)."""
+    rng = np.random.default_rng(11)
+    base = rng.random((100, 3), dtype=np.float32)
+    y = np.concatenate([base, base[::-1], base])
+    x = np.concatenate([rng.random((300, 3), dtype=np.float32), base[10:60], base[10:60]])
+    return x, y
+
+
+def _chamfer_cases():
+    rng = np.random.default_rng(3)
+    out = {n: CASES[n] for n in NAMES}
+    out["duplicated"] = _duplicated()
+    # more than 16 tiles on the streamed axis: two-tile chunks with a ragged end, in both directions
+    out["uniform_4100_4609"] = (rng.random((4100, 3), dtype=np.float32), rng.random((4609, 3), dtype=np.float32))
+    return out
+
+
+@pytest.mark.parametrize("name", sorted(_chamfer_cases()))
+def test_chamfer_points_equal_the_float32_brute_force(name):
+    x, y = _chamfer_cases()[name]
+    want = R.chamfer_ref(x, y, np.float32)
+    mean, dx, ix, dy, iy = _M().chamfer_segments(_t(x), [0, len(x)], _t(y), [0, len(y)])
+    assert np.array_equal(dx.cpu().numpy().view(np.uint32), want["min_d2_x"].view(np.uint32))
+    assert np.array_equal(dy.cpu().numpy().view(np.uint32), want["min_d2_y"].view(np.uint32))
+    assert np.array_equal(ix.cpu().numpy(), want["nn_x"]) and np.array_equal(iy.cpu().numpy(), want["nn_y"])
+    # the means: the same doubles summed in two orders.  The kernel adds ceil(n / 256) terms per thread and then 8 tree levels,
+    # numpy's pairwise sum at most 128 terms and then its tree: relative bounds (n / 256 + 8) and under 24 units of 2^-53
+    got = mean.cpu().numpy()[0]
+    for k, (key, n) in enumerate((("x_to_y", len(x)), ("y_to_x", len(y)))):
+        assert abs(got[k] - want[key]) <= (n / 256 + 32) * 2.0 ** -53 * want[key], (key, got[k], want[key])
+
+
+@pytest.mark.parametrize("name", NAMES)
+def test_chamfer_against_the_reference(name):
+    index, g = _golden()
+    x, y = CASES[name]
+    golden = g["chamfer"][index[name]]
+    ref32 = R.chamfer_ref(x, y, np.float32)
+    M = _M()
+    for k, direction in enumerate(("x_to_y", "y_to_x", "bi")):
+        got = float(M.chamfer_distance(_t(x), _t(y), direction=direction))
+        tol = max(4 * abs(ref32[direction] - golden[k]), 4 * ULP * abs(golden[k]))
+        print(f"\n{name} {direction}: golden {golden[k]:.9g} kernel {got:.9g} |err| {abs(got - golden[k]):.2e} tol {tol:.2e}")
+        assert abs(got - golden[k]) <= tol
+
+
+def test_evaluate_classes():
+    M = _M()
+    rng = np.random.default_rng(17)
+    # five classes; class 3 is absent from the prediction, class 4 from the ground truth
+    points = rng.random((6000, 3), dtype=np.float32)
+    labels = rng.choice([0, 1, 2, 4], size=6000, p=[0.4, 0.3, 0.2, 0.1])
+    gt_points = (rng.random((5000, 3), dtype=np.float32) * np.float32(1.1)).astype(np.float32)
+    gt_labels = rng.choice([10, 11, 12, 13], size=5000)   # the ground truth's own ids
+    pairs = [(0, 10), (1, 11), (2, 12), (3, 13), (4, 14)]
+    per, avg = M.evaluate_classes(_t(points), _t(labels), _t(gt_points), _t(gt_labels), pairs, stride=8)
+    assert len(per) == 5 and per[3] is None and per[4] is None and avg["evaluated"] == 3
+    cds, emds = [], []
+    for (p, g), r in zip(pairs[:3], per[:3]):
+        a, b = points[labels == p][::8], gt_points[gt_labels == g][::8]
+        assert (r["n_pred"], r["n_gt"]) == (len(a), len(b))
+        cd = float(M.chamfer_distance(_t(a), _t(b)))
+        emd, res = M.emd_segments(_t(a), [0, len(a)], _t(b), [0, len(b)], return_residual=True)
+        assert r["cd"] == cd and r["emd"] == float(emd[0])
+        assert r["emd_residual"] == (float(res[0, 0]), float(res[0, 1]))
+        cds.append(cd)
+        emds.append(float(emd[0]))
+    assert avg["cd"] == sum(cds) / 3 and avg["emd"] == sum(emds) / 3
+    # nothing to evaluate: no averages
+    per, avg = M.evaluate_classes(_t(points), _t(labels), _t(gt_points), _t(gt_labels), [(3, 10)])
+    assert per == [None] and avg == dict(cd=None, emd=None, evaluated=0)
+
+
+def test_end_to_end_on_the_tsdf_surface():
+    """The surface points of the wall scene of tests/golden/tsdf.npz against themselves: Chamfer is exactly 0, and the EMD per
+    point is the approximate matching's leakage, no more than the truth's own value plus the tolerance for that cloud."""
+    from online_lang_splatting_amd.tsdf import TSDFVolume
+    g = np.load(os.path.join(ROOT, "tests", "golden", "tsdf.npz"))
+    vol = TSDFVolume(g["vol_bnds"], float(g["voxel_size"]), feature_dim="rgb", device=DEV)
+    for k in range(len(g["depths"])):
+        vol.integrate(g["colours"][k].astype(np.float32), g["depths"][k], g["cam_intr"], g["cam_poses"][k], float(g["obs_weights"][k]))
+    points = vol.surface_points()[0]
+    n = points.shape[0]
+    assert 200 <= n <= 5000, n
+    M = _M()
+    assert float(M.chamfer_distance(points, points.clone())) == 0.0
+    got = float(M.earth_mover_distance(points, points.clone(), transpose=False)[0])
+    host = points.cpu().numpy()
+    truth, dev_c, _ = R.emd_yardstick(host, host)
+    tol = max(4.0 * dev_c, 16 * ULP * abs(truth["cost"])) / n
+    print(f"\n{n} surface points: emd {got:.6e} truth {truth['emd']:.6e} tol {tol:.3e}")
+    assert 0.0 <= got <= truth["emd"] + tol
