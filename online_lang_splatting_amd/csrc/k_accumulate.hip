@@ -194,11 +194,8 @@ __global__ __launch_bounds__(256) void exchange_pack_kernel(int P, int width, in
     total += c;
     before += (i < b) ? c : 0;
   }
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    before += __shfl_xor(before, o);
-    total += __shfl_xor(total, o);
-  }
+  before = wave_sum(before);
+  total = wave_sum(total);
   if (lane == 0) {
     s_red[0][w] = before;
     s_red[1][w] = total;
@@ -282,15 +279,9 @@ void launch_exchange_mask(int P, int width, const float* flat, const unsigned lo
 // a count without a pack (idx == NULL): status = {rows in the union, whether they exceed cap}
 __global__ __launch_bounds__(256) void exchange_total_kernel(int nb, int cap, const int32_t* __restrict__ counts,
                                                              int32_t* __restrict__ status) {
-  __shared__ int s_t[4];
-  int total = 0;
-  for (int i = threadIdx.x; i < nb; i += 256) total += counts[i];
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) total += __shfl_xor(total, o);
-  if ((threadIdx.x & 63) == 0) s_t[threadIdx.x >> 6] = total;
-  __syncthreads();
+  __shared__ int32_t s_t[4];
+  const int32_t total = single_block_sum<4>(nb, counts, s_t);
   if (threadIdx.x == 0) {
-    total = s_t[0] + s_t[1] + s_t[2] + s_t[3];
     status[0] = total;
     status[1] = total > cap ? 1 : 0;
   }

@@ -20,47 +20,6 @@ namespace olsr {
 constexpr int SCAN_THREADS = 256;
 constexpr int SCAN_ITEMS = SCAN_CHUNK / SCAN_THREADS;  // 16
 
-__device__ __forceinline__ u32 wave_incl_scan(u32 v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    u32 o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-
-// exclusive prefix of `v` across a 256-thread block; *total receives the block sum
-__device__ __forceinline__ u32 block_excl_scan_256(u32 v, u32* total) {
-  __shared__ u32 wave_sums[4];
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  const u32 incl = wave_incl_scan(v);
-  if (lane == 63) wave_sums[w] = incl;
-  __syncthreads();
-  u32 base = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    if (i < w) base += wave_sums[i];
-  if (total) *total = wave_sums[0] + wave_sums[1] + wave_sums[2] + wave_sums[3];
-  __syncthreads();
-  return base + incl - v;
-}
-
-// Sum of partials[0 .. b) computed by the whole block (the per-chunk totals are few: one per 4096
-// elements), which saves the separate single-block scan launch between reduce and apply.
-__device__ __forceinline__ u32 block_prefix_of_partials(const u32* __restrict__ partials, int b) {
-  __shared__ u32 red[4];
-  u32 s = 0;
-  for (int j = threadIdx.x; j < b; j += SCAN_THREADS) s += partials[j];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  const u32 tot = red[0] + red[1] + red[2] + red[3];
-  __syncthreads();
-  return tot;
-}
-
 struct LoadPlain {
   const u32* p;
   __device__ __forceinline__ u32 operator()(int64_t i) const { return p[i]; }
@@ -79,11 +38,14 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_reduce_kernel(Load ld, int6
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k)
     if (base + k < n) s += ld(base + k);
+  __shared__ u32 s_w[SCAN_THREADS / 64];
   u32 total;
-  block_excl_scan_256(s, &total);
+  block_excl_scan<SCAN_THREADS / 64>(s, s_w, &total);
   if (threadIdx.x == 0) partials[blockIdx.x] = total;
 }
 
+// (the sum of the earlier blocks' partials is computed by the whole block — the per-chunk totals are few: one per 4096
+//  elements — which saves the separate single-block scan launch between reduce and apply)
 template <class Load, bool INCLUSIVE>
 __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(Load ld, int64_t n, const u32* partials, u32* out) {
   const int64_t base = (int64_t)blockIdx.x * SCAN_CHUNK + (int64_t)threadIdx.x * SCAN_ITEMS;
@@ -94,7 +56,10 @@ __global__ __launch_bounds__(SCAN_THREADS) void scan_apply_kernel(Load ld, int64
     v[k] = (base + k < n) ? ld(base + k) : 0;
     s += v[k];
   }
-  u32 run = block_excl_scan_256(s, nullptr) + block_prefix_of_partials(partials, blockIdx.x);
+  __shared__ u32 s_w[SCAN_THREADS / 64];
+  u32 run = block_excl_scan<SCAN_THREADS / 64>(s, s_w);
+  __syncthreads();  // (s_w is reused)
+  run += single_block_sum<SCAN_THREADS / 64>((int)blockIdx.x, partials, s_w);
 #pragma unroll
   for (int k = 0; k < SCAN_ITEMS; ++k) {
     if (INCLUSIVE) run += v[k];
@@ -119,14 +84,6 @@ constexpr int SORT_ROUNDS = SORT_CHUNK / SORT_THREADS;  // 16 rounds of 64 per w
 // The self-scanning scatter reads the whole [block][digit] table in every block (nblk^2 * NB loads in total): it
 // wins while that table is small — measured: 123 blocks x 256 digits -24 us per sort, 489 x 256 +17 us.
 constexpr int SELF_SCAN_MAX_TABLE = 40960;              // blocks * digits
-
-__device__ __forceinline__ int64_t bounded_n(int64_t n_host, const int32_t* n_dev) {
-  if (n_dev) {
-    const int64_t nd = (int64_t)(*n_dev);
-    return nd < n_host ? nd : n_host;
-  }
-  return n_host;
-}
 
 // number of keys of block b whose digit is d: table[d * nblk + b] (the layout the device-wide scan walks), or,
 // transposed, table[b * (dmask + 1) + d] (the layout the self-scanning scatter reads coalesced)
@@ -172,6 +129,7 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
   __shared__ u32 ex_key[SORT_CHUNK];
   __shared__ u32 ex_val[SORT_CHUNK];
   __shared__ u32 s_part[2][SORT_THREADS];  // SELF_SCAN partial column sums
+  __shared__ u32 s_w[SORT_THREADS / 64];   // the block scans' wave sums
   const int64_t n = bounded_n(n_host, n_dev);
   const int lane = lane_id(), w = threadIdx.x >> 6;
   const int64_t bbase = (int64_t)blockIdx.x * SORT_CHUNK;
@@ -193,7 +151,8 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
     u32 c0 = 0, c1 = 0, c2 = 0, c3 = 0;
     if (d < NB) { c0 = cnt[0][d]; c1 = cnt[1][d]; c2 = cnt[2][d]; c3 = cnt[3][d]; }
     const u32 tot = c0 + c1 + c2 + c3;
-    const u32 start = block_excl_scan_256(tot, nullptr);
+    const u32 start = block_excl_scan<SORT_THREADS / 64>(tot, s_w);
+    __syncthreads();  // (s_w is reused by the second scan)
     u32 gb = 0;
     if constexpr (SELF_SCAN) {
       constexpr u32 PARTS = SORT_THREADS / NB;  // threads per digit
@@ -220,7 +179,8 @@ __global__ __launch_bounds__(SORT_THREADS) void radix_scatter_kernel(
           }
         }
       }
-      gb = block_excl_scan_256(row_total, nullptr) + row_before;
+      gb = block_excl_scan<SORT_THREADS / 64>(row_total, s_w) + row_before;
+      __syncthreads();  // (s_w is free again)
     } else {
       if (d < NB) gb = table[(size_t)d * gridDim.x + blockIdx.x];
     }
@@ -355,8 +315,7 @@ __device__ __forceinline__ u32 lb_block_exclusive(u32* status, u32 b, u32 total,
   if (first + tid < b) v = lb_wait(&status[2 * (first + tid)], spin_limit, sync_error);
   if (tid == THREADS - 1 && first > 0)  // (first + tid >= b for this thread)
     v += lb_wait(&status[2 * (first - 1) + 1], spin_limit, sync_error);
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+  v = wave_sum(v);
   if ((tid & 63) == 0) s_red[tid >> 6] = v;
   __syncthreads();
   u32 excl = 0;
@@ -399,31 +358,6 @@ constexpr int EO_T = 256;
 constexpr int EO_PER = EMIT_CHUNK / EO_T;  // 4
 static_assert(EO_PER == 4, "one 16-byte load of the depth order per thread");
 
-// base slot of this thread's `cnt` list entries: one aggregated atomic per block (the list order influences no result)
-__device__ __forceinline__ u32 block_list_base(u32 cnt, int32_t* counter, u32* s_cnt /* [EO_T / 64] */, u32* s_base) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  u32 incl = cnt;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  __syncthreads();  // (scratch may still be read from the previous use)
-  if (lane == 63) s_cnt[w] = incl;
-  __syncthreads();
-  if (threadIdx.x == 0) {
-    u32 tot = 0;
-    for (int i = 0; i < EO_T / 64; ++i) {
-      const u32 c = s_cnt[i];
-      s_cnt[i] = tot;
-      tot += c;
-    }
-    *s_base = tot ? (u32)atomicAdd(counter, (int)tot) : 0u;
-  }
-  __syncthreads();
-  return *s_base + s_cnt[w] + incl - cnt;
-}
-
 __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
     int P, const u32* __restrict__ order, const u32* __restrict__ inst_count, int32_t* __restrict__ counters,
     const u64* __restrict__ block_totals_sort, uint4* __restrict__ bin_sync, int bin_sync_quads,
@@ -446,7 +380,6 @@ __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
   if (counters[CNT_OVERFLOW] != 0) return;  // more instances than the caller's capacity: nothing is emitted (uniform)
   if (counters[CNT_SYNC_ERROR] != 0) return;  // the depth sort lost a predecessor's counts: its order is garbage, index nothing with it
   const u32 b = blockIdx.x;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int r0 = (int)(b * EMIT_CHUNK + threadIdx.x * EO_PER);  // this thread's four consecutive depth ranks
   // (P_true sizes the Gaussian-indexed arrays; the ORDER holds n_order entries — all P, or only the Gaussians that emit when
   //  the depth sort compacted its input, k_sort.hip.  Blocks beyond them have nothing to do: uniform.)
@@ -469,30 +402,18 @@ __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
     n[k] = (r0 + k < P) ? inst_count[g[k]] : 0u;  // 0 when culled
     mine += emit_total_pack(n[k]);
   }
-  u64 incl = mine;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u64 o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  if (lane == 63) s_wsum[w] = incl;
+  // (the cross-wave step is written out, not block_excl_scan<.., u64>: that instantiation costs this kernel 4 VGPRs)
+  const int w = (int)(threadIdx.x >> 6);
+  const u64 incl = wave_incl_scan(mine);
+  if ((threadIdx.x & 63) == 63) s_wsum[w] = incl;
   __syncthreads();
   u64 wbase = 0;
 #pragma unroll
   for (int i = 0; i < EO_T / 64; ++i) wbase += (i < w) ? s_wsum[i] : 0ull;
-  __syncthreads();
+  __syncthreads();  // (s_wsum is reused)
   // first instance (and first emitting rank) of this block = the totals of all earlier blocks (left behind by the depth
   // sort's last pass, or by the repair of a carried order)
-  u64 pre = 0;
-  for (u32 j = threadIdx.x; j < b; j += EO_T) pre += block_totals[j];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) pre += __shfl_xor(pre, m);
-  if (lane == 0) s_wsum[w] = pre;
-  __syncthreads();
-  u64 base = 0;
-#pragma unroll
-  for (int i = 0; i < EO_T / 64; ++i) base += s_wsum[i];
-  const u64 first = base + wbase + incl - mine;
+  const u64 first = single_block_sum<EO_T / 64>((int)b, block_totals, s_wsum) + wbase + incl - mine;
   constexpr u64 LOW = (1ull << EMIT_TOTAL_SHIFT) - 1ull;
   u32 off[EO_PER];
   u32 run = (u32)(first & LOW);
@@ -524,37 +445,14 @@ __global__ __launch_bounds__(EO_T) void emit_offsets_kernel(
   // (the thread that holds the last rank has seen every rank: the number of emitting Gaussians)
   if ((r0 <= P - 1 && P - 1 < r0 + EO_PER) || (P == 0 && b == 0 && threadIdx.x == 0)) counters[CNT_EMITTERS] = (int32_t)ci;
   // the two work lists of the backward's row sums: big footprints from the front, medium ones from the back
-  u32 slot = block_list_base(nbig, &counters[CNT_BIG_LIST], s_lsum, &s_lbase);
+  u32 slot = block_list_base<EO_T / 64>(nbig, &counters[CNT_BIG_LIST], s_lsum, &s_lbase);
 #pragma unroll
   for (int k = 0; k < EO_PER; ++k)
     if (n[k] > EMIT_BIG) big_list[slot++] = make_uint4(g[k], off[k], n[k], 0u);
-  u32 mslot = block_list_base(nmid, &counters[CNT_MID_LIST], s_lsum, &s_lbase);
+  u32 mslot = block_list_base<EO_T / 64>(nmid, &counters[CNT_MID_LIST], s_lsum, &s_lbase);
 #pragma unroll
   for (int k = 0; k < EO_PER; ++k)
     if (n[k] > OLSR_MID_FOOTPRINT && n[k] <= EMIT_BIG) big_list[(u32)P_true - 1u - (mslot++)] = make_uint4(g[k], off[k], n[k], 0u);
-}
-
-// exclusive scan of v over the EB_T threads of the block; *total = the sum (two barriers; s_w: [EB_T / 64])
-__device__ __forceinline__ u32 eb_scan(u32 v, u32* s_w, u32* total) {
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-  u32 incl = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
-  __syncthreads();  // (s_w may still be read from the previous use)
-  if (lane == 63) s_w[w] = incl;
-  __syncthreads();
-  u32 wb = 0, tot = 0;
-#pragma unroll
-  for (int i = 0; i < EB_T / 64; ++i) {
-    const u32 c = s_w[i];
-    wb += (i < w) ? c : 0u;
-    tot += c;
-  }
-  *total = tot;
-  return wb + incl - v;
 }
 
 // what a row's thread needs about its Gaussian: the ellipse of cull_setup, the rect's columns, where the rows start
@@ -624,7 +522,8 @@ __global__ __launch_bounds__(EB_T) void emit_balanced_kernel(
     u32 off_n, end_n, g_n;
     load_rank(r + EB_T, off_n, end_n, g_n);
     u32 total_rows;
-    const u32 rowoff = eb_scan(nrows, s_w, &total_rows);
+    __syncthreads();  // (s_w itself is free here — every batch ends with a barrier; left where the scan used to begin with one)
+    const u32 rowoff = block_excl_scan<EB_T / 64>(nrows, s_w, &total_rows);
     s_rowoff[tid] = rowoff;
     __syncthreads();
     const bool more = s_flag != 0u;
@@ -662,7 +561,8 @@ __global__ __launch_bounds__(EB_T) void emit_balanced_kernel(
           key0 = (u32)(y * gx + xa);
         }
         u32 chunk_total;
-        const u32 S = carry + eb_scan(cnt, s_w, &chunk_total);
+        __syncthreads();  // (s_w may still be read from the previous scan)
+        const u32 S = carry + block_excl_scan<EB_T / 64>(cnt, s_w, &chunk_total);
         carry += chunk_total;
         // a row's first instance = its Gaussian's first instance + the instances of the Gaussian's earlier rows
         if (live && idx == s_rowoff[owner]) s_first[owner] = S;
@@ -711,8 +611,7 @@ __global__ __launch_bounds__(EMIT_THREADS) void emit_totals_kernel(int P, const 
   __shared__ u64 s_w[EMIT_THREADS / 64];
   const int r = (int)(blockIdx.x * EMIT_THREADS + threadIdx.x);
   u64 n = (r < P) ? emit_total_pack(inst_count[order[r]]) : 0ull;
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) n += __shfl_xor(n, m);
+  n = wave_sum(n);
   if ((threadIdx.x & 63) == 0) s_w[threadIdx.x >> 6] = n;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -767,7 +666,7 @@ void launch_emit(const olsr_scene& s, const FrameDims& d, const GeometryState& g
 // Exclusive scan of popcount(flags[u]) — how many slot rows each instance owns — in ONE kernel: a 1024-thread block
 // covers 16384 instances (a thread fetches its 16 flag bytes with one 16-byte load: the flag array is 256-byte aligned
 // and padded to a multiple of 16), publishes its total and gets the sum of the earlier blocks by decoupled look-back
-// (lb_exclusive_prefix above).  The status words and the ticket are zeroed by the forward's emission; because a
+// (lb_block_exclusive above).  The status words and the ticket are zeroed by the forward's emission; because a
 // backward may be repeated on the same forward, the last block to finish zeroes them again for the next launch.
 // rows per instance = popcount((flag >> shift) & mask): shift 0 / mask 15 = one row per forward slot,
 // shift 4 / mask 3 = one row per packed survivor wave (reference mode, 15x15 tiles)
@@ -828,7 +727,6 @@ __device__ __forceinline__ void row_compaction_block(const RowCompactionArgs& ra
   if (threadIdx.x == 0) s_bid = atomicAdd(&sync[0], 1u);
   __syncthreads();
   const u32 b = s_bid;
-  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
   const int64_t n = bounded_n(n_host, n_dev);  // flags beyond the instances of this frame are stale
   const int64_t bbase = (int64_t)b * ROWS_CHUNK;
   // (a ticket beyond the grid: the ticket word was not the zero the emission left — corrupted from outside)
@@ -840,24 +738,11 @@ __device__ __forceinline__ void row_compaction_block(const RowCompactionArgs& ra
     u32 sum = 0;
 #pragma unroll
     for (int k = 0; k < 16; ++k) sum += v[k];
-    u32 incl = sum;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const u32 o = __shfl_up(incl, d);
-      if (lane >= d) incl += o;
-    }
-    if (lane == 63) s_wsum[w] = incl;
-    __syncthreads();
-    u32 wbase = 0, total = 0;
-#pragma unroll
-    for (int i = 0; i < ROWS_THREADS / 64; ++i) {
-      const u32 c = s_wsum[i];
-      wbase += (i < w) ? c : 0u;
-      total += c;
-    }
-    __syncthreads();
+    u32 total;
+    const u32 excl = block_excl_scan<ROWS_THREADS / 64>(sum, s_wsum, &total);
+    __syncthreads();  // (s_wsum is reused by the look-back)
     const u32 pre = lb_block_exclusive<ROWS_THREADS>(status, b, total, s_wsum, spin_limit, &counters[CNT_SYNC_ERROR]);
-    u32 run = pre + wbase + incl - sum;
+    u32 run = pre + excl;
     // (static indices only: a dynamically indexed private array would be promoted to 64 KB of LDS)
     u32 L = 0;
     const int at_n = (base <= n && n < base + 16) ? (int)(n - base) : -1;
@@ -970,11 +855,8 @@ __device__ __forceinline__ void sum_and_post_live_rows(u32 a, u32 b, u32 nblocks
   __shared__ u32 s_sum[2];
   if (threadIdx.x == 0) s_sum[0] = s_sum[1] = 0;
   __syncthreads();
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    a += __shfl_xor(a, m);
-    b += __shfl_xor(b, m);
-  }
+  a = wave_sum(a);
+  b = wave_sum(b);
   if ((threadIdx.x & 63) == 0) {
     if (a) atomicAdd(&s_sum[0], a);
     if (b) atomicAdd(&s_sum[1], b);

@@ -30,6 +30,18 @@ struct Aabb {
   float lo[3], hi[3];
 };
 
+// every lane: the minima of lo[3] and the maxima of hi[3] over the wave (xor butterfly, steps 32 .. 1)
+__device__ __forceinline__ void wave_minmax3(float (&lo)[3], float (&hi)[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+      lo[a] = fminf(lo[a], __shfl_xor(lo[a], m));
+      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m));
+    }
+  }
+}
+
 // ---------------------------------------------------------------- bounding box (two kernels)
 __global__ __launch_bounds__(256) void knn_bbox_partial_kernel(int P, const float* __restrict__ pts,
                                                                float* __restrict__ partials) {
@@ -43,14 +55,7 @@ __global__ __launch_bounds__(256) void knn_bbox_partial_kernel(int P, const floa
     }
   }
   __shared__ float red[4][6];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], m));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m));
-    }
-  }
+  wave_minmax3(lo, hi);
   if ((threadIdx.x & 63) == 0) {
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
@@ -122,12 +127,8 @@ __global__ __launch_bounds__(256) void knn_gather_kernel(int P, const float* __r
   for (int a = 0; a < 3; ++a) {
     lo[a] = (i < P) ? p[a] : FLT_MAX;
     hi[a] = (i < P) ? p[a] : -FLT_MAX;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], m));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m));
-    }
   }
+  wave_minmax3(lo, hi);
   if (lane == 0) {
     Aabb bx;
 #pragma unroll
@@ -151,14 +152,7 @@ __global__ __launch_bounds__(64) void knn_super_kernel(int nboxes, const Aabb* _
       hi[a] = boxes[b].hi[a];
     }
   }
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-      lo[a] = fminf(lo[a], __shfl_xor(lo[a], m));
-      hi[a] = fmaxf(hi[a], __shfl_xor(hi[a], m));
-    }
-  }
+  wave_minmax3(lo, hi);
   if (lane == 0) {
     Aabb bx;
 #pragma unroll

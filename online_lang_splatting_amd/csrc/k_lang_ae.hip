@@ -239,11 +239,8 @@ __global__ __launch_bounds__(AE_ROWS) void lang_ae_grad_kernel(int N, int vec4, 
   ae_param_grad<AE_H, AE_IN>(lds, dh, x, valid, partial + AE_W1);
   // the row's loss terms: wave tree, then the four waves in order
   double s_l1 = valid ? (double)l1 : 0.0, s_cos = valid ? (double)cosv : 0.0;
-#pragma unroll
-  for (int mm = 32; mm >= 1; mm >>= 1) {
-    s_l1 += __shfl_xor(s_l1, mm);
-    s_cos += __shfl_xor(s_cos, mm);
-  }
+  s_l1 = wave_sum(s_l1);
+  s_cos = wave_sum(s_cos);
   if ((t & 63) == 0) {
     red[t >> 6][0] = s_l1;
     red[t >> 6][1] = s_cos;
@@ -287,9 +284,7 @@ __global__ __launch_bounds__(256) void lang_ae_adam_kernel(int N, int nb, LangAe
   }
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int mm = 32; mm >= 1; mm >>= 1) v += __shfl_xor(v, mm);
+    const double v = wave_sum(acc[k]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][k] = v;
   }
   __syncthreads();

@@ -131,9 +131,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void mapping_loss_kernel(
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < LOSS_SUMS; ++k) {
-    float v = s[k];
-#pragma unroll
-    for (int mm = 32; mm >= 1; mm >>= 1) v += __shfl_xor(v, mm);
+    const float v = wave_sum(s[k]);
     if (lane == 0) red[w][k] = v;
   }
   __syncthreads();

@@ -55,8 +55,6 @@ __host__ __device__ inline MeScratch me_carve(void* scratch, int P) {
   return s;
 }
 
-__device__ inline float me_sigmoid(float x) { return 1.0f / (1.0f + expf(-x)); }  // torch.sigmoid
-
 __device__ inline float me_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
 
 // the class of source row j in densify mode
@@ -68,7 +66,7 @@ __device__ inline uint8_t me_densify_class(const olsr_map_edit_params& p, const 
   const float smax = me_max3(s0, s1, s2);    // torch.max(get_scaling, dim=1).values
   const bool clone = fabsf(g) >= p.max_grad && smax <= p.clone_max_scale;  // torch.norm over a [P,1] row: |g|
   const bool split = g >= p.max_grad && smax > p.clone_max_scale;          // padded_grad: clones never split
-  const bool low_opacity = me_sigmoid(src.opacities[j]) < p.min_opacity;
+  const bool low_opacity = act_sigmoid(src.opacities[j]) < p.min_opacity;
   const bool big = p.screen_size_term && smax > p.big_scale;
   uint8_t c = 0;
   if (split) {
@@ -107,42 +105,11 @@ __global__ __launch_bounds__(ME_ROWS) void map_edit_classify(int P, olsr_map_edi
 // exclusive prefix of the three per-block counts over the blocks, in block order; status = segment totals
 __global__ __launch_bounds__(ME_PREFIX_THREADS) void map_edit_prefix(int nb, int n_append, MeScratch sc,
                                                                       int32_t* __restrict__ status) {
-  __shared__ int32_t part[ME_PREFIX_THREADS / 64];
-  __shared__ int32_t carry_sh;
+  __shared__ int32_t s_w[ME_PREFIX_THREADS / 64];
   int32_t totals[3];
-  for (int seg = 0; seg < 3; ++seg) {
-    const int32_t* cnt = sc.counts + (size_t)seg * nb;
-    int32_t* off = sc.offsets + (size_t)seg * nb;
-    int32_t carry = 0;
-    for (int base = 0; base < nb; base += ME_PREFIX_THREADS) {
-      const int i = base + threadIdx.x;
-      const int32_t v = i < nb ? cnt[i] : 0;
-      // inclusive scan inside the wave (shuffles), then over the waves
-      int32_t x = v;
-      const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-      for (int d = 1; d < 64; d <<= 1) {
-        const int32_t y = __shfl_up(x, d, 64);
-        if (lane >= d) x += y;
-      }
-      if (lane == 63) part[wave] = x;
-      __syncthreads();
-      if (threadIdx.x == 0) {
-        int32_t acc = 0;
-        for (int w = 0; w < ME_PREFIX_THREADS / 64; ++w) {
-          const int32_t t = part[w];
-          part[w] = acc;
-          acc += t;
-        }
-        carry_sh = acc;
-      }
-      __syncthreads();
-      if (i < nb) off[i] = carry + part[wave] + x - v;
-      carry += carry_sh;
-      __syncthreads();
-    }
-    totals[seg] = carry;
-  }
+  for (int seg = 0; seg < 3; ++seg)
+    totals[seg] = single_block_excl_scan<ME_PREFIX_THREADS / 64>(nb, sc.counts + (size_t)seg * nb,
+                                                                 sc.offsets + (size_t)seg * nb, s_w);
   if (threadIdx.x == 0) {
     status[0] = totals[0] + totals[1] + 2 * totals[2] + n_append;
     status[1] = totals[0];
@@ -153,19 +120,6 @@ __global__ __launch_bounds__(ME_PREFIX_THREADS) void map_edit_prefix(int nb, int
   }
 }
 
-// rank of this thread's flag among the block's rows (exclusive), ME_ROWS threads
-__device__ inline int me_block_rank(bool flag, int32_t* wave_counts) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const unsigned long long b = __ballot(flag);
-  const int in_wave = __popcll(b & ((1ull << lane) - 1ull));
-  if (lane == 0) wave_counts[wave] = __popcll(b);
-  __syncthreads();
-  int before = 0;
-  for (int w = 0; w < wave; ++w) before += wave_counts[w];
-  __syncthreads();
-  return before + in_wave;
-}
-
 __global__ __launch_bounds__(ME_ROWS) void map_edit_apply(int P, int M, int F, int nb_src, olsr_map_edit_params p,
                                                           olsr_map_buffers src, const float* __restrict__ z,
                                                           olsr_map_buffers app, MeScratch sc,
@@ -174,7 +128,7 @@ __global__ __launch_bounds__(ME_ROWS) void map_edit_apply(int P, int M, int F, i
   __shared__ int32_t dest[4][ME_ROWS];         // destination row per segment (keep, clone, child 0, child 1), -1 = none
   __shared__ float child_xyz[2][3][ME_ROWS];   // split children, [k][axis][row]
   __shared__ float child_scale[3][ME_ROWS];
-  __shared__ int32_t wave_counts[ME_WAVES];
+  __shared__ u32 wave_counts[ME_WAVES];
   const int width = 11 + 3 * M + F, sh_w = 3 * M;
   const int32_t n_keep = status[1], n_clone = status[2], n_child = status[3];
   const bool zero_acc = (p.mode == OLSR_MAP_EDIT_DENSIFY) || p.n_append > 0;
@@ -220,9 +174,12 @@ __global__ __launch_bounds__(ME_ROWS) void map_edit_apply(int P, int M, int F, i
   const int j = j0 + t;
   const uint8_t c = j < P ? sc.cls[j] : 0;
   const size_t nb = (size_t)nb_src;
-  const int rk = me_block_rank(c & ME_KEEP, wave_counts);
-  const int rc = me_block_rank(c & ME_CLONE, wave_counts);
-  const int rs = me_block_rank(c & ME_CHILD, wave_counts);
+  // ranks of this row among the block's rows of each class (wave_counts is reused: a barrier in between)
+  const int rk = (int)block_rank<ME_WAVES>(c & ME_KEEP, wave_counts);
+  __syncthreads();
+  const int rc = (int)block_rank<ME_WAVES>(c & ME_CLONE, wave_counts);
+  __syncthreads();
+  const int rs = (int)block_rank<ME_WAVES>(c & ME_CHILD, wave_counts);
   dest[0][t] = (c & ME_KEEP) ? sc.offsets[blockIdx.x] + rk : -1;
   dest[1][t] = (c & ME_CLONE) ? n_keep + sc.offsets[nb + blockIdx.x] + rc : -1;
   dest[2][t] = (c & ME_CHILD) ? n_keep + n_clone + sc.offsets[2 * nb + blockIdx.x] + rs : -1;

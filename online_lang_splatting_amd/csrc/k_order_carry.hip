@@ -210,9 +210,7 @@ __global__ __launch_bounds__(T) void order_repair_b_kernel(int P, const u32* __r
   if (totals != nullptr) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
-      u64 t = tot[h];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+      const u64 t = wave_sum(tot[h]);
       if (lane == 0) s_tot[h][w] = t;
     }
     __syncthreads();

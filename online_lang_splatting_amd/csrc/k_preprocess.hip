@@ -95,12 +95,7 @@ __device__ __forceinline__ u32 count_pending_rows(const PendingRows& pd, PreWave
                                                   const float* __restrict__ cut) {
   const int lane = threadIdx.x & 63;
   const u32 nrows = (u32)pd.nrows;
-  u32 incl = nrows;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 o = __shfl_up(incl, d);
-    if (lane >= d) incl += o;
-  }
+  const u32 incl = wave_incl_scan(nrows);
   const u32 total = (u32)__shfl((int)incl, 63);
   if (total == 0) return 0;  // (wave-uniform)
   const u32 rowoff = incl - nrows;
@@ -313,11 +308,8 @@ __global__ __launch_bounds__(256) void preprocess_kernel(
   const u32 nvis = (u32)__popcll(ballot(idx < P && count > 0u));  // Gaussians of this wave that emit instances
   // instances of the reference's rect binning (its num_rendered) and instances this frame emits: one partial per
   // block each, summed by the next kernel (7.8 k same-address atomics would cost more than the whole kernel)
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    area += __shfl_xor(area, m);
-    count += __shfl_xor(count, m);
-  }
+  area = wave_sum(area);
+  count = wave_sum(count);
   if ((threadIdx.x & 63) == 0) {
     s_area[threadIdx.x >> 6] = area;
     s_cnt[threadIdx.x >> 6] = count;

@@ -779,9 +779,7 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     const int lane = lane_id(), w = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      float v = tau[i];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+      const float v = wave_sum(tau[i]);
       if (lane == 0) wsum[w][i] = v;
     }
     __syncthreads();
@@ -800,25 +798,13 @@ __global__ __launch_bounds__(PC_THREADS) void pb_compact_kernel(int nb, const u3
                                                                 const u32* __restrict__ act_list, u32* __restrict__ compact,
                                                                 int32_t* __restrict__ total_out) {
   __shared__ u32 s_w[PC_THREADS / 64];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const int per = (nb + PC_THREADS - 1) / PC_THREADS;
   const int b0 = min(tid * per, nb), b1 = min(b0 + per, nb);
   u32 mine = 0;
   for (int b = b0; b < b1; ++b) mine += act_count[b];
-  u32 incl = mine;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const u32 v = __shfl_up(incl, o);
-    if (lane >= o) incl += v;
-  }
-  if (lane == 63) s_w[w] = incl;
-  __syncthreads();
-  u32 off = incl - mine, total = 0;
-#pragma unroll
-  for (int k = 0; k < PC_THREADS / 64; ++k) {
-    off += (k < w) ? s_w[k] : 0u;
-    total += s_w[k];
-  }
+  u32 total;
+  u32 off = block_excl_scan<PC_THREADS / 64>(mine, s_w, &total);
   for (int b = b0; b < b1; ++b) {
     const u32 c = act_count[b];
     for (u32 i = 0; i < c; ++i) compact[off + i] = act_list[(size_t)b * PB_THREADS + i];
@@ -905,9 +891,7 @@ __global__ __launch_bounds__(CH_THREADS) void pb_chain_kernel(
     const int lane = lane_id(), w = threadIdx.x >> 6;
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
-      float v = tau[i];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+      const float v = wave_sum(tau[i]);
       if (lane == 0) wsum[w][i] = v;
     }
     __syncthreads();
@@ -955,9 +939,7 @@ __global__ __launch_bounds__(TAU_T) void tau_final_kernel(const float* __restric
   }
 #pragma unroll
   for (int c = 0; c < 6; ++c) {
-    float v = acc[c];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m);
+    const float v = wave_sum(acc[c]);
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6][c] = v;
   }
   __syncthreads();

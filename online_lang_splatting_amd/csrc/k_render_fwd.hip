@@ -539,9 +539,7 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
     __syncthreads();
 #pragma unroll
     for (int k = 0; k < LOSS_SUMS; ++k) {
-      float v = sums[k];
-#pragma unroll
-      for (int mm = 32; mm >= 1; mm >>= 1) v += __shfl_xor(v, mm);
+      const float v = wave_sum(sums[k]);
       if ((tid & 63) == 0) s_loss[w * LOSS_SUMS + k] = v;
     }
     __syncthreads();

@@ -35,37 +35,6 @@ constexpr int FS_T = FUSED_SORT_THREADS;  // 1024
 constexpr int FS_W = FS_T / 64;           // 16 waves
 // (the look-back's spin bound is SortKnobs::spin_limit, default 1 << 22 polls: seconds; a predecessor publishes within microseconds)
 
-__device__ __forceinline__ int64_t fs_bounded_n(int64_t n_host, const int32_t* n_dev) {
-  if (n_dev) {
-    const int64_t nd = (int64_t)(*n_dev);
-    return nd < n_host ? nd : n_host;
-  }
-  return n_host;
-}
-
-__device__ __forceinline__ u32 fs_wave_incl_scan(u32 v) {
-  const int lane = lane_id();
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const u32 o = __shfl_up(v, d);
-    if (lane >= d) v += o;
-  }
-  return v;
-}
-// exclusive prefix across the threads of a block of NW waves; s_w: NW words of LDS scratch (reusable after return)
-template <int NW = FS_W>
-__device__ __forceinline__ u32 fs_block_excl_scan(u32 v, u32* s_w) {
-  const int lane = lane_id(), w = threadIdx.x >> 6;
-  const u32 incl = fs_wave_incl_scan(v);
-  if (lane == 63) s_w[w] = incl;
-  __syncthreads();
-  u32 base = 0;
-#pragma unroll
-  for (int i = 0; i < NW; ++i) base += (i < w) ? s_w[i] : 0u;
-  __syncthreads();
-  return base + incl - v;
-}
-
 // Published digit counts: one 16-bit word per digit (bit 15 = ready, count <= 8192 below), eight of them per 16-byte
 // granule.  Granules are written and read whole with agent-scope (sc1: write-through / L1-bypassing) accesses; every
 // 16-bit word carries its own ready bit, so a reader needs no ordering between them.
@@ -147,11 +116,8 @@ __device__ __forceinline__ void frame_housekeeping(const FrameHousekeeping& hous
     rect += house.part_rect[i];
     cnt += house.part_count[i];
   }
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) {
-    rect += __shfl_xor(rect, m);
-    cnt += __shfl_xor(cnt, m);
-  }
+  rect = wave_sum(rect);
+  cnt = wave_sum(cnt);
   if ((tid & 63) == 0) {
     s_red[0][tid >> 6] = rect;
     s_red[1][tid >> 6] = cnt;
@@ -237,7 +203,8 @@ __global__ __launch_bounds__(T) void sort_hist_kernel(const u32* __restrict__ ke
     u32 mine = 0;
     for (int i = p0; i < p1; ++i) mine += ca.part_vis[i];
     __shared__ u32 s_scan[2 * (T / 64)];
-    u32 run = fs_block_excl_scan<T / 64>(mine, s_scan);
+    u32 run = block_excl_scan<T / 64>(mine, s_scan);
+    __syncthreads();  // (s_scan is free again)
     for (int i = p0; i < p1; ++i) {
       s_pref[i] = run;
       run += ca.part_vis[i];
@@ -245,7 +212,7 @@ __global__ __launch_bounds__(T) void sort_hist_kernel(const u32* __restrict__ ke
     if (blockIdx.x == 0 && p0 < ca.nparts && p1 == ca.nparts) *ca.n_out = (int32_t)run;  // (the thread that holds the last share)
   }
   __syncthreads();
-  const int64_t n = fs_bounded_n(n_host, n_dev);
+  const int64_t n = bounded_n(n_host, n_dev);
   const u32 mask = (1u << db) - 1u;
   const int64_t stride = (int64_t)gridDim.x * T * 4;
   constexpr int HU = 4;  // independent 16-byte loads in flight per thread (the loop is latency-bound otherwise)
@@ -281,7 +248,7 @@ __global__ __launch_bounds__(T) void sort_hist_kernel(const u32* __restrict__ ke
         const int64_t wave0 = i0 - 4 * (int64_t)(tid & 63);  // (wave-uniform; a multiple of 256)
         if (wave0 >= n) continue;
         const u32 c = (u32)__builtin_popcount(emits[u]);
-        u32 pos = s_pref[(int)(wave0 >> 8)] + fs_wave_incl_scan(c) - c;
+        u32 pos = s_pref[(int)(wave0 >> 8)] + wave_incl_scan(c) - c;
 #pragma unroll
         for (int j = 0; j < 4; ++j)
           if (emits[u] & (1u << j)) {
@@ -422,14 +389,15 @@ __global__ __launch_bounds__(T, (T == 1024 ? (KPT <= 2 ? 8 : 4) : (KPT <= 8 ? 8 
   if (tid == 0) s_bid = atomicAdd(ticket, 1u);
   for (u32 i = tid; i < TW * NB; i += T) cnt[i] = 0;
   const u32 gh = ((u32)tid < NB) ? ghist[tid] : 0u;
-  const u32 gdig = fs_block_excl_scan<TW>(gh, s_w);  // global start of every digit (two barriers: s_bid is visible after them)
+  const u32 gdig = block_excl_scan<TW>(gh, s_w);  // global start of every digit
+  __syncthreads();  // (s_w is reused; s_bid is visible after the scan's barrier)
   const u32 b = s_bid;
   FS_STAMP(0);
   if (timing != nullptr && tid == 0) {
     timing[(size_t)b * 8 + 6] = (unsigned long long)(__builtin_amdgcn_s_getreg(63508) & 15);  // HW_REG_XCC_ID
     timing[(size_t)b * 8 + 7] = (unsigned long long)blockIdx.x;
   }
-  const int64_t n = fs_bounded_n(n_host, n_dev);
+  const int64_t n = bounded_n(n_host, n_dev);
   const int64_t bbase = (int64_t)b * CHUNK;
   // The frame is already broken (an earlier kernel of it lost a predecessor's counts): keys and values may be garbage — the
   // last tile pass would index the tile ranges with them — so do nothing.  Uniform for an error raised by an earlier kernel;
@@ -469,7 +437,8 @@ __global__ __launch_bounds__(T, (T == 1024 ? (KPT <= 2 ? 8 : 4) : (KPT <= 8 ? 8 
     pub[d] = (u16)(FS_READY16 | tot);
   }
   // local start of every digit inside the block
-  const u32 start = fs_block_excl_scan<TW>(d < NB ? tot : 0u, s_w);
+  const u32 start = block_excl_scan<TW>(d < NB ? tot : 0u, s_w);
+  __syncthreads();  // (s_w is free again)
   // publish this block's row: NB / 8 granules of eight 16-bit counts, write-through (sc1)
   const auto rsrc = __builtin_amdgcn_make_buffer_rsrc(status, 0, (int)(gridDim.x * NB * 2u), 0x00020000);
   if (tid < C && !(fault != 0 && b == 0)) {  // (fault: test hook — this block's counts never arrive)
@@ -599,9 +568,7 @@ __global__ __launch_bounds__(T, (T == 1024 ? (KPT <= 2 ? 8 : 4) : (KPT <= 8 ? 8 
         const u32 b0 = (u32)__builtin_amdgcn_readfirstlane((int)bucket);
         if (act == ~0ull && ballot(bucket != b0) == 0ull) {
           // the common case: a full wave inside one emission block — a plain wave sum
-          u64 t = cntg;
-#pragma unroll
-          for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+          const u64 t = wave_sum(cntg);
           if (lane == 0 && t) atomicAdd(&emit_totals[b0], t);
         } else {
           u64 run = cntg;
@@ -705,7 +672,8 @@ __global__ __launch_bounds__(FS_T) void sort_small_kernel(const u32* __restrict_
         tot += c[i];
       }
     }
-    const u32 start = fs_block_excl_scan(d < NB ? tot : 0u, s_w);
+    const u32 start = block_excl_scan<FS_W>(d < NB ? tot : 0u, s_w);
+    __syncthreads();  // (s_w is free again)
     if (d < NB) {
       u32 run = start;
 #pragma unroll
@@ -755,8 +723,7 @@ __global__ __launch_bounds__(FS_T) void sort_small_kernel(const u32* __restrict_
       t = emit_total_pack(inst_count[vv]);
     }
     static_assert(EMIT_CHUNK == FS_T, "one emission block per 1024 ranks");
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) t += __shfl_xor(t, m);
+    t = wave_sum(t);
     if (lane == 0 && t) atomicAdd(&emit_totals[k], t);
   }
 }

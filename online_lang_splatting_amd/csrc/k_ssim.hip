@@ -152,11 +152,8 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_stats_kernel(int W, int H, 
     }
   }
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-  for (int mm = 32; mm >= 1; mm >>= 1) {
-    s_l1 += __shfl_xor(s_l1, mm);
-    s_ssim += __shfl_xor(s_ssim, mm);
-  }
+  s_l1 = wave_sum(s_l1);
+  s_ssim = wave_sum(s_ssim);
   if (lane == 0) {
     red[w][0] = s_l1;
     red[w][1] = s_ssim;
@@ -186,9 +183,7 @@ __device__ __forceinline__ void ssim_final_block(const SsimFinalArgs& a, double 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < 2; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int mm = 32; mm >= 1; mm >>= 1) v += __shfl_xor(v, mm);
+    const double v = wave_sum(acc[k]);
     if (lane == 0) red[w][k] = v;
   }
   __syncthreads();

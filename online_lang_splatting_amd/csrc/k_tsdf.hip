@@ -157,28 +157,6 @@ __device__ inline int ts_crossings(const olsr_tsdf_volume& vol, float min_weight
   return bits;
 }
 
-// exclusive prefix of v over the block's threads (thread order); total: the block's sum
-__device__ inline int ts_block_scan(int v, int32_t* wave_sums, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int x = v;
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const int y = __shfl_up(x, d, 64);
-    if (lane >= d) x += y;
-  }
-  if (lane == 63) wave_sums[wave] = x;
-  __syncthreads();
-  int before = 0;
-  total = 0;
-#pragma unroll
-  for (int k = 0; k < TS_WAVES; ++k) {
-    const int s = wave_sums[k];
-    if (k < wave) before += s;
-    total += s;
-  }
-  return before + x - v;
-}
-
 template <bool EMIT>
 __global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol, float min_weight, int32_t* __restrict__ counts,
                                                            const int32_t* __restrict__ offsets, int capacity,
@@ -198,8 +176,8 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol,
     t0 = vol.tsdf[i];
     bits = ts_crossings(vol, min_weight, i, x, y, z, t0);
   }
-  int total;
-  const int rank = ts_block_scan(__popc(bits), wave_sums, total);
+  int32_t total;
+  const int rank = block_excl_scan<TS_WAVES>((int32_t)__popc(bits), wave_sums, &total);
   if constexpr (!EMIT) {
     if (threadIdx.x == 0) counts[blockIdx.x] = total;
     return;
@@ -244,37 +222,10 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol,
 __global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_surface_prefix(int nb, const int32_t* __restrict__ counts,
                                                                           int32_t* __restrict__ offsets,
                                                                           int32_t* __restrict__ status) {
-  __shared__ int32_t part[TS_PREFIX_THREADS / 64];
-  __shared__ int32_t carry_sh;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  int32_t carry = 0;
-  for (int base = 0; base < nb; base += TS_PREFIX_THREADS) {
-    const int i = base + threadIdx.x;
-    const int32_t v = i < nb ? counts[i] : 0;
-    int32_t x = v;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-      const int32_t y = __shfl_up(x, d, 64);
-      if (lane >= d) x += y;
-    }
-    if (lane == 63) part[wave] = x;
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      int32_t acc = 0;
-      for (int k = 0; k < TS_PREFIX_THREADS / 64; ++k) {
-        const int32_t t = part[k];
-        part[k] = acc;
-        acc += t;
-      }
-      carry_sh = acc;
-    }
-    __syncthreads();
-    if (i < nb) offsets[i] = carry + part[wave] + x - v;
-    carry += carry_sh;
-    __syncthreads();
-  }
+  __shared__ int32_t s_w[TS_PREFIX_THREADS / 64];
+  const int32_t total = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, counts, offsets, s_w);
   if (threadIdx.x == 0) {
-    status[0] = carry;
+    status[0] = total;
     status[1] = 0;
   }
 }

@@ -80,9 +80,7 @@ __device__ __forceinline__ void loss_final_block(const LossFinalArgs& a, double 
   const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
 #pragma unroll
   for (int k = 0; k < LOSS_SUMS; ++k) {
-    double v = acc[k];
-#pragma unroll
-    for (int mm = 32; mm >= 1; mm >>= 1) v += __shfl_xor(v, mm);
+    const double v = wave_sum(acc[k]);
     if (lane == 0) red[w][k] = v;
   }
   __syncthreads();

@@ -47,7 +47,8 @@ def _bits(mask, P):
 
 @pytest.mark.parametrize("P,width,rows,mask_kind", [
     (5000, 29, 300, "exact"), (5000, 29, 300, "none"), (64 * 16 * 3 + 17, 91, 777, "superset"), (1024, 14, 5, "ones"),
-    (100003, 29, 2500, "exact"), (63, 11, 10, "exact"), (2048, 29, 0, "exact")])
+    (100003, 29, 2500, "exact"), (63, 11, 10, "exact"), (2048, 29, 0, "exact"),
+    (256 * 1024 + 1041, 11, 3000, "exact")])  # 258 count blocks: more than the 256 threads that stride over them
 def test_two_ranks_on_one_gpu_equal_the_dense_exchange(hip, P, width, rows, mask_kind):
     _two_ranks(P, width, rows, mask_kind)
 
@@ -98,6 +99,10 @@ def _two_ranks(P, width, rows, mask_kind):
         imax = torch.maximum(ranks[0]["imax"], ranks[1]["imax"])          # collective 1: MAX
         for r in ranks:
             r["imax"].copy_(imax)
+            check(L.olsr_sparse_exchange_pack(P, width, cap, p(r["flat"]), p(r["imax"]), p(r["rad"]), p(r["mask"]), p(r["den"]),
+                                              None, None, p(r["scr"]), p(r["status"]), stream))      # the count-only call
+            assert r["status"].tolist() == [n_union, int(n_union > cap)]
+            r["status"].zero_()
             check(L.olsr_sparse_exchange_pack(P, width, cap, p(r["flat"]), p(r["imax"]), p(r["rad"]), p(r["mask"]), p(r["den"]),
                                               p(r["idx"]), p(r["fsum"]), p(r["scr"]), p(r["status"]), stream))
             assert r["status"].tolist() == [n_union, int(n_union > cap)]

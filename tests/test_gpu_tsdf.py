@@ -337,7 +337,8 @@ def test_surface_of_a_fused_volume(hip, feature, min_weight):
         assert len(want[2]) > len(R.surface(*ref.arrays(), vol.vol_origin, VOXEL, 1.0, feature == "rgb")[2])
 
 
-@pytest.mark.parametrize("dim", [(1, 1, 1), (5, 3, 70), (64, 1, 65)])
+# (65, 64, 65): 1057 blocks of 256 voxels, more than the 1024 block counts one round of the surface prefix handles
+@pytest.mark.parametrize("dim", [(1, 1, 1), (5, 3, 70), (64, 1, 65), (65, 64, 65)])
 @pytest.mark.parametrize("feature", [3, "rgb"])
 def test_surface_of_a_random_volume_reaches_the_last_planes(hip, dim, feature):
     """Random signs: crossings on every kind of edge, those that end on the last plane of each axis included, over several
