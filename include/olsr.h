@@ -714,6 +714,48 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params *params, const float 
                               float *smoothed, float *blended, float *score, int32_t *coord, float *minmax,
                               uint8_t *mask, int32_t *labels, void *scratch, void *hip_stream);
 
+/* ---- the general language encoder 768 -> 32 (utils/slam_backend.py:556-559 and :392-395) ---------------------------------
+ * The reference turns a keyframe's CLIP map clip_viz_dense [1,768,h,w] into the rows the online autoencoder trains on with
+ *   clip_viz_dense.permute(0,2,3,1).view(-1,768) -> auto_model.encode  (AutoencoderMLP.encode, language/autoencoder/model.py:
+ *   15-56: Linear 768 -> 512, then three times BatchNorm1d / ReLU / Linear down to 256 -> 128 -> 64 -> 32, then x / |x|)
+ * in torch ops: about 15 launches, a permuted copy of the map and every intermediate written and read again.  The module is in
+ * eval() there (:142), so a BatchNorm1d is its running statistics.  Here one launch, the mirror of olsr_lang_query_sims:
+ *   h1 = W0 x + b0;   h(k+1) = W(k) relu(bn(k)(h(k))) + b(k), k = 1..4;   features32 = h5 / |h5|
+ *   bn(h) = alpha h + beta per channel, alpha = weight / sqrt(running_var + bn_eps), beta = bias - running_mean alpha, both
+ *   computed in double and rounded once, applied as one fmaf in the producing layer's epilogue (never folded into weights)
+ * Every product is float32 on v_mfma_f32_16x16x4_f32 (a fixed fmaf chain per output), ReLU is fmaxf(., 0) with a NaN kept
+ * (torch's ReLU: a NaN input row gives a NaN output row), |h5|^2 is accumulated in double, and the norm has no epsilon: a row
+ * whose h5 is exactly zero gives NaN, as in the reference.  No atomics: a call is bit-reproducible, a pixel's result does not
+ * depend on the other pixels, and both input layouts give the same bits.
+ *   widths          the layer widths, input first.  This build has a kernel for the two-stage chain {768, 512, 256, 128, 64, 32};
+ *                   any other list (the single-stage {768, 384, 192, 96, 48, 24, 15} included) is OLSR_ERR_ARG
+ *   features768     device float, N >= 1 pixels.  OLSR_LANG_ENCODER_IN_CHANNELS: [768] planes of N pixels, plane_stride >= N
+ *                   elements apart — a [1,768,h,w] tensor, or one item of a batch, read in place; no alignment is assumed and
+ *                   nothing beyond pixel N - 1 of a plane is read.  OLSR_LANG_ENCODER_IN_ROWS: [N,768] (plane_stride unused)
+ *   encoder_params  device float[572128], 16-byte aligned: AutoencoderMLP.encoder in state_dict order without
+ *                   num_batches_tracked: encoder.0.weight [512,768], encoder.0.bias [512], encoder.1.{weight, bias,
+ *                   running_mean, running_var} [512], encoder.3.weight [256,512], encoder.3.bias, encoder.4.*, encoder.6.*,
+ *                   encoder.7.*, encoder.9.*, encoder.10.*, encoder.12.weight [32,64], encoder.12.bias [32]
+ *   features32      device float[N,32] rows or NULL: what olsr_lang_ae_train_step takes, the back end's coco_lang_feat
+ *   online_params, codes   both or neither, codes only with online_params: device float[2351] (the layout of olsr_lang_ae_*) and
+ *                   float[N,15] or [15,N] (code_layout, OLSR_LANG_AE_CODES_*).  The epilogue then also runs the online encoder
+ *                   32 -> 24 -> 15 on each pixel's unit row; the codes equal olsr_lang_ae_encode(features32) bit for bit
+ * features32 and codes must not both be NULL. */
+#define OLSR_LANG_ENCODER_PARAMS 572128 /* 568288 Linear + 3840 BatchNorm */
+#define OLSR_LANG_ENCODER_IN_ROWS 0
+#define OLSR_LANG_ENCODER_IN_CHANNELS 1
+typedef struct olsr_lang_encoder_params {
+  int32_t n_widths;
+  int32_t widths[8];
+  int32_t in_layout;     /* OLSR_LANG_ENCODER_IN_* */
+  int32_t code_layout;   /* OLSR_LANG_AE_CODES_* (checked even when codes is NULL) */
+  int64_t plane_stride;  /* elements between two channel planes (channel layout) */
+  double bn_eps;         /* BatchNorm1d's eps: 1e-5 */
+} olsr_lang_encoder_params;
+int olsr_lang_encoder_encode(const olsr_lang_encoder_params *params, int32_t N, const float *features768,
+                             const float *encoder_params, const float *online_params, float *features32,
+                             float *codes, void *hip_stream);
+
 /* ---- TSDF fusion of depth and language maps into a 3-D map (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) ---------------
  * The reference's 3-D evaluation fuses, per keyframe, a depth image and a feature image (packed 8-bit colour in fusion.py, 3
  * float channels in fusion2.py, 15 in fusion3.py) into a truncated signed distance volume with one CUDA launch per frame, 16

@@ -155,6 +155,31 @@ class OlsrLangQueryParams(C.Structure):
                                  "out_height")] + [("thresh", C.c_float), ("flags", C.c_uint32)]
 
 
+# the general language encoder (OLSR_LANG_ENCODER_*): AutoencoderMLP.encoder in state_dict order, without num_batches_tracked
+LANG_ENCODER_PARAMS = 572128
+LANG_ENCODER_IN_ROWS, LANG_ENCODER_IN_CHANNELS = 0, 1   # features as [N,768] rows / as [768] planes of a [1,768,h,w] map
+LANG_ENCODER_WIDTHS = (768, 512, 256, 128, 64, 32)
+
+
+def _lang_encoder_state():
+    out = []
+    for k, (i, o) in enumerate(zip(LANG_ENCODER_WIDTHS, LANG_ENCODER_WIDTHS[1:])):
+        out += [(f"encoder.{3 * k}.weight", (o, i)), (f"encoder.{3 * k}.bias", (o,))]
+        if k < len(LANG_ENCODER_WIDTHS) - 2:   # BatchNorm1d on the layer's output, ahead of the ReLU
+            out += [(f"encoder.{3 * k + 1}.{n}", (o,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    return tuple(out)
+
+
+LANG_ENCODER_STATE = _lang_encoder_state()
+
+
+class OlsrLangEncoderParams(C.Structure):
+    """struct olsr_lang_encoder_params, include/olsr.h."""
+
+    _fields_ = [("n_widths", C.c_int32), ("widths", C.c_int32 * 8), ("in_layout", C.c_int32), ("code_layout", C.c_int32),
+                ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
+
+
 # point-cloud metrics (OLSR_CLOUD_*)
 CLOUD_MAX_SEGMENTS = 32767
 

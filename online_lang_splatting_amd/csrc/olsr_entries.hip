@@ -332,6 +332,31 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params* p, const float* sims
   return launch_check("lang_query_relevancy");
 }
 
+int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const float* features768, const float* encoder_params,
+                             const float* online_params, float* features32, float* codes, void* hip_stream) {
+  static const int32_t built[6] = {OLSR_LANG_QUERY_FEATURE_DIM, 512, 256, 128, 64, OLSR_LANG_AE_IN};
+  const char* widths_msg = "lang_encoder_encode: this build encodes the layer widths {768, 512, 256, 128, 64, 32} only";
+  if (!p) return fail(OLSR_ERR_ARG, "lang_encoder_encode: the parameter struct is NULL");
+  if (p->n_widths != 6) return fail(OLSR_ERR_ARG, widths_msg);
+  for (int k = 0; k < 6; ++k)
+    if (p->widths[k] != built[k]) return fail(OLSR_ERR_ARG, widths_msg);
+  if (N < 1) return fail(OLSR_ERR_ARG, "lang_encoder_encode: N must be positive");
+  if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS)
+    return fail(OLSR_ERR_ARG, "lang_encoder_encode: unknown input layout");
+  if (!lang_ae_layout_ok(p->code_layout)) return fail(OLSR_ERR_ARG, "lang_encoder_encode: unknown code layout");
+  if (p->in_layout == OLSR_LANG_ENCODER_IN_CHANNELS && p->plane_stride < (int64_t)N)
+    return fail(OLSR_ERR_ARG, "lang_encoder_encode: plane_stride must be at least N in the channel layout");
+  if (!(p->bn_eps > 0.0)) return fail(OLSR_ERR_ARG, "lang_encoder_encode: bn_eps must be positive");
+  if (!features768 || !encoder_params) return fail(OLSR_ERR_ARG, "lang_encoder_encode: features768 and encoder_params are required");
+  if (!features32 && !codes) return fail(OLSR_ERR_ARG, "lang_encoder_encode: features32 and codes are both NULL");
+  if (codes && !online_params) return fail(OLSR_ERR_ARG, "lang_encoder_encode: codes need online_params");
+  if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "lang_encoder_encode: encoder_params must be 16-byte aligned");
+  const hipError_t e = launch_lang_encoder(*p, N, features768, encoder_params, online_params, features32, codes,
+                                           (hipStream_t)hip_stream);
+  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("lang_encoder_encode: ") + hipGetErrorString(e));
+  return launch_check("lang_encoder_encode");
+}
+
 int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
                               const float* dL_dsh,
                               const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,

@@ -275,6 +275,10 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
                                  float* blended, float* score, int32_t* coord, float* minmax, uint8_t* mask, int32_t* labels,
                                  void* scratch, hipStream_t st);
 
+// k_lang_encoder.hip: the general language encoder 768 -> 32 (include/olsr.h)
+hipError_t launch_lang_encoder(const olsr_lang_encoder_params& p, int N, const float* features, const float* params,
+                               const float* online, float* features32, float* codes, hipStream_t st);
+
 // k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface point cloud (include/olsr.h)
 void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st);
 void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_tsdf_view* views, hipStream_t st);

@@ -29,7 +29,7 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 
 from . import _abi, losses
-from ._lib import check, lib
+from ._lib import OlsrError, check, lib
 from .frame_shard import FrameLanes, FusedAdam, GradLayout, RasterWorkspace
 
 
@@ -591,6 +591,25 @@ class OnlineLanguageTargets:
             raise RuntimeError(f"add_keyframe: features must be [{h * w},32] for hw = {self.hw}")
         loss, codes = self.codec.train_step(features32, self.lr, codes="pre", layout="channels")
         self.features[view_id] = features32.detach().clone()
+        self.targets[view_id] = codes.clone().view(codes.shape[0], h, w)
+        self.steps += 1
+        self.last_loss = loss.clone()
+        return self.targets[view_id]
+
+    def add_keyframe_hr(self, view_id, hr_features: torch.Tensor, encoder) -> torch.Tensor:
+        """hr_features [1,768,h,w] (or [768,h,w], or [h*w,768] rows) float32 on the codec's device, encoder a
+        lang_encoder.LanguageEncoder: the general encoder writes the view's [h*w,32] rows straight into the buffer kept for
+        rehearsal (utils/slam_backend.py:556-559), then the train step of add_keyframe on them.  -> the [15,h,w] target."""
+        h, w = self.hw
+        feats = torch.empty(h * w, _abi.LANG_AE_IN, dtype=torch.float32, device=self.codec.device)
+        try:
+            encoder.encode(hr_features, out=feats)
+        except OlsrError:
+            raise
+        except RuntimeError as e:
+            raise RuntimeError(f"add_keyframe_hr: features must encode to [{h * w},32] for hw = {self.hw}: {e}") from e
+        loss, codes = self.codec.train_step(feats, self.lr, codes="pre", layout="channels")
+        self.features[view_id] = feats
         self.targets[view_id] = codes.clone().view(codes.shape[0], h, w)
         self.steps += 1
         self.last_loss = loss.clone()
