@@ -6,9 +6,13 @@
 // the frame-sharded step all-reduces IS the gradient of all seven (row = [3 xyz | 3M sh | 1 opacity |
 // 3 scale | 4 rotation | F language]), so one pass reads a row of gradient, parameters and both moments and
 // writes parameters and moments back.  The arithmetic is torch.optim.Adam's single-tensor path, operation for
-// operation (torch/optim/adam.py: lerp, mul/addcmul, sqrt / bias_correction2_sqrt + eps, addcdiv), dense:
-// a Gaussian with zero gradient still decays its moments and moves, exactly as in the reference — a
-// "visible rows only" step would be cheaper but is a different optimiser.
+// operation (torch/optim/adam.py, _single_tensor_adam: lerp, mul/addcmul, sqrt / bias_correction2_sqrt + eps, addcdiv),
+// every float32 operation rounded once: the UNFUSED sequence, equal bit for bit to its numpy restatement
+// (tests/adam_ref.py, tests/test_gpu_adam.py).  torch's own CPU build departs from that sequence by the multiply-adds
+// its kernels fuse (a quarter of the exp_avg elements differ in bits after three steps), so
+// against torch.optim.Adam itself the match is to rounding, not to the bit.  Dense: a Gaussian with zero gradient
+// still decays its moments and moves, exactly as in the reference — a "visible rows only" step would be cheaper but
+// is a different optimiser.
 //
 // HBM-bound: 5 reads + 3 writes of P x width floats, all coalesced (consecutive threads = consecutive floats
 // of the flat arrays; the parameter arrays are [P, k] slices addressed per (row, column)).
@@ -41,7 +45,7 @@ struct AdamBuckets {
   int n_more;
   // row masks (olsr_grad_bucket.row_mask: bit g clear = row g of that bucket is zero), or null = every row is read.
   // A block covers ADAM_G = 64 Gaussians = one mask word: rows a mask proves zero are not read at all (their gradient is the
-  // +0.0 the row holds), the update itself stays dense — parameters and moments are those of torch.optim.Adam bit for bit.
+  // +0.0 the row holds), the update itself stays dense — parameters and moments are those of the unmasked step bit for bit.
   const unsigned long long* mask0;
   const unsigned long long* mask_more[OLSR_ADAM_MAX_BUCKETS - 1];
 };

@@ -12,7 +12,9 @@
 //                         bias gradient: float32 sums over the workgroup's rows in a fixed order, written as this workgroup's partial.
 //   lang_ae_adam_kernel   one thread per parameter: the partials are added across workgroups in DOUBLE in workgroup order, rounded
 //                         once to float32 (the gradient autograd would hand to Adam), and the parameter takes torch's single-tensor
-//                         Adam step, operation for operation as k_adam.hip.  Its first workgroup also adds the loss partials.
+//                         Adam step, operation for operation as k_adam.hip: the unfused float32 sequence, bit for bit its
+//                         restatement tests/adam_ref.py on the recorded gradient (torch's CPU build fuses some of the
+//                         multiply-adds and agrees to rounding only).  Its first workgroup also adds the loss partials.
 // No atomics: every sum has a fixed order, so a step is bit-reproducible.  The step count lives on the device (as in k_pose.hip).
 //
 // Decisions autograd makes and this kernel repeats: relu'(0) = 0 (a unit whose pre-activation is <= 0 passes nothing),

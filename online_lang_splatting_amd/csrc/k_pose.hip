@@ -14,7 +14,9 @@
 // and ~40 dependent launches of one-element kernels cost more than the 0.6 ms of rasterizer work they separate.
 //
 // Arithmetic: torch's single-tensor Adam operation for operation (lerp, mul/addcmul, sqrt / bias_correction2_sqrt +
-// eps, addcdiv on a parameter that update_pose reset to zero), scalars formed in double on the host; SE3_exp with the
+// eps, addcdiv on a parameter that update_pose reset to zero), scalars formed in double on the host, every float32
+// operation rounded once — the unfused sequence, bit for bit its restatement tests/adam_ref.py (tests/test_gpu_pose.py);
+// torch's CPU build departs from it by its own fused multiply-adds, hence the golden file's tolerances; SE3_exp with the
 // reference's small-angle branches (SO3_exp / V, utils/pose_utils.py:26-58); fp32 matrix products in torch's
 // row-times-column order.  Pinned by golden vectors generated from the reference's own SE3_exp / update_pose / Camera
 // (tests/golden/make_golden_pose.py).

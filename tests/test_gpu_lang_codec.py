@@ -15,6 +15,7 @@ golden cases); 4 * 2^-24 is two ulp of a float32 of magnitude 1.  The single-ste
 import pytest
 import torch
 
+import adam_ref
 import lang_codec_ref as R
 
 pytestmark = pytest.mark.gpu
@@ -137,6 +138,25 @@ def test_adam_on_the_recorded_gradient(hip, key, counter):
         print(f"{key} {counter} counter, step {i + 1}: largest parameter move {moved:.3e}, largest distance to torch.optim.Adam {d:.3e}")
         assert moved > 0.5 * lr
         assert int(c.step_dev) == i + 1
+
+
+@pytest.mark.parametrize("key", ["n1000_s0", "n257_s3"])
+def test_adam_on_the_recorded_gradient_equals_the_fp32_restatement(hip, key):
+    """lang_ae_adam_kernel with the caller's counter: the 2 351 parameters and both moments after each of six steps equal, bit
+    for bit (a == b or both NaN, the sign of zero included), adam_ref.vector_step — the unfused float32 sequence of torch's
+    single-tensor Adam — applied to the float32 gradient that step recorded (grad_out)."""
+    flat, x, lr, _, _, _ = _golden_case(key)
+    xd = x.to(DEV)
+    c = _codec(flat)
+    p, m, v = flat.numpy().copy(), c.exp_avg.cpu().numpy().copy(), c.exp_avg_sq.cpu().numpy().copy()
+    assert not m.any() and not v.any()
+    for i in range(6):
+        grad = torch.zeros(R.N_PARAMS, device=DEV)
+        c.train_step(xd, lr, codes=None, grad_out=grad, step=i + 1)
+        p, m, v = adam_ref.vector_step(p, m, v, grad.cpu().numpy(), lr, i + 1)
+        for name, got, want in (("parameters", c.flat, p), ("exp_avg", c.exp_avg, m), ("exp_avg_sq", c.exp_avg_sq, v)):
+            same = adam_ref.same_bits(got.cpu().numpy(), want)
+            assert same.all(), (key, i + 1, name, int((~same).sum()))
 
 
 @pytest.mark.parametrize("key,N,seed", R.golden_cases())

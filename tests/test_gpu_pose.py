@@ -6,6 +6,7 @@ import numpy as np
 import pytest
 import torch
 
+import adam_ref
 from online_lang_splatting_amd.scene import default_camera, make_scene
 
 pytestmark = pytest.mark.gpu
@@ -51,6 +52,26 @@ def test_pose_step_matches_the_references_update(hip):
             np.testing.assert_allclose(ps.T_w2c.cpu().numpy(), o.T_w2c, rtol=0, atol=tol)
         # the last row of T_w2c is exactly [0 0 0 1] (update_RT rebuilds it)
         assert ps.T_w2c.cpu()[3].tolist() == [0.0, 0.0, 0.0, 1.0]
+
+
+def test_pose_adam_equals_the_fp32_restatement(hip):
+    """The Adam half of olsr_pose_step with the host-side step count, bit for bit (the sign of zero included) against
+    adam_ref.pose_step_adam — the unfused float32 sequence of torch's single-tensor Adam — after every step of every golden
+    sequence: the tau applied (state words 64..69), the moments of tau (52..63), the exposure pair (70, 71) and its moments
+    (72..75).  Sequence 2 has exactly-zero gradients (tau = +0.0, moments stay zero), sequence 3 tiny learning rates."""
+    dev = torch.device(DEV)
+    words = dict(tau=slice(64, 70), tau_m=slice(52, 58), tau_v=slice(58, 64), exposure=slice(70, 72), exposure_m=slice(72, 74),
+                 exposure_v=slice(74, 76))
+    for s in range(int(G["num_seq"])):
+        ps = _pose_state(s, dev)
+        lr = tuple(float(x) for x in G[f"seq{s}_lr"])
+        for i, (gt, ge) in enumerate(zip(G[f"seq{s}_grad_tau"], G[f"seq{s}_grad_exposure"])):
+            before = ps.state.cpu().numpy().copy()
+            ps.step(torch.from_numpy(gt).to(dev), torch.from_numpy(ge).to(dev))
+            after = ps.state.cpu().numpy()
+            want = adam_ref.pose_step_adam(before, gt, ge, lr, i + 1)
+            for name, sl in words.items():
+                assert adam_ref.same_bits(after[sl], want[name]).all(), (s, i, name, after[sl].tolist(), want[name].tolist())
 
 
 def test_tracking_loop_recovers_a_perturbed_pose(hip):
