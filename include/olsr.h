@@ -24,7 +24,8 @@
  * their size / introspection / profiling helpers — SURVEY.md section 8 rows a-e), then the callers and
  * data either side of it (rows f1-f3): olsr_mapping_loss, olsr_tracking_loss, olsr_pose_step,
  * olsr_accumulate_gradients, olsr_sparse_exchange_mask / _pack / _unpack, olsr_adam_step (and its per-group form
- * olsr_adam_step_groups), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2.
+ * olsr_adam_step_groups), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2,
+ * olsr_keyframe_seed_plan / _finish (a keyframe's new Gaussians from its RGB-D image).
  */
 #ifndef OLSR_H_INCLUDED
 #define OLSR_H_INCLUDED
@@ -500,6 +501,69 @@ int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_par
  * to the host twice). */
 size_t olsr_knn_scratch_bytes(int32_t P);
 int olsr_knn_mean_dist2(int32_t P, const float *points, float *mean_dist2, void *scratch, void *hip_stream);
+
+/* ---- keyframe seeding: the rows of a keyframe's new Gaussians from its RGB-D image (csrc/k_keyframe_seed.hip) ----------
+ * Replaces FrontEnd.add_new_keyframe (utils/slam_frontend.py:106-132) + BackEnd.add_next_kf (utils/slam_backend.py:187-202)
+ * -> GaussianModel.extend_from_pcd_seq -> create_pcd_from_image / create_pcd_from_image_and_depth
+ * (gaussian_splatting/scene/gaussian_model.py:135-281), which copy image and depth to the host, go through Open3D
+ * (create_from_color_and_depth, create_from_rgbd_image, random_down_sample), take np.median(depth) on the host and copy the
+ * points back for distCUDA2.  Here: plan (dependent launches, no host read, no atomics on data — the radix histograms are
+ * integer atomics, order-independent), ONE host read of status[1] = n_keep by the caller, finish.
+ *
+ * olsr_keyframe_seed_plan, with i = v W + u the pixel index, image [3,H,W] (planes plane_stride floats apart), depth [H,W]:
+ *  1. validity   rgb_ok = ((r + g) + b) > rgb_boundary_threshold on the raw image; d' = rgb_ok ? depth : 0; a pixel is VALID
+ *                iff 0 < d' < depth_trunc in float32 (NaN, negative and +inf depths are invalid).  status[0] = n_valid.
+ *  2. median     of d' over ALL W H pixels, zeros included (np.median(depth), gaussian_model.py:204), by a radix select on the
+ *                float bits: odd count -> the middle element, even count -> fl32(fl32(a + b) / 2) of the two middle ones.
+ *                DEVIATION: a non-finite or negative d' counts as 0 (numpy would return NaN).
+ *                point size ps = adaptive_pointsize ? (float) min(0.05, point_size * (double) median) : (float) point_size —
+ *                the product in double, narrowed once, as numpy 1.x (the reference's environment) evaluates
+ *                python_float * np.float32.  aux = {median, ps, 0, 0}.
+ *  3. sample     n_keep = (int32)((double) n_valid * (1.0 / downsample)) (the count rule of Open3D's random_down_sample as
+ *                this project states it); status[1] = n_keep.  Pixel i has the key fmix32(i ^ (seed * 0x9E3779B9)), fmix32 =
+ *                murmur3's finaliser (x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16, mod 2^32):
+ *                a bijection, so no two pixels tie.  Kept: the n_keep valid pixels with the smallest keys, emitted in PIXEL
+ *                ORDER; pix_index[k] = i.  DEVIATION: Open3D's shuffle (and its order of the sample) is not reproduced.
+ *  4. colour     c = clamp(exp(a) img + b, 0, 1) in float32 — the library's pinned exp, product and sum rounded separately —
+ *                or img itself when exposure == NULL; byte = (uint8)(c * 255) (truncation); colour = (float) byte / 255.0f;
+ *                shs[k, 0, :] = (colour - 0.5f) / (float) 0.28209479177387814 (RGB2SH), shs[k, 1:, :] = 0.
+ *  5. position   in double, as Open3D back-projects: z = d', x = (u - cx) z / fx, y = (v - cy) z / fy; world = Rt (p - t) with
+ *                R, t the float32 entries of w2c (row-major world-to-camera) widened to double, component k =
+ *                (R0k q0 + R1k q1) + R2k q2, q = p - t, no FMA contraction; narrowed to float32 once (the reference's
+ *                .float()).  DEVIATION: the reference inverts the 4x4 in Eigen; Rt (p - t) is the contract here.
+ *  6. constants  rotations (1, 0, 0, 0), opacities 0.0f = inverse_sigmoid(0.5).
+ * olsr_keyframe_seed_finish(n = status[1]): olsr_knn_mean_dist2 over the n new points alone, then
+ * scales[k, 0:3] = logf(sqrtf(max(d2, 1e-7f) * ps)).  DEVIATION: with n < 4 distCUDA2 has no three neighbours; finish then
+ * returns OLSR_OK and writes nothing, and the caller appends nothing.
+ * The monocular branch of the reference (random synthetic depth, gaussian_model.py:163-169) is not part of this entry.
+ * rows: staging of `capacity` rows (means3D, shs [capacity, M, 3], opacities, scales, rotations; the other members are not
+ * read); capacity >= (W H) / downsample always holds n_keep, so the caller sizes it without a host read.  scratch:
+ * olsr_keyframe_seed_scratch_bytes(W, H), the same buffer for plan and finish; knn_scratch: olsr_knn_scratch_bytes(n).
+ * OLSR_ERR_ARG before anything touches the device: a NULL pointer (exposure excepted); W, H or downsample <= 0;
+ * plane_stride < W H; capacity < W H / downsample; M < 1; fx or fy not finite or not positive; depth_trunc <= 0;
+ * finish: n < 0 or n > capacity. */
+typedef struct olsr_keyframe_seed_params {
+  int32_t W, H;                 /* image size */
+  int64_t plane_stride;         /* floats between the three colour planes */
+  int32_t M;                    /* SH coefficients per channel, (max_sh_degree + 1)^2 */
+  int32_t downsample;           /* pcd_downsample or pcd_downsample_init: the caller chooses */
+  uint32_t seed;                /* seed of the sampling hash */
+  int32_t _pad0;
+  double fx, fy, cx, cy;        /* intrinsics */
+  float rgb_boundary_threshold; /* rgb-validity threshold */
+  float depth_trunc;            /* the reference passes 100 */
+  double point_size;            /* configured point size */
+  int32_t adaptive_pointsize;   /* 0 or 1 */
+  int32_t capacity;             /* rows the staging buffers (and pix_index) hold */
+} olsr_keyframe_seed_params;
+size_t olsr_keyframe_seed_scratch_bytes(int32_t W, int32_t H);
+int olsr_keyframe_seed_plan(const olsr_keyframe_seed_params *p, const float *image, const float *depth,
+                            const float *exposure /* device float[2] {a, b} or NULL */,
+                            const float *w2c /* device float[16], row-major world-to-camera */, const olsr_map_buffers *rows,
+                            int32_t *pix_index /* [capacity] */, void *scratch, int32_t *status /* int32[8] */,
+                            float *aux /* float[4] {median, point_size, 0, 0} */, void *hip_stream);
+int olsr_keyframe_seed_finish(const olsr_keyframe_seed_params *p, int32_t n, const olsr_map_buffers *rows, const float *aux,
+                              void *scratch, void *knn_scratch, void *hip_stream);
 
 /* ---- caller side of the path -----------------------------------------
  * Mapping loss of one view and its gradient with respect to the rendered images, in one pass over the

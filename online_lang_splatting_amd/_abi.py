@@ -117,6 +117,15 @@ class OlsrMapEditParams(C.Structure):
                 ("max_grad", C.c_float), ("min_opacity", C.c_float), ("clone_max_scale", C.c_float), ("big_scale", C.c_float)]
 
 
+class OlsrKeyframeSeedParams(C.Structure):
+    """struct olsr_keyframe_seed_params, include/olsr.h."""
+
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("plane_stride", C.c_int64), ("M", C.c_int32), ("downsample", C.c_int32),
+                ("seed", C.c_uint32), ("_pad0", C.c_int32), ("fx", C.c_double), ("fy", C.c_double), ("cx", C.c_double),
+                ("cy", C.c_double), ("rgb_boundary_threshold", C.c_float), ("depth_trunc", C.c_float),
+                ("point_size", C.c_double), ("adaptive_pointsize", C.c_int32), ("capacity", C.c_int32)]
+
+
 class OlsrPoseParams(C.Structure):
     """struct olsr_pose_params, include/olsr.h."""
 

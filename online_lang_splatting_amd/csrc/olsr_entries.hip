@@ -1,8 +1,9 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, TSDF fusion, point-cloud metrics.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, TSDF fusion, point-cloud metrics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <cmath>
 #include <cstring>
 #include <vector>
 
@@ -455,6 +456,50 @@ int olsr_map_edit_apply(int32_t P, int32_t M, int32_t F, const olsr_map_edit_par
   launch_map_edit_apply(P, M, F, *params, *src, z, append, scratch, status, dst_capacity, *dst, src_index,
                         (hipStream_t)hip_stream);
   return launch_check("map_edit_apply");
+}
+
+size_t olsr_keyframe_seed_scratch_bytes(int32_t W, int32_t H) { return keyframe_seed_scratch_bytes(W, H); }
+
+// what is wrong with the parameters of a keyframe seeding, if anything
+static const char* keyframe_seed_params_error(const olsr_keyframe_seed_params* p) {
+  if (!p) return "params are required";
+  if (p->W <= 0 || p->H <= 0) return "W and H must be > 0";
+  if (p->downsample <= 0) return "downsample must be > 0";
+  const int64_t N = (int64_t)p->W * (int64_t)p->H;
+  if (N > (int64_t)0x7FFFFFFF) return "W * H must fit an int32";
+  if (p->plane_stride < N) return "plane_stride must be >= W * H";
+  if (p->M < 1) return "M must be >= 1";
+  if ((int64_t)p->capacity < N / p->downsample) return "capacity must be >= W * H / downsample";
+  if (!(p->fx > 0.0) || !(p->fy > 0.0) || !std::isfinite(p->fx) || !std::isfinite(p->fy)) return "fx and fy must be finite and > 0";
+  if (!(p->depth_trunc > 0.0f)) return "depth_trunc must be > 0";
+  return nullptr;
+}
+
+int olsr_keyframe_seed_plan(const olsr_keyframe_seed_params* p, const float* image, const float* depth, const float* exposure,
+                            const float* w2c, const olsr_map_buffers* rows, int32_t* pix_index, void* scratch,
+                            int32_t* status, float* aux, void* hip_stream) {
+  if (const char* e = keyframe_seed_params_error(p)) return fail(OLSR_ERR_ARG, std::string("keyframe_seed_plan: ") + e);
+  if (!image || !depth || !w2c || !rows || !pix_index || !scratch || !status || !aux)
+    return fail(OLSR_ERR_ARG, "keyframe_seed_plan: image, depth, w2c, rows, pix_index, scratch, status and aux are required");
+  if (!rows->means3D || !rows->shs || !rows->opacities || !rows->scales || !rows->rotations)
+    return fail(OLSR_ERR_ARG, "keyframe_seed_plan: the staging rows need means3D, shs, opacities, scales and rotations");
+  const int e = launch_keyframe_seed_plan(*p, image, depth, exposure, w2c, *rows, pix_index, scratch, status, aux,
+                                          (hipStream_t)hip_stream);
+  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("keyframe_seed_plan: ") + hipGetErrorString((hipError_t)e));
+  return launch_check("keyframe_seed_plan");
+}
+
+int olsr_keyframe_seed_finish(const olsr_keyframe_seed_params* p, int32_t n, const olsr_map_buffers* rows, const float* aux,
+                              void* scratch, void* knn_scratch, void* hip_stream) {
+  if (const char* e = keyframe_seed_params_error(p)) return fail(OLSR_ERR_ARG, std::string("keyframe_seed_finish: ") + e);
+  if (n < 0 || n > p->capacity || (int64_t)n > (int64_t)p->W * p->H)
+    return fail(OLSR_ERR_ARG, "keyframe_seed_finish: n must lie in 0 ... min(capacity, W * H)");
+  if (!rows || !aux || !scratch) return fail(OLSR_ERR_ARG, "keyframe_seed_finish: rows, aux and scratch are required");
+  if (!rows->means3D || !rows->scales) return fail(OLSR_ERR_ARG, "keyframe_seed_finish: the staging rows need means3D and scales");
+  if (n < 4) return OLSR_OK;   // no three neighbours: nothing is written, the caller appends nothing
+  if (!knn_scratch) return fail(OLSR_ERR_ARG, "keyframe_seed_finish: knn_scratch is required");
+  launch_keyframe_seed_finish(*p, n, *rows, aux, scratch, knn_scratch, (hipStream_t)hip_stream);
+  return launch_check("keyframe_seed_finish");
 }
 
 // what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)

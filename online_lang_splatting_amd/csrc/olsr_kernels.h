@@ -234,6 +234,14 @@ void launch_map_edit_apply(int P, int M, int F, const olsr_map_edit_params& p, c
                            const olsr_map_buffers* append, const void* scratch, const int32_t* status, int dst_capacity,
                            const olsr_map_buffers& dst, int32_t* src_index, hipStream_t st);
 
+// k_keyframe_seed.hip (plan: 0, or the HIP error of its memset)
+size_t keyframe_seed_scratch_bytes(int W, int H);
+int launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* image, const float* depth,
+                              const float* exposure, const float* w2c, const olsr_map_buffers& rows, int32_t* pix_index,
+                              void* scratch, int32_t* status, float* aux, hipStream_t st);
+void launch_keyframe_seed_finish(const olsr_keyframe_seed_params& p, int n, const olsr_map_buffers& rows, const float* aux,
+                                 void* scratch, void* knn_scratch, hipStream_t st);
+
 // k_pose.hip
 void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,
                       float* state, int32_t* status, const int32_t* frame_status, hipStream_t st);

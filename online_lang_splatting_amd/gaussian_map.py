@@ -288,7 +288,7 @@ class GaussianMap:
     `map.params` again after one.  Method names and arguments follow GaussianModel's.
 
     Host synchronisation: exactly one 4-byte read per topology edit (the new P, which sizes the destination: densify_and_prune,
-    prune_points, covisibility_prune, extend); statistics, resets and Adam steps read nothing back."""
+    prune_points, covisibility_prune, extend, extend_from_rgbd); statistics, resets and Adam steps read nothing back."""
 
     PARAM_ROWS = dict(means3D=(3,), opacities=(1,), scales=(3,), rotations=(4,))
 
@@ -388,7 +388,9 @@ class GaussianMap:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- the edit primitive ----
-    def _edit(self, ep: _abi.OlsrMapEditParams, drop_mask=None, z=None, append=None):
+    def _edit(self, ep: _abi.OlsrMapEditParams, drop_mask=None, z=None, append=None, P_new: Optional[int] = None):
+        """P_new: the size after the edit when the caller knows it (a pure append: P + n) — the plan's status is then not
+        read back and the edit makes no host synchronisation of its own."""
         L, P = lib(), self.P
         need = int(L.olsr_map_edit_scratch_bytes(P))
         if self._scratch.numel() < need:
@@ -396,7 +398,8 @@ class GaussianMap:
         src = self._struct(self._bufs[self._front])
         check(L.olsr_map_edit_plan(P, C.byref(ep), C.byref(src), drop_mask.data_ptr() if drop_mask is not None else None,
                                    self._scratch.data_ptr(), self.status.data_ptr(), self._stream()))
-        P_new = int(self.status[0].item())   # the edit's one host synchronisation: the destination's size
+        if P_new is None:
+            P_new = int(self.status[0].item())   # the edit's one host synchronisation: the destination's size
         back = 1 - self._front
         if self._bufs[back] is None or self._bufs[back]["cap"] < P_new:
             self._bufs[back] = None
@@ -437,9 +440,10 @@ class GaussianMap:
         ep = _abi.OlsrMapEditParams(mode=_abi.MAP_EDIT_MASK)
         return self._edit(ep, drop_mask=mask)
 
-    def extend(self, means3D, shs, opacities, scales, rotations, kf_id: int):
+    def extend(self, means3D, shs, opacities, scales, rotations, kf_id: int, _known_size=False):
         """GaussianModel.extend_from_pcd with ready rows: language zero, kfID = kf_id, n_obs 0, zero moments; the
-        accumulators of every row are zeroed (densification_postfix)."""
+        accumulators of every row are zeroed (densification_postfix).  (_known_size: an append drops no row, so P_new =
+        P + n needs no read of the plan's status — extend_from_rgbd, whose one host read has already happened.)"""
         n = int(means3D.shape[0])
         f32 = dict(device=self.device, dtype=torch.float32)
         app = dict(means3D=means3D.to(**f32).reshape(n, 3).contiguous(),
@@ -447,7 +451,27 @@ class GaussianMap:
                    opacities=opacities.to(**f32).reshape(n).contiguous(), scales=scales.to(**f32).reshape(n, 3).contiguous(),
                    rotations=rotations.to(**f32).reshape(n, 4).contiguous())
         ep = _abi.OlsrMapEditParams(mode=_abi.MAP_EDIT_MASK, n_append=n, append_kf_id=int(kf_id))
-        return self._edit(ep, append=app)
+        return self._edit(ep, append=app, P_new=self.P + n if _known_size else None)
+
+    def extend_from_rgbd(self, image, depth, w2c, intrinsics, kf_id: int, *, init=False, downsample: Optional[int] = None,
+                         seed: Optional[int] = None, exposure=None, rgb_boundary_threshold=0.01, point_size=0.05,
+                         adaptive_pointsize=True):
+        """GaussianModel.extend_from_pcd_seq — FrontEnd.add_new_keyframe + BackEnd.add_next_kf of the reference: the rows
+        of the keyframe's new Gaussians from its RGB-D image (keyframe_seed.seed_rows, on the device), then `extend`.
+        downsample: Dataset.pcd_downsample_init = 32 when `init`, else pcd_downsample = 64 (configs/rgbd/base_config.yaml:
+        11-12); seed of the sampling hash: kf_id.  One host read in all (the number of new rows).  Returns src_index
+        (int32 [P_new]: the old rows 0 .. P - 1, then -(k + 1) for new row k).  When the frame yields fewer than four rows
+        (no three neighbours for their scales) nothing is appended and the map is left as it is."""
+        from .keyframe_seed import seed_rows
+        if downsample is None:
+            downsample = 32 if init else 64
+        rows = seed_rows(image, depth, w2c, intrinsics, downsample=int(downsample), seed=int(kf_id if seed is None else seed),
+                         exposure=exposure, rgb_boundary_threshold=rgb_boundary_threshold, point_size=point_size,
+                         adaptive_pointsize=adaptive_pointsize, M=max(self.M, 1))
+        if int(rows["means3D"].shape[0]) == 0:
+            return torch.arange(self.P, dtype=torch.int32, device=self.device)
+        return self.extend(rows["means3D"], rows["shs"], rows["opacities"], rows["scales"], rows["rotations"], kf_id,
+                           _known_size=True)
 
     def covisibility_prune(self, visibilities: Sequence[torch.Tensor], window: Sequence[int], mode="slam"):
         """The back end's co-visibility prune of a full window (slam_backend.py:683-716): n_obs = the number of window views
