@@ -820,6 +820,55 @@ int olsr_lang_encoder_encode(const olsr_lang_encoder_params *params, int32_t N, 
                              const float *encoder_params, const float *online_params, float *features32,
                              float *codes, void *hip_stream);
 
+/* ---- the high-resolution language feature net (language/supervisedNet.py:6-109, utils/slam_backend.py:547-555) ------------
+ * The stage between the CLIP backbone and olsr_lang_encoder_encode: HighResLanguageFeatureNet in eval() turns the backbone's
+ * maps fv = clip_vis_dense [768,h,w], f3 = res3 [384,h3,w3] and f2 = res2 [192,h2,w2] into the [768,8h,8w] map the encoder
+ * reads.  Forward only, exact float32 on v_mfma_f32_16x16x4_f32, thirteen launches of one implicit-GEMM convolution kernel:
+ *    0 initial_conv     3x3 768 -> 512, BN, ReLU                                    [512,h,w]
+ *    1 upsample1        ConvTranspose2d(4, 2, 1) 512 -> 512, BN, ReLU               [512,2h,2w]
+ *    2 fusion1 align    bilinear(f3 -> 2h x 2w, align_corners = False), 1x1 384 -> 512
+ *    3 fusion1 fusion   3x3 over (upsample1 | align) 1024 -> 512, BN, ReLU  = fused
+ *    4 fusion1 att.0    3x3 512 -> 512, BN, ReLU
+ *    5 fusion1 att.3    1x1 512 -> 512, fused * sigmoid(.) + fused (one fmaf)
+ *    6 upsample2        ConvTranspose2d 512 -> 256, BN, ReLU                        [256,4h,4w]
+ *    7..10 fusion2      as 2..5 with f2 (192) and 256 channels
+ *   11 upsample3        ConvTranspose2d 256 -> 128, BN, ReLU                        [128,8h,8w]
+ *   12 final_conv       1x1 128 -> 768                                              [768,8h,8w]
+ * The resize is sampled while the 1x1's input is staged and the concatenation is two sources walked one after the other along
+ * K: neither copy exists.  A ConvTranspose2d runs as its four output parities, each a 2x2 convolution.  BatchNorm2d is its
+ * running statistics, alpha = weight / sqrt(running_var + bn_eps), beta = bias - running_mean alpha, folded in double and
+ * rounded once in the producing launch's epilogue, applied as relu(fmaf(alpha, conv + bias, beta)); ReLU keeps a NaN.  The K
+ * order of every output is fixed (chunks of 32 input channels in order, the taps in order inside a chunk), there are no
+ * atomics and no split K: a value depends on its own receptive field only and a call is bit-reproducible.
+ *   fv, f3, f2      device float, channel planes of h w (h3 w3, h2 w2) contiguous pixels, *_stride >= that many elements apart:
+ *                   a [1,C,.,.] tensor or one item of a batch, read in place; no alignment is assumed and nothing beyond a
+ *                   plane's last pixel is read.  channels x stride must stay below 2^31.
+ *   packed_params   device float[OLSR_HR_NET_PARAMS], 16-byte aligned.  The module's layers in the order of the list above,
+ *                   each as   weight: taps x [out][in]  |  bias [out]  |  BatchNorm weight, bias, running_mean, running_var
+ *                   [4][out] (the six layers that have one)   with the weight regrouped so that a tap's [out][in] slab is
+ *                   contiguous: Conv2d's [out,in,kh,kw] as slab kh * kw_count + kw, ConvTranspose2d's [in,out,4,4] as slab
+ *                   4 ky + kx, transposed to [out][in].  The fusion layers' in runs over the concatenation (high | low).
+ *   workspace       device, 16-byte aligned, olsr_hr_net_workspace_bytes bytes: the intermediates.  The library allocates
+ *                   nothing.  workspace_bytes in the struct is what the caller provides.
+ *   out             device float [768] planes of 8h x 8w pixels, out_stride >= 64 h w elements apart
+ *   launches        0: all thirteen.  Otherwise bit k selects launch k of the list (for timing single launches; the others'
+ *                   outputs are whatever the workspace holds).
+ * Enqueues on hip_stream, reads nothing back and does not synchronise. */
+#define OLSR_HR_NET_PARAMS 19890816
+#define OLSR_HR_NET_LAUNCHES 13
+typedef struct olsr_hr_net_params {
+  int32_t h, w, h3, w3, h2, w2;           /* the sizes of fv, f3, f2 */
+  int32_t c_fv, c_f3, c_f2, c_out;        /* this build: 768, 384, 192, 768 */
+  uint32_t launches;
+  int32_t _pad0;
+  int64_t fv_stride, f3_stride, f2_stride, out_stride; /* elements between two channel planes */
+  double bn_eps;                          /* BatchNorm2d's eps: 1e-5 */
+  uint64_t workspace_bytes;
+} olsr_hr_net_params;
+size_t olsr_hr_net_workspace_bytes(int32_t h, int32_t w, int32_t h3, int32_t w3, int32_t h2, int32_t w2); /* 0: bad sizes */
+int olsr_hr_net_forward(const olsr_hr_net_params *params, const float *fv, const float *f3, const float *f2,
+                        const float *packed_params, void *workspace, float *out, void *hip_stream);
+
 /* ---- TSDF fusion of depth and language maps into a 3-D map (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) ---------------
  * The reference's 3-D evaluation fuses, per keyframe, a depth image and a feature image (packed 8-bit colour in fusion.py, 3
  * float channels in fusion2.py, 15 in fusion3.py) into a truncated signed distance volume with one CUDA launch per frame, 16

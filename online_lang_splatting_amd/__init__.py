@@ -14,12 +14,13 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # n
 from .renderer import render  # noqa: F401,E402  (the caller-side façade: gaussian_renderer.render)
 from .lang_query import LanguageDecoder, LanguageQuery  # noqa: F401,E402  (text queries on a rendered language map)
 from .lang_encoder import LanguageEncoder  # noqa: F401,E402  (the general encoder 768 -> 32 ahead of the online autoencoder)
+from .hr_net import HighResLanguageNet  # noqa: F401,E402  (the high-resolution feature net ahead of that encoder)
 from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and language maps into a 3-D map)
 from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_distance,  # noqa: F401,E402  (the 3-D evaluation's
                             emd_segments, evaluate_classes)                            # Chamfer and earth mover's distances)
 from .keyframe_seed import seed_rows  # noqa: F401,E402  (a keyframe's new Gaussians from its RGB-D image, on the device)
 
-__all__ = ["render", "seed_rows", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "seed_rows", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

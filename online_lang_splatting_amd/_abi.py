@@ -189,6 +189,53 @@ class OlsrLangEncoderParams(C.Structure):
                 ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
 
 
+# the high-resolution language feature net (OLSR_HR_NET_*): HighResLanguageFeatureNet's layers in forward order as
+# (module path, kind, out, in, BatchNorm path or None); kind "conv1" / "conv3" is nn.Conv2d [out,in,k,k], "convT" is
+# nn.ConvTranspose2d(4, 2, 1) [in,out,4,4].  The packed array holds, per layer, taps x [out][in] | bias | BatchNorm [4][out].
+HR_NET_PARAMS = 19890816
+HR_NET_LAUNCHES = 13
+HR_NET_CHANNELS = (768, 384, 192, 768)   # fv, f3, f2, out
+HR_NET_TAPS = {"conv1": 1, "conv3": 9, "convT": 16}
+HR_NET_LAYERS = (
+    ("initial_conv.0", "conv3", 512, 768, "initial_conv.1"),
+    ("upsample1.0", "convT", 512, 512, "upsample1.1"),
+    ("attention_fusion1.low_res_align", "conv1", 512, 384, None),
+    ("attention_fusion1.fusion.0", "conv3", 512, 1024, "attention_fusion1.fusion.1"),
+    ("attention_fusion1.attention.0", "conv3", 512, 512, "attention_fusion1.attention.1"),
+    ("attention_fusion1.attention.3", "conv1", 512, 512, None),
+    ("upsample2.0", "convT", 256, 512, "upsample2.1"),
+    ("attention_fusion2.low_res_align", "conv1", 256, 192, None),
+    ("attention_fusion2.fusion.0", "conv3", 256, 512, "attention_fusion2.fusion.1"),
+    ("attention_fusion2.attention.0", "conv3", 256, 256, "attention_fusion2.attention.1"),
+    ("attention_fusion2.attention.3", "conv1", 256, 256, None),
+    ("upsample3.0", "convT", 128, 256, "upsample3.1"),
+    ("final_conv", "conv1", 768, 128, None),
+)
+HR_NET_BN_FIELDS = ("weight", "bias", "running_mean", "running_var")
+
+
+def _hr_net_state():
+    out = []
+    for path, kind, o, i, bn in HR_NET_LAYERS:
+        k = {"conv1": 1, "conv3": 3, "convT": 4}[kind]
+        out += [(f"{path}.weight", (i, o, k, k) if kind == "convT" else (o, i, k, k)), (f"{path}.bias", (o,))]
+        if bn:
+            out += [(f"{bn}.{n}", (o,)) for n in HR_NET_BN_FIELDS]
+    return tuple(out)
+
+
+HR_NET_STATE = _hr_net_state()   # state_dict order of the module, without num_batches_tracked
+
+
+class OlsrHrNetParams(C.Structure):
+    """struct olsr_hr_net_params, include/olsr.h."""
+
+    _fields_ = [(n, C.c_int32) for n in ("h", "w", "h3", "w3", "h2", "w2", "c_fv", "c_f3", "c_f2", "c_out")] + [
+        ("launches", C.c_uint32), ("_pad0", C.c_int32)] + [
+        (n, C.c_int64) for n in ("fv_stride", "f3_stride", "f2_stride", "out_stride")] + [
+        ("bn_eps", C.c_double), ("workspace_bytes", C.c_uint64)]
+
+
 # point-cloud metrics (OLSR_CLOUD_*)
 CLOUD_MAX_SEGMENTS = 32767
 

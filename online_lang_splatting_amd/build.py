@@ -41,6 +41,7 @@ UNITS = [
     ("k_lang_ae.hip", "k_lang_ae.o", []),
     ("k_lang_query.hip", "k_lang_query.o", []),
     ("k_lang_encoder.hip", "k_lang_encoder.o", []),
+    ("k_hr_net.hip", "k_hr_net.o", []),
     ("k_knn.hip", "k_knn.o", []),
     ("k_adam.hip", "k_adam.o", []),
     ("k_map_edit.hip", "k_map_edit.o", []),

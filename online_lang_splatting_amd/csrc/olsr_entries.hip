@@ -358,6 +358,35 @@ int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const
   return launch_check("lang_encoder_encode");
 }
 
+size_t olsr_hr_net_workspace_bytes(int32_t h, int32_t w, int32_t h3, int32_t w3, int32_t h2, int32_t w2) {
+  if (h < 1 || w < 1 || h3 < 1 || w3 < 1 || h2 < 1 || w2 < 1) return 0;
+  return hr_net_workspace_bytes(h, w);  // f3 and f2 are sampled in place: their sizes add nothing
+}
+
+int olsr_hr_net_forward(const olsr_hr_net_params* p, const float* fv, const float* f3, const float* f2, const float* packed_params,
+                        void* workspace, float* out, void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "hr_net_forward: the parameter struct is NULL");
+  if (p->c_fv != 768 || p->c_f3 != 384 || p->c_f2 != 192 || p->c_out != 768)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: this build has the channel widths fv 768, f3 384, f2 192, out 768 only");
+  if (p->h < 1 || p->w < 1 || p->h3 < 1 || p->w3 < 1 || p->h2 < 1 || p->w2 < 1)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: every size must be positive");
+  const int64_t n = (int64_t)p->h * p->w, n3 = (int64_t)p->h3 * p->w3, n2 = (int64_t)p->h2 * p->w2, lim = (int64_t)1 << 31;
+  if (p->fv_stride < n || p->f3_stride < n3 || p->f2_stride < n2 || p->out_stride < 64 * n)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: a plane stride is smaller than its plane");
+  if (p->fv_stride >= lim / 768 || p->f3_stride >= lim / 384 || p->f2_stride >= lim / 192 || p->out_stride >= lim / 768)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: channels x plane stride must stay below 2^31 elements");
+  if (!(p->bn_eps > 0.0)) return fail(OLSR_ERR_ARG, "hr_net_forward: bn_eps must be positive");
+  if (p->launches >> OLSR_HR_NET_LAUNCHES) return fail(OLSR_ERR_ARG, "hr_net_forward: launches names a launch that does not exist");
+  if (!fv || !f3 || !f2 || !packed_params || !workspace || !out)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: fv, f3, f2, packed_params, workspace and out are required");
+  if (((uintptr_t)packed_params | (uintptr_t)workspace) & 15u)
+    return fail(OLSR_ERR_ARG, "hr_net_forward: packed_params and workspace must be 16-byte aligned");
+  if (p->workspace_bytes < (uint64_t)hr_net_workspace_bytes(p->h, p->w))
+    return fail(OLSR_ERR_ARG, "hr_net_forward: the workspace is smaller than olsr_hr_net_workspace_bytes");
+  launch_hr_net(*p, fv, f3, f2, packed_params, (float*)workspace, out, (hipStream_t)hip_stream);
+  return launch_check("hr_net_forward");
+}
+
 int olsr_accumulate_gradients(int32_t P, int32_t M, int32_t F, int32_t assign, const float* dL_dmeans3D,
                               const float* dL_dsh,
                               const float* dL_dopacity, const float* dL_dscales, const float* dL_drotations,

@@ -287,6 +287,11 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
 hipError_t launch_lang_encoder(const olsr_lang_encoder_params& p, int N, const float* features, const float* params,
                                const float* online, float* features32, float* codes, hipStream_t st);
 
+// k_hr_net.hip: the high-resolution language feature net ahead of the encoder (include/olsr.h)
+size_t hr_net_workspace_bytes(long long h, long long w);
+void launch_hr_net(const olsr_hr_net_params& p, const float* fv, const float* f3, const float* f2, const float* packed,
+                   float* workspace, float* out, hipStream_t st);
+
 // k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface point cloud (include/olsr.h)
 void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st);
 void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_tsdf_view* views, hipStream_t st);

@@ -615,6 +615,13 @@ class OnlineLanguageTargets:
         self.last_loss = loss.clone()
         return self.targets[view_id]
 
+    def add_keyframe_backbone(self, view_id, fv: torch.Tensor, f3: torch.Tensor, f2: torch.Tensor, hr_net, encoder) -> torch.Tensor:
+        """fv [1,768,h/8,w/8], f3 [1,384,.,.], f2 [1,192,.,.]: the backbone's clip_vis_dense, res3 and res2 on the codec's
+        device; hr_net an hr_net.HighResLanguageNet, encoder a lang_encoder.LanguageEncoder.  The high-resolution net turns
+        them into the [1,768,h,w] map (a buffer of hr_net's, overwritten by its next call), then add_keyframe_hr on that map:
+        utils/slam_backend.py:547-576 from the backbone's three maps to the stored target.  -> the [15,h,w] target."""
+        return self.add_keyframe_hr(view_id, hr_net.forward(fv, f3, f2), encoder)
+
     def rehearse(self, view_ids: Sequence) -> None:
         """One train step on the stored features of each id; their targets stay as they are."""
         for v in view_ids:
