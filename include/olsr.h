@@ -25,7 +25,8 @@
  * data either side of it (rows f1-f3): olsr_mapping_loss, olsr_tracking_loss, olsr_pose_step,
  * olsr_accumulate_gradients, olsr_sparse_exchange_mask / _pack / _unpack, olsr_adam_step (and its per-group form
  * olsr_adam_step_groups), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2,
- * olsr_keyframe_seed_plan / _finish (a keyframe's new Gaussians from its RGB-D image).
+ * olsr_keyframe_seed_plan / _finish (a keyframe's new Gaussians from its RGB-D image), olsr_grad_mask, olsr_median_depth,
+ * olsr_covisibility and olsr_keyframe_decide (the front end's frame step around the tracking loop).
  */
 #ifndef OLSR_H_INCLUDED
 #define OLSR_H_INCLUDED
@@ -564,6 +565,95 @@ int olsr_keyframe_seed_plan(const olsr_keyframe_seed_params *p, const float *ima
                             float *aux /* float[4] {median, point_size, 0, 0} */, void *hip_stream);
 int olsr_keyframe_seed_finish(const olsr_keyframe_seed_params *p, int32_t n, const olsr_map_buffers *rows, const float *aux,
                               void *scratch, void *knn_scratch, void *hip_stream);
+
+/* ---- front end: the frame step around the tracking loop (csrc/k_frontend.hip) ------------------------------------------
+ * What the reference's front end does once per frame in PyTorch ops with host reads (utils/slam_frontend.py:577-676): the
+ * tracking mask (Camera.compute_grad_mask, utils/camera_utils.py:123-152), the median depth after tracking (get_median_depth,
+ * utils/slam_utils.py:168-179) and the keyframe test with the window policy (is_keyframe / add_to_window and the small-window
+ * rule, utils/slam_frontend.py:279-430, 633-645).  No float atomics; the radix histograms and the counts are integer atomics,
+ * order-independent: two runs give the same bits.  "Lower median" below is the element of rank (n - 1) / 2 in ascending order,
+ * which is what torch.median returns.  Every entry returns OLSR_ERR_ARG before anything touches the device for a NULL required
+ * pointer, a size <= 0, a size above 2^31 - 1, and what its own paragraph lists.
+ *
+ * olsr_grad_mask: image [3,H,W] (planes plane_stride floats apart, no alignment requirement) -> mask [H,W] float.
+ * Float32 statements, every operation rounded once (correctly rounded divide and sqrt, no FMA), in this order:
+ *   gray = ((r + g) + b) / 3.0f;  p = gray reflect-padded by 1 (index -1 -> 1, index n -> n - 2)
+ *   gv = (1/32) (((3 p[y-1,x-1] + 10 p[y-1,x]) + 3 p[y-1,x+1]) - ((3 p[y+1,x-1] + 10 p[y+1,x]) + 3 p[y+1,x+1]))
+ *   gh = (1/32) (((3 p[y-1,x-1] + 10 p[y,x-1]) + 3 p[y+1,x-1]) - ((3 p[y-1,x+1] + 10 p[y,x+1]) + 3 p[y+1,x+1]))
+ *   ok = all nine padded neighbours satisfy |p| > 0.01f;  I = ok ? sqrtf(gv gv + gh gh) : 0
+ * OLSR_GRAD_MASK_BLOCKS (the reference's `replica` branch): bh = H / 32, bw = W / 32; for r, c < 32 the block
+ *   [r bh, (r+1) bh) x [c bw, (c+1) bw) takes the lower median med of its intensities, th = med * edge_threshold, and each of
+ *   its pixels becomes (I > th && !(1.0f <= th)) ? 1 : 0 — the second term is the reference's two sequential masked writes,
+ *   which zero everything when th >= 1.  Pixels outside the 32 x 32 blocks keep the RAW INTENSITY I, as the reference leaves
+ *   them.  One launch, a workgroup per block, no scratch (scratch may be NULL).  OLSR_ERR_ARG: H or W < 32; a block of more
+ *   than 8192 pixels (a 4K frame has 8040), or one whose (bh + 3) (bw + 2) floats exceed 64 KiB of LDS.
+ * OLSR_GRAD_MASK_GLOBAL (every other dataset): mask = I > med_all * edge_threshold as 0 / 1 floats, med_all the lower median
+ *   of all W H intensities (radix select on the float bits).  scratch: olsr_frontend_scratch_bytes(W H).  OLSR_ERR_ARG: H or
+ *   W < 2 (reflect padding), scratch NULL.
+ * Both: OLSR_ERR_ARG for plane_stride < W H and an unknown mode.  An image with NaN or infinite values is outside the contract
+ * (the reference propagates NaN through its median).
+ *
+ * olsr_median_depth: get_median_depth(depth, opacity, mask) over N pixels.  A pixel is valid when depth > 0 && opacity > 0.95f
+ * && (mask == NULL || mask[i] != 0), mask uint8; a NaN depth is invalid (NaN > 0 is false), +inf is valid, as in the reference.
+ * median (device float[1]) = the lower median of the valid depths, count (device int32[1]) = how many there are.
+ * DEVIATION: with no valid pixel the reference raises; here the median is NaN and the count 0.  return_std is not built
+ * (nothing in the reference calls it).  scratch: olsr_frontend_scratch_bytes(N).
+ *
+ * olsr_covisibility: cur[i] = n_touched[i] > 0 over P Gaussians against K <= 16 keyframe visibilities (uint8 [P] each, nonzero
+ * = visible; window position 0 = the last keyframe).  counts (device int64[OLSR_COVIS_COUNTS]): counts[0] = |cur|,
+ * counts[1 + 2k] = |cur & vis_k|, counts[2 + 2k] = |vis_k|, the rest 0.  cur_out (uint8 [P] or NULL) receives cur — the new
+ * keyframe's occ_aware_visibility entry.  One pass over the K + 1 arrays.  OLSR_ERR_ARG: K outside 0 ... 16, vis[k] NULL, k < K.
+ *
+ * olsr_keyframe_decide: one wave; reads counts and the median word on the device, the tracked pose cur_pose (float[16],
+ * row-major world-to-camera, last row 0 0 0 1) and the K = window_len keyframe poses [K][16], and writes one record for the
+ * host: int32[8] followed by float[OLSR_KEYFRAME_RECORD_FLOATS].  The reference's logic, statement for statement:
+ *   t(A, B) = translation of A B^-1 = R_A c_B + t_A with c_B = -(R_B^-1 t_B), in double from the float32 entries: R^-1 =
+ *     cofactors * (1 / det), det = (r00 c00 + r01 c01) + r02 c02, sums left to right, no FMA; t narrowed to float32 once;
+ *     |t| = sqrtf((t0 t0 + t1 t1) + t2 t2) in float32.
+ *   dist = |t(cur, kf_0)|;  ratio_u = (float) inter_0 / (float) (|cur| + |vis_0| - inter_0)  (torch's int / int)
+ *   is_kf = (ratio_u < kf_overlap && dist > kf_min_translation * median) || dist > kf_translation * median  (float32 products)
+ *   create = is_kf;  if (window_len < window_size) create = check_time && ratio_u < kf_overlap;
+ *   if (single_thread) create = check_time && create.
+ * Window policy on [cur] + window (window position k is position k + 1 there, so "positions >= 2" are k >= 1):
+ *   cut_k = (float) inter_k / (float) min(|cur|, |vis_k|); the LAST k >= 1 with cut_k <= kf_cutoff is removed (removed_a).
+ *   If K + 1 - (one removed) > window_size: score_i = (double) sqrtf(|t(kf_i, cur)|) * sum over the remaining j >= 1, j != i,
+ *   ascending, of 1.0 / (double) (|t(kf_i, kf_j)| + 1e-6f), in double; the remaining i >= 1 with the largest score is removed
+ *   (removed_b; the first maximum wins, np.argmax).  Both removals can happen in one call.  They are computed whether or not
+ *   create is set; the caller commits them only when it is.  A union or minimum of 0 gives NaN, and every comparison with NaN
+ *   is false, as in torch.  K = 0: dist and ratio_u are NaN, is_kf = 0.  DEVIATION: with nothing left to score the reference's
+ *   np.argmax raises; here nothing is removed.
+ * record int32: {create, removals, removed_a (-1: none), removed_b (-1: none), is_kf, |cur|, inter_0, |vis_0|};
+ * record float: {dist, median, ratio_u, 0, cut_k [16], (float) score_k [16], 0 ...} (NaN where not computed).  The record has
+ * 40 floats, not 24: K = 16 needs 4 + 2 * 16.
+ * OLSR_ERR_ARG: window_len outside 0 ... 16, window_size < 1, kf_poses NULL with window_len > 0. */
+#define OLSR_GRAD_MASK_BLOCKS 0
+#define OLSR_GRAD_MASK_GLOBAL 1
+#define OLSR_GRAD_MASK_MAX_BLOCK_PIXELS 8192
+#define OLSR_COVIS_MAX_VIEWS 16
+#define OLSR_COVIS_COUNTS 33            /* 1 + 2 * OLSR_COVIS_MAX_VIEWS */
+#define OLSR_KEYFRAME_RECORD_FLOATS 40
+#define OLSR_KEYFRAME_RECORD_BYTES 192  /* int32[8] + float[40] */
+typedef struct olsr_covis_views {
+  int32_t K;                                 /* keyframes in the window, 0 ... 16 */
+  int32_t _pad0;
+  const uint8_t *vis[OLSR_COVIS_MAX_VIEWS];  /* device uint8 [P] each; entries from K on are not read */
+} olsr_covis_views;
+typedef struct olsr_keyframe_decide_params {
+  int32_t window_len;    /* K: keyframes in the window now */
+  int32_t window_size;   /* Training.window_size */
+  int32_t check_time;    /* (cur_frame_idx - last_keyframe_idx) >= kf_interval */
+  int32_t single_thread;
+  float kf_translation, kf_min_translation, kf_overlap, kf_cutoff;
+} olsr_keyframe_decide_params;
+size_t olsr_frontend_scratch_bytes(int64_t n);
+int olsr_grad_mask(int32_t W, int32_t H, int64_t plane_stride, int32_t mode, float edge_threshold, const float *image,
+                   float *mask, void *scratch, void *hip_stream);
+int olsr_median_depth(int64_t N, const float *depth, const float *opacity, const uint8_t *mask /* or NULL */, void *scratch,
+                      float *median, int32_t *count, void *hip_stream);
+int olsr_covisibility(int64_t P, const int32_t *n_touched, const olsr_covis_views *views, uint8_t *cur_out /* or NULL */,
+                      int64_t *counts, void *hip_stream);
+int olsr_keyframe_decide(const olsr_keyframe_decide_params *p, const int64_t *counts, const float *median,
+                         const float *cur_pose, const float *kf_poses, void *record, void *hip_stream);
 
 /* ---- caller side of the path -----------------------------------------
  * Mapping loss of one view and its gradient with respect to the rendered images, in one pass over the

@@ -19,8 +19,9 @@ from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and langu
 from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_distance,  # noqa: F401,E402  (the 3-D evaluation's
                             emd_segments, evaluate_classes)                            # Chamfer and earth mover's distances)
 from .keyframe_seed import seed_rows  # noqa: F401,E402  (a keyframe's new Gaussians from its RGB-D image, on the device)
+from .frontend import KeyframeSelector, median_depth, tracking_mask  # noqa: F401,E402  (the front end's frame step)
 
-__all__ = ["render", "seed_rows", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

@@ -126,6 +126,24 @@ class OlsrKeyframeSeedParams(C.Structure):
                 ("point_size", C.c_double), ("adaptive_pointsize", C.c_int32), ("capacity", C.c_int32)]
 
 
+# the front end's frame step (OLSR_GRAD_MASK_*, OLSR_COVIS_*, OLSR_KEYFRAME_RECORD_*)
+GRAD_MASK_BLOCKS, GRAD_MASK_GLOBAL, GRAD_MASK_MAX_BLOCK_PIXELS = 0, 1, 8192
+COVIS_MAX_VIEWS, COVIS_COUNTS, KEYFRAME_RECORD_FLOATS, KEYFRAME_RECORD_BYTES = 16, 33, 40, 192
+
+
+class OlsrCovisViews(C.Structure):
+    """struct olsr_covis_views, include/olsr.h."""
+
+    _fields_ = [("K", C.c_int32), ("_pad0", C.c_int32), ("vis", C.c_void_p * COVIS_MAX_VIEWS)]
+
+
+class OlsrKeyframeDecideParams(C.Structure):
+    """struct olsr_keyframe_decide_params, include/olsr.h."""
+
+    _fields_ = [(n, C.c_int32) for n in ("window_len", "window_size", "check_time", "single_thread")] + [
+        (n, C.c_float) for n in ("kf_translation", "kf_min_translation", "kf_overlap", "kf_cutoff")]
+
+
 class OlsrPoseParams(C.Structure):
     """struct olsr_pose_params, include/olsr.h."""
 

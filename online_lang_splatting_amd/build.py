@@ -46,6 +46,7 @@ UNITS = [
     ("k_adam.hip", "k_adam.o", []),
     ("k_map_edit.hip", "k_map_edit.o", []),
     ("k_keyframe_seed.hip", "k_keyframe_seed.o", []),
+    ("k_frontend.hip", "k_frontend.o", []),
     ("k_pose.hip", "k_pose.o", []),
     ("k_tsdf.hip", "k_tsdf.o", []),
     ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),

@@ -1,5 +1,5 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, TSDF fusion, point-cloud metrics.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, TSDF fusion, point-cloud metrics.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -529,6 +529,65 @@ int olsr_keyframe_seed_finish(const olsr_keyframe_seed_params* p, int32_t n, con
   if (!knn_scratch) return fail(OLSR_ERR_ARG, "keyframe_seed_finish: knn_scratch is required");
   launch_keyframe_seed_finish(*p, n, *rows, aux, scratch, knn_scratch, (hipStream_t)hip_stream);
   return launch_check("keyframe_seed_finish");
+}
+
+size_t olsr_frontend_scratch_bytes(int64_t n) { return frontend_scratch_bytes(n); }
+
+int olsr_grad_mask(int32_t W, int32_t H, int64_t plane_stride, int32_t mode, float edge_threshold, const float* image,
+                   float* mask, void* scratch, void* hip_stream) {
+  if (W <= 0 || H <= 0) return fail(OLSR_ERR_ARG, "grad_mask: W and H must be > 0");
+  const int64_t N = (int64_t)W * (int64_t)H;
+  if (N > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "grad_mask: W * H must fit an int32");
+  if (plane_stride < N) return fail(OLSR_ERR_ARG, "grad_mask: plane_stride must be >= W * H");
+  if (!image || !mask) return fail(OLSR_ERR_ARG, "grad_mask: image and mask are required");
+  if (mode == OLSR_GRAD_MASK_BLOCKS) {
+    if (W < 32 || H < 32) return fail(OLSR_ERR_ARG, "grad_mask: block mode needs W and H >= 32");
+    const int64_t bh = H / 32, bw = W / 32;
+    if (bh * bw > OLSR_GRAD_MASK_MAX_BLOCK_PIXELS || (bh + 3) * (bw + 2) * (int64_t)sizeof(float) > 65536)
+      return fail(OLSR_ERR_ARG, "grad_mask: an image block may hold 8192 pixels and (H / 32 + 3) (W / 32 + 2) floats 64 KiB at most");
+  } else if (mode == OLSR_GRAD_MASK_GLOBAL) {
+    if (W < 2 || H < 2) return fail(OLSR_ERR_ARG, "grad_mask: W and H must be >= 2");
+    if (!scratch) return fail(OLSR_ERR_ARG, "grad_mask: global mode needs scratch");
+  } else {
+    return fail(OLSR_ERR_ARG, "grad_mask: mode must be OLSR_GRAD_MASK_BLOCKS or OLSR_GRAD_MASK_GLOBAL");
+  }
+  const int e = launch_grad_mask(W, H, plane_stride, mode, edge_threshold, image, mask, scratch, (hipStream_t)hip_stream);
+  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("grad_mask: ") + hipGetErrorString((hipError_t)e));
+  return launch_check("grad_mask");
+}
+
+int olsr_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch, float* median,
+                      int32_t* count, void* hip_stream) {
+  if (N <= 0 || N > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "median_depth: N must lie in 1 ... 2^31 - 1");
+  if (!depth || !opacity || !scratch || !median || !count)
+    return fail(OLSR_ERR_ARG, "median_depth: depth, opacity, scratch, median and count are required");
+  const int e = launch_median_depth(N, depth, opacity, mask, scratch, median, count, (hipStream_t)hip_stream);
+  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("median_depth: ") + hipGetErrorString((hipError_t)e));
+  return launch_check("median_depth");
+}
+
+int olsr_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views* views, uint8_t* cur_out, int64_t* counts,
+                      void* hip_stream) {
+  if (P <= 0 || P > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "covisibility: P must lie in 1 ... 2^31 - 1");
+  if (!n_touched || !views || !counts) return fail(OLSR_ERR_ARG, "covisibility: n_touched, views and counts are required");
+  if (views->K < 0 || views->K > OLSR_COVIS_MAX_VIEWS) return fail(OLSR_ERR_ARG, "covisibility: K must lie in 0 ... 16");
+  for (int k = 0; k < views->K; ++k)
+    if (!views->vis[k]) return fail(OLSR_ERR_ARG, "covisibility: a keyframe visibility is NULL");
+  const int e = launch_covisibility(P, n_touched, *views, cur_out, counts, (hipStream_t)hip_stream);
+  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("covisibility: ") + hipGetErrorString((hipError_t)e));
+  return launch_check("covisibility");
+}
+
+int olsr_keyframe_decide(const olsr_keyframe_decide_params* p, const int64_t* counts, const float* median,
+                         const float* cur_pose, const float* kf_poses, void* record, void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "keyframe_decide: params are required");
+  if (p->window_len < 0 || p->window_len > OLSR_COVIS_MAX_VIEWS)
+    return fail(OLSR_ERR_ARG, "keyframe_decide: window_len must lie in 0 ... 16");
+  if (p->window_size < 1) return fail(OLSR_ERR_ARG, "keyframe_decide: window_size must be >= 1");
+  if (!counts || !median || !cur_pose || !record || (p->window_len > 0 && !kf_poses))
+    return fail(OLSR_ERR_ARG, "keyframe_decide: counts, median, cur_pose, record and (window_len > 0) kf_poses are required");
+  launch_keyframe_decide(*p, counts, median, cur_pose, kf_poses, record, (hipStream_t)hip_stream);
+  return launch_check("keyframe_decide");
 }
 
 // what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)
