@@ -1,0 +1,60 @@
+"""A module's parameters as one flat float32 array in state_dict order: the views into it and the loader every language net
+shares (lang_codec, lang_query, lang_encoder; hr_net packs its weights itself and uses the unwrapping and the key check).
+
+table: ((state_dict name, shape), ...) of _abi; who: the module's name at the head of every message.
+"""
+from collections import OrderedDict
+
+CHECKPOINT_PREFIX = "model."   # AutoencoderLight / LangSupervisedNet keep the torch module as self.model
+
+
+def _numel(shape):
+    n = 1
+    for s_ in shape:
+        n *= s_
+    return n
+
+
+def views(flat, table, who, what):
+    """name -> view of `flat` in the module's shape, in table order.  what: the array's name in the message."""
+    total = sum(_numel(shape) for _, shape in table)
+    if flat.dim() != 1 or flat.numel() != total:
+        raise RuntimeError(f"{who}: the {what} has {total} elements, got {tuple(flat.shape)}")
+    out, off = OrderedDict(), 0
+    for name, shape in table:
+        n = _numel(shape)
+        out[name] = flat[off:off + n].view(shape)
+        off += n
+    return out
+
+
+def unwrap(state, who, prefix=CHECKPOINT_PREFIX, keep=""):
+    """A Lightning checkpoint ({"state_dict": {...}}), its state_dict or a plain state dict -> the entries under `prefix`
+    (if any key carries it) whose names start with `keep`, without num_batches_tracked."""
+    if not isinstance(state, dict):
+        raise RuntimeError(f"{who}: a checkpoint or state dict is expected, got {type(state).__name__}")
+    if "state_dict" in state and isinstance(state["state_dict"], dict):
+        state = state["state_dict"]
+    if any(k.startswith(prefix) for k in state):
+        state = {k[len(prefix):]: v for k, v in state.items() if k.startswith(prefix)}
+    return {k: v for k, v in state.items() if k.startswith(keep) and not k.endswith("num_batches_tracked")}
+
+
+def check_keys(state, table, who, what):
+    want = dict(table)
+    missing, extra = sorted(set(want) - set(state)), sorted(set(state) - set(want))
+    if missing or extra:
+        raise RuntimeError(f"{who}: {what} with missing keys {missing}, unexpected keys {extra}")
+    return want
+
+
+def load(flat, state, table, who, what, hint, prefix=None, keep=""):
+    """Copies `state` into `flat`; keys and shapes must be the table's.  what: (the array's name, the state's name) in the
+    messages; hint: why a shape is fixed.  prefix: unwrap a checkpoint first and keep the names that start with `keep`."""
+    if prefix is not None:
+        state = unwrap(state, who, prefix, keep)
+    for k, shape in check_keys(state, table, who, what[1]).items():
+        if tuple(state[k].shape) != tuple(shape):
+            raise RuntimeError(f"{who}: {k} has shape {tuple(state[k].shape)}, expected {tuple(shape)} ({hint})")
+    for k, v in views(flat, table, who, what[0]).items():
+        v.copy_(state[k].detach().to(device=flat.device, dtype=flat.dtype))

@@ -277,8 +277,8 @@ __global__ __launch_bounds__(FE_THREADS) void grad_threshold_kernel(int64_t N, f
   out[i] = bits2f(sc.keys[i]) > th ? 1.0f : 0.0f;
 }
 
-int launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float edge_threshold, const float* image, float* mask,
-                     void* scratch, hipStream_t st) {
+hipError_t launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float edge_threshold, const float* image,
+                            float* mask, void* scratch, hipStream_t st) {
   const int64_t N = (int64_t)W * H;
   if (mode == OLSR_GRAD_MASK_BLOCKS) {
     const int bh = H / FE_GRID_BLOCKS, bw = W / FE_GRID_BLOCKS;
@@ -286,15 +286,15 @@ int launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float edge_th
     const int grid = FE_GRID_BLOCKS * FE_GRID_BLOCKS + (int)((margin + FE_THREADS - 1) / FE_THREADS);
     const size_t lds = (size_t)grad_mask_block_floats(W, H) * sizeof(float);
     grad_mask_blocks_kernel<<<grid, FE_THREADS, lds, st>>>(W, H, plane_stride, edge_threshold, image, mask);
-    return 0;
+    return hipSuccess;
   }
   const FeScratch sc = fe_carve(scratch);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) return e;
   grad_intensity_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(W, H, plane_stride, image, sc);
   launch_select(N, sc, nullptr, nullptr, st);
   grad_threshold_kernel<<<(int)((N + FE_THREADS - 1) / FE_THREADS), FE_THREADS, 0, st>>>(N, edge_threshold, sc, mask);
-  return 0;
+  return hipSuccess;
 }
 
 // ---- median depth -------------------------------------------------------------------------------------------------------------
@@ -318,14 +318,14 @@ __global__ __launch_bounds__(FE_THREADS) void median_depth_keys_kernel(int64_t N
   select_flush(h, sc.hist);
 }
 
-int launch_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch, float* median,
-                        int32_t* count, hipStream_t st) {
+hipError_t launch_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch,
+                               float* median, int32_t* count, hipStream_t st) {
   const FeScratch sc = fe_carve(scratch);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) return e;
   median_depth_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(N, depth, opacity, mask, sc);
   launch_select(N, sc, median, count, st);
-  return 0;
+  return hipSuccess;
 }
 
 // ---- covisibility counts ------------------------------------------------------------------------------------------------------
@@ -370,14 +370,14 @@ __global__ __launch_bounds__(FE_THREADS) void covisibility_kernel(int64_t P, con
   if (t < 1 + 2 * v.K && s_c[t]) atomicAdd(&counts[t], (unsigned long long)s_c[t]);
 }
 
-int launch_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views& views, uint8_t* cur_out, int64_t* counts,
-                        hipStream_t st) {
+hipError_t launch_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views& views, uint8_t* cur_out,
+                               int64_t* counts, hipStream_t st) {
   const hipError_t e = hipMemsetAsync(counts, 0, (size_t)OLSR_COVIS_COUNTS * sizeof(int64_t), st);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) return e;
   const int64_t per = (int64_t)FE_THREADS * FE_COVIS_PER_THREAD;
   covisibility_kernel<<<(int)((P + per - 1) / per), FE_THREADS, 0, st>>>(P, n_touched, views, cur_out,
                                                                         reinterpret_cast<unsigned long long*>(counts));
-  return 0;
+  return hipSuccess;
 }
 
 // ---- the keyframe decision ----------------------------------------------------------------------------------------------------

@@ -9,7 +9,8 @@
 //                         one 16-byte load per lane and 16-deep k block straight from the packed array (a tap's [out][in] slab is
 //                         contiguous), the next block's load issued ahead of the current block's MFMAs; the activations are the
 //                         B operand out of an LDS image [pixel][32 channels + 4], double-buffered: the next chunk's global loads
-//                         are issued before the current chunk's MFMAs and stored behind them (k_lang_encoder.hip's layer 1).
+//                         are issued before the current chunk's MFMAs and stored behind them (k_lang_encoder.hip's layer 1).  Operand
+//                         layout and block: olsr_dense.h.
 //     TAPS  1x1           64 consecutive pixels of the flattened plane.
 //           3x3, pad 1    an 8 x 8 tile; a chunk of its 10 x 10 halo patch is staged once and the nine taps walk over it;
 //                         what lies outside the image is staged as zeros.
@@ -20,16 +21,15 @@
 //     SRC   one tensor; two tensors one after the other along K (torch.cat([high, low], 1) without the copy); or one tensor
 //           sampled bilinearly while it is staged (F.interpolate(mode='bilinear', align_corners=False) ahead of a 1x1: the
 //           resize comes first, as in the reference, and no resized copy exists).
-//     EPI   bias;  relu(fmaf(alpha, h, beta)) with BatchNorm2d's running statistics folded per channel as le_bn_fold does (in
+//     EPI   bias;  relu(fmaf(alpha, h, beta)) with BatchNorm2d's running statistics folded per channel as bn_fold does (in
 //           double, rounded once; ReLU keeps a NaN);  or the gate fused * sigmoid(h) + fused as one fmaf, reading fused once.
 // K order is fixed: chunks of 32 channels in order, inside a chunk the taps in order, inside a tap two 16-deep blocks.  No
 // atomics, no split K: a value depends on its own receptive field only and a call is bit-reproducible.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_dense.h"
 
 namespace olsr {
-
-typedef float hr_f4 __attribute__((ext_vector_type(4)));
 
 constexpr int HR_TP = 64;           // pixels per workgroup
 constexpr int HR_TN = 64;           // output channels per workgroup, 16 per wave
@@ -75,8 +75,6 @@ struct hr_conv_args {
   float* out;
   int out_ps, OUT;
 };
-
-__device__ __forceinline__ float hr_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
 
 template <int TAPS, int SRC, int EPI>
 __global__ __launch_bounds__(HR_THREADS) void hr_conv_kernel(const hr_conv_args a) {
@@ -181,14 +179,14 @@ __global__ __launch_bounds__(HR_THREADS) void hr_conv_kernel(const hr_conv_args 
   // ---- K loop ----------------------------------------------------------------------------------------------------------------
   const size_t slab_stride = (size_t)a.OUT * (size_t)IN;
   const float* wp = a.wt + (size_t)(n0 + li) * (size_t)IN + 4 * q;
-  hr_f4 acc[4];
+  f32x4 acc[1][4];
   {
-    const hr_f4 bv = *reinterpret_cast<const hr_f4*>(a.bias + n0 + 4 * q);  // D layout: rows 4 q + {0..3}, column li
+    const f32x4 bv = *reinterpret_cast<const f32x4*>(a.bias + n0 + 4 * q);
 #pragma unroll
-    for (int pt = 0; pt < 4; ++pt) acc[pt] = bv;
+    for (int pt = 0; pt < 4; ++pt) acc[0][pt] = bv;
   }
   const int nchunks = IN / HR_KC;
-  hr_f4 wa = *reinterpret_cast<const hr_f4*>(wp + (size_t)tap_slab[0] * slab_stride);
+  f32x4 wa[1] = {*reinterpret_cast<const f32x4*>(wp + (size_t)tap_slab[0] * slab_stride)};
   fetch(0);
   park(buf[0]);
   __syncthreads();
@@ -206,15 +204,12 @@ __global__ __launch_bounds__(HR_THREADS) void hr_conv_kernel(const hr_conv_args 
         const int tn = kb + 16 < HR_KC ? t : (t + 1 < NTAP ? t + 1 : 0);
         const int kn = last ? (more ? (ch + 1) * HR_KC : ch * HR_KC + kb) : ch * HR_KC + (kb + 16 < HR_KC ? kb + 16 : 0);
         const int tl = last && !more ? t : tn;
-        const hr_f4 wn = *reinterpret_cast<const hr_f4*>(wp + (size_t)tap_slab[tl] * slab_stride + kn);
-        hr_f4 b[4];
+        const f32x4 wn = *reinterpret_cast<const f32x4*>(wp + (size_t)tap_slab[tl] * slab_stride + kn);
+        f32x4 b[4];
 #pragma unroll
-        for (int pt = 0; pt < 4; ++pt) b[pt] = *reinterpret_cast<const hr_f4*>(xb + base[pt] + tap_off[t] + kb);
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-          for (int pt = 0; pt < 4; ++pt) acc[pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(wa[j], b[pt][j], acc[pt], 0, 0, 0);
-        wa = wn;
+        for (int pt = 0; pt < 4; ++pt) b[pt] = *reinterpret_cast<const f32x4*>(xb + base[pt] + tap_off[t] + kb);
+        dense_mfma_block<1>(wa, b, acc);
+        wa[0] = wn;
       }
     }
     if (more) park(buf[(ch + 1) & 1]);  // last read before the previous barrier
@@ -225,6 +220,8 @@ __global__ __launch_bounds__(HR_THREADS) void hr_conv_kernel(const hr_conv_args 
   const int n = n0 + 4 * q;
   float al[4], be[4];
   if (EPI == HR_EPI_BN) {
+    // bn_fold's arithmetic (olsr_dense.h), written out: through the call the compiler orders this epilogue's address
+    // arithmetic differently, and upsample1 then measured 0.4 % slower (profiles/dense_core_ab.json)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const double s = (double)a.bn[n + r] / sqrt((double)a.bn[3 * a.OUT + n + r] + a.eps);
@@ -245,8 +242,8 @@ __global__ __launch_bounds__(HR_THREADS) void hr_conv_kernel(const hr_conv_args 
     if (o < 0) continue;
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
-      float v = acc[pt][r];
-      if (EPI == HR_EPI_BN) v = hr_relu(fmaf(al[r], v, be[r]));
+      float v = acc[0][pt][r];
+      if (EPI == HR_EPI_BN) v = relu_keep_nan(fmaf(al[r], v, be[r]));
       if (EPI == HR_EPI_GATE) {
         const float f = a.gate[(size_t)(n + r) * (size_t)a.gate_ps + o];
         v = fmaf(f, 1.f / (1.f + expf(-v)), f);

@@ -277,13 +277,13 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_scales(int n, const float* 
   scales[3 * i + 2] = s;
 }
 
-int launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* image, const float* depth,
-                              const float* exposure, const float* w2c, const olsr_map_buffers& rows, int32_t* pix_index,
-                              void* scratch, int32_t* status, float* aux, hipStream_t st) {
+hipError_t launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* image, const float* depth,
+                                     const float* exposure, const float* w2c, const olsr_map_buffers& rows,
+                                     int32_t* pix_index, void* scratch, int32_t* status, float* aux, hipStream_t st) {
   const int64_t N = (int64_t)p.W * p.H;
   const SeedScratch sc = seed_carve(scratch, (size_t)N);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SEED_PASSES * SEED_SELECTS * 256 * sizeof(u32), st);
-  if (e != hipSuccess) return (int)e;
+  if (e != hipSuccess) return e;
   const int hb = (int)((N + SEED_HIST_PIX - 1) / SEED_HIST_PIX), nb = (int)seed_blocks((size_t)N);
   for (int pass = 0; pass < SEED_PASSES; ++pass) {
     if (pass == 0) seed_hist<true><<<hb, SEED_THREADS, 0, st>>>(N, pass, p, image, depth, sc);
@@ -293,7 +293,7 @@ int launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* i
   seed_count<<<nb, SEED_THREADS, 0, st>>>(N, p, sc);
   seed_prefix<<<1, SEED_PREFIX_THREADS, 0, st>>>(nb, sc);
   seed_emit<<<nb, SEED_THREADS, 0, st>>>(N, p, image, exposure, w2c, rows, pix_index, sc);
-  return 0;
+  return hipSuccess;
 }
 
 void launch_keyframe_seed_finish(const olsr_keyframe_seed_params& p, int n, const olsr_map_buffers& rows, const float* aux,

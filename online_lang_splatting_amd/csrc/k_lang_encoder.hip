@@ -3,10 +3,10 @@
 // The reference turns a keyframe's high-resolution CLIP map [1,768,h,w] into the 32-wide rows the online autoencoder trains on
 // with clip.permute(0,2,3,1).view(-1,768) and AutoencoderMLP.encode (language/autoencoder/model.py:15-56, in eval(), so every
 // BatchNorm1d is its running statistics): five GEMMs, four BatchNorm, four ReLU and a norm in torch ops, a permuted copy of the
-// input and every intermediate written and read again.  Here one kernel, the mirror of k_lang_query.hip's stage A:
+// input and every intermediate written and read again.  Here one kernel on olsr_dense.h, as k_lang_query.hip's stage A:
 //   lang_encoder_kernel   64 pixels per workgroup of four waves, every product Y^T = W X^T on v_mfma_f32_16x16x4_f32 with the
-//                         weights as the A operand (straight from global memory / L2, every weight read by exactly one wave of
-//                         the workgroup) and the activations as the B operand out of LDS.
+//                         weights straight from global memory / L2 (every weight read by exactly one wave of the workgroup)
+//                         and the activations out of LDS.
 //     layer 1 (768 -> 512)  a wave owns 128 neurons for all 64 pixels: 32 accumulator tiles that stay in registers while the
 //                         input passes through LDS in twelve chunks of 64 channels, [64 pixels][68] each, double-buffered: the
 //                         next chunk's global loads are issued before the current chunk's MFMAs and stored behind them.  The
@@ -14,22 +14,22 @@
 //                         load: no alignment is assumed, the pixel tail is guarded, nothing is read past the end) or from rows;
 //                         both fill the same LDS image, so both give the same bits.  The two chunk buffers lie inside the
 //                         activation image, which is not in use before layer 1 has finished.
-//     layers 2 - 5        out of one LDS image [64][516], in place, as lq_hidden: a wave keeps its share of the layer's neurons
+//     layers 2 - 5        out of one LDS image [64][516], in place (dense_layer): a wave keeps its share of the layer's neurons
 //                         in accumulators until every wave has read the layer's input.
 //     BatchNorm + ReLU    in the producing layer's epilogue: relu(fmaf(alpha, h, beta)) with alpha = weight / sqrt(var + eps),
 //                         beta = bias - mean alpha per channel, computed in double once per workgroup, rounded once, kept in LDS.
 //                         relu is fmaxf(., 0) with a NaN kept, as torch's: a NaN input row is a NaN output row.
 //     the norm            one lane per pixel: |h5|^2 in double in channel order, h5 / (float)sqrt, no epsilon (a zero row is NaN,
 //                         as in the reference).  The unit rows leave through LDS as one contiguous block.
-//     the online encoder  optional, the same lane: 32 -> 24 -> 15 of k_lang_ae.hip's lang_ae_encode_kernel operation for
-//                         operation on the unit row, so the codes equal olsr_lang_ae_encode of the stored features bit for bit.
+//     the online encoder  optional, the same lane: ae_encode (olsr_lang_ae_device.h), what lang_ae_encode_kernel calls, on the
+//                         unit row, so the codes equal olsr_lang_ae_encode of the stored features bit for bit.
 // No atomics; a pixel's result depends on its own column of every product only, whatever else is in its tile.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_dense.h"
+#include "olsr_lang_ae_device.h"
 
 namespace olsr {
-
-typedef float le_f4 __attribute__((ext_vector_type(4)));
 
 constexpr int LE_M = 64;      // pixels per workgroup
 constexpr int LE_WAVES = 4;   // 256 threads
@@ -52,93 +52,12 @@ static_assert(2 * LE_M * LE_CS <= LE_M * LE_S, "both chunk buffers inside the ac
 constexpr size_t LE_LDS_BYTES = ((size_t)LE_M * LE_S + 2 * LE_BN) * sizeof(float);
 static_assert(LE_LDS_BYTES <= 160 * 1024, "one LDS image per workgroup");
 
-// the encoder half of the online autoencoder inside the flat [2351] array of olsr_lang_ae_* (k_lang_ae.hip)
-constexpr int LE_AH = OLSR_LANG_AE_HIDDEN, LE_AC = OLSR_LANG_AE_CODE;
-constexpr int LE_AW1 = 0, LE_AB1 = LE_AW1 + LE_AH * LE_D5, LE_AW2 = LE_AB1 + LE_AH, LE_AB2 = LE_AW2 + LE_AC * LE_AH;
-
-// One 16-deep k block of Y^T[NT x 16 neurons][64 pixels] += W X^T out of an LDS image of S floats per pixel: lq_block's
-// operand layout (k_lang_query.hip).
-template <int NT, int S>
-__device__ __forceinline__ void le_block(const le_f4 (&a)[NT], const float* __restrict__ xk, le_f4 (&acc)[NT][4]) {
-  le_f4 b[4];
-#pragma unroll
-  for (int pt = 0; pt < 4; ++pt) b[pt] = *reinterpret_cast<const le_f4*>(xk + pt * 16 * S);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt) acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], b[pt][j], acc[t][pt], 0, 0, 0);
-}
-
-template <int NT>
-__device__ __forceinline__ void le_bias(const float* __restrict__ bias, int n0, int q, le_f4 (&acc)[NT][4]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const le_f4 bv = *reinterpret_cast<const le_f4*>(bias + n0 + 16 * t + 4 * q);
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) acc[t][pt] = bv;
-  }
-}
-
-// ReLU as torch has it: fmaxf(v, 0), except that a NaN stays a NaN (fmaxf alone returns the other operand, and a NaN input row
-// would come out as finite numbers)
-__device__ __forceinline__ float le_relu(float v) { return v != v ? v : fmaxf(v, 0.f); }
-
-// the accumulators of a layer into the image: relu(alpha h + beta) per neuron (BN), or h as it is.  In the D layout lane
-// (li, q) holds neurons n0 + 16 t + 4 q + {0..3} of pixel 16 pt + li.
-template <int NT, bool BN>
-__device__ __forceinline__ void le_store(float* __restrict__ X, const float* __restrict__ alpha, const float* __restrict__ beta,
-                                         int n0, int li, int q, const le_f4 (&acc)[NT][4]) {
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const int n = n0 + 16 * t + 4 * q;
-    le_f4 al = le_f4{1.f, 1.f, 1.f, 1.f}, be = le_f4{0.f, 0.f, 0.f, 0.f};
-    if (BN) {
-      al = *reinterpret_cast<const le_f4*>(alpha + n);
-      be = *reinterpret_cast<const le_f4*>(beta + n);
-    }
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      le_f4 v = acc[t][pt];
-      if (BN) {
-#pragma unroll
-        for (int r = 0; r < 4; ++r) v[r] = le_relu(fmaf(al[r], v[r], be[r]));
-      }
-      *reinterpret_cast<le_f4*>(X + (pt * 16 + li) * LE_S + n) = v;
-    }
-  }
-}
-
-// one layer out of the image, in place: X[64][KIN] -> X[64][NOUT].  The first WUSED waves share the neurons.
-template <int KIN, int NOUT, int WUSED, bool BN>
+// one layer out of the activation image, in place; the first WUSED waves share the neurons
+template <int KIN, int NOUT, int WUSED, int EPI>
 __device__ __forceinline__ void le_layer(float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
                                          const float* __restrict__ alpha, const float* __restrict__ beta, int wave, int li,
                                          int q) {
-  constexpr int NT = NOUT / (16 * WUSED);
-  static_assert(NT * 16 * WUSED == NOUT && WUSED <= LE_WAVES && KIN % 16 == 0 && KIN <= LE_S, "an equal share per wave");
-  const int n0 = wave * NT * 16;
-  le_f4 acc[NT][4];
-  if (wave < WUSED) {
-    le_bias<NT>(bias, n0, q, acc);
-    const float* wp = W + (size_t)(n0 + li) * KIN + 4 * q;
-    const float* xp = X + li * LE_S + 4 * q;
-    le_f4 a[NT], an[NT];
-#pragma unroll
-    for (int t = 0; t < NT; ++t) a[t] = *reinterpret_cast<const le_f4*>(wp + (size_t)t * 16 * KIN);
-#pragma unroll 2
-    for (int k0 = 0; k0 < KIN; k0 += 16) {
-      const int kn = k0 + 16 < KIN ? k0 + 16 : k0;
-#pragma unroll
-      for (int t = 0; t < NT; ++t) an[t] = *reinterpret_cast<const le_f4*>(wp + (size_t)t * 16 * KIN + kn);
-      le_block<NT, LE_S>(a, xp + k0, acc);
-#pragma unroll
-      for (int t = 0; t < NT; ++t) a[t] = an[t];
-    }
-  }
-  __syncthreads();  // every wave has read the layer's input
-  if (wave < WUSED) le_store<NT, BN>(X, alpha, beta, n0, li, q, acc);
-  __syncthreads();
+  dense_layer<KIN, NOUT, LE_WAVES, WUSED, LE_S, EPI>(X, W, bias, alpha, beta, wave, li, q);
 }
 
 // A thread's 16 elements of the chunk of channels k0 .. k0 + 63: element i is (pixel, channel) = (tid & 63, (tid >> 6) + 4 i)
@@ -166,14 +85,6 @@ __device__ __forceinline__ void le_park(float* __restrict__ buf, int tid, const 
   }
 }
 
-// BatchNorm1d in eval(): alpha = weight / sqrt(running_var + eps), beta = bias - running_mean alpha, in double, rounded once
-__device__ __forceinline__ void le_bn_fold(const float* __restrict__ bn, int C, int c, double eps, float* __restrict__ alpha,
-                                           float* __restrict__ beta) {
-  const double a = (double)bn[c] / sqrt((double)bn[3 * C + c] + eps);
-  alpha[c] = (float)a;
-  beta[c] = (float)((double)bn[C + c] - (double)bn[2 * C + c] * a);
-}
-
 template <bool CHANNELS>
 __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, long long plane_stride, double bn_eps,
                                                                         const float* __restrict__ features,
@@ -191,10 +102,10 @@ __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, lo
   float pre[16];
   le_fetch<CHANNELS>(features, N, plane_stride, row0, 0, tid, pre);
   for (int c = tid; c < LE_BN; c += LE_M * LE_WAVES) {
-    if (c < A2) le_bn_fold(P + LE_N1, LE_D1, c - A1, bn_eps, alpha + A1, beta + A1);
-    else if (c < A3) le_bn_fold(P + LE_N2, LE_D2, c - A2, bn_eps, alpha + A2, beta + A2);
-    else if (c < A4) le_bn_fold(P + LE_N3, LE_D3, c - A3, bn_eps, alpha + A3, beta + A3);
-    else le_bn_fold(P + LE_N4, LE_D4, c - A4, bn_eps, alpha + A4, beta + A4);
+    if (c < A2) bn_fold(P + LE_N1, LE_D1, c - A1, bn_eps, alpha[c], beta[c]);
+    else if (c < A3) bn_fold(P + LE_N2, LE_D2, c - A2, bn_eps, alpha[c], beta[c]);
+    else if (c < A4) bn_fold(P + LE_N3, LE_D3, c - A3, bn_eps, alpha[c], beta[c]);
+    else bn_fold(P + LE_N4, LE_D4, c - A4, bn_eps, alpha[c], beta[c]);
   }
   le_park<CHANNELS>(X, tid, pre);
   __syncthreads();
@@ -203,12 +114,12 @@ __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, lo
   {
     constexpr int NT = LE_D1 / (16 * LE_WAVES);
     const int n0 = wave * NT * 16;
-    le_f4 acc[NT][4];
-    le_bias<NT>(P + LE_B1, n0, q, acc);
+    f32x4 acc[NT][4];
+    dense_bias<NT>(P + LE_B1, n0, q, acc);
     const float* wp = P + LE_W1 + (size_t)(n0 + li) * LE_D0 + 4 * q;
-    le_f4 a[NT], an[NT];
+    f32x4 a[NT], an[NT];
 #pragma unroll
-    for (int t = 0; t < NT; ++t) a[t] = *reinterpret_cast<const le_f4*>(wp + (size_t)t * 16 * LE_D0);
+    for (int t = 0; t < NT; ++t) a[t] = *reinterpret_cast<const f32x4*>(wp + (size_t)t * 16 * LE_D0);
 #pragma unroll 1
     for (int ch = 0; ch < LE_CHUNKS; ++ch) {
       const bool more = ch + 1 < LE_CHUNKS;
@@ -219,21 +130,22 @@ __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, lo
         const int k0 = ch * LE_KC + kb;
         const int kn = k0 + 16 < LE_D0 ? k0 + 16 : k0;
 #pragma unroll
-        for (int t = 0; t < NT; ++t) an[t] = *reinterpret_cast<const le_f4*>(wp + (size_t)t * 16 * LE_D0 + kn);
-        le_block<NT, LE_CS>(a, xp + kb, acc);
+        for (int t = 0; t < NT; ++t) an[t] = *reinterpret_cast<const f32x4*>(wp + (size_t)t * 16 * LE_D0 + kn);
+        dense_block<NT, LE_CS>(a, xp + kb, acc);
 #pragma unroll
         for (int t = 0; t < NT; ++t) a[t] = an[t];
       }
       if (more) le_park<CHANNELS>(X + ((ch + 1) & 1) * LE_M * LE_CS, tid, pre);  // last read before the previous barrier
       __syncthreads();
     }
-    le_store<NT, true>(X, alpha + A1, beta + A1, n0, li, q, acc);  // every wave is past its last chunk read
+    // (every wave is past its last chunk read)
+    dense_store<NT, LE_S, DENSE_EPI_BN_RELU>(X, alpha + A1, beta + A1, n0, li, q, acc);
     __syncthreads();
   }
-  le_layer<LE_D1, LE_D2, 4, true>(X, P + LE_W2, P + LE_B2, alpha + A2, beta + A2, wave, li, q);
-  le_layer<LE_D2, LE_D3, 4, true>(X, P + LE_W3, P + LE_B3, alpha + A3, beta + A3, wave, li, q);
-  le_layer<LE_D3, LE_D4, 4, true>(X, P + LE_W4, P + LE_B4, alpha + A4, beta + A4, wave, li, q);
-  le_layer<LE_D4, LE_D5, 2, false>(X, P + LE_W5, P + LE_B5, nullptr, nullptr, wave, li, q);
+  le_layer<LE_D1, LE_D2, 4, DENSE_EPI_BN_RELU>(X, P + LE_W2, P + LE_B2, alpha + A2, beta + A2, wave, li, q);
+  le_layer<LE_D2, LE_D3, 4, DENSE_EPI_BN_RELU>(X, P + LE_W3, P + LE_B3, alpha + A3, beta + A3, wave, li, q);
+  le_layer<LE_D3, LE_D4, 4, DENSE_EPI_BN_RELU>(X, P + LE_W4, P + LE_B4, alpha + A4, beta + A4, wave, li, q);
+  le_layer<LE_D4, LE_D5, 2, DENSE_EPI_NONE>(X, P + LE_W5, P + LE_B5, nullptr, nullptr, wave, li, q);
 
   // one lane per pixel: x / |x|, and the online encoder on the unit row
   if (tid < LE_M) {
@@ -242,7 +154,7 @@ __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, lo
     double s = 0.0;
 #pragma unroll
     for (int k4 = 0; k4 < LE_D5 / 4; ++k4) {
-      const le_f4 v = *reinterpret_cast<const le_f4*>(mine + 4 * k4);
+      const f32x4 v = *reinterpret_cast<const f32x4*>(mine + 4 * k4);
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         u[4 * k4 + r] = v[r];
@@ -254,35 +166,12 @@ __global__ __launch_bounds__(LE_M * LE_WAVES) void lang_encoder_kernel(int N, lo
     for (int k = 0; k < LE_D5; ++k) u[k] = u[k] / n;
 #pragma unroll
     for (int k4 = 0; k4 < LE_D5 / 4; ++k4)
-      *reinterpret_cast<le_f4*>(mine + 4 * k4) = le_f4{u[4 * k4], u[4 * k4 + 1], u[4 * k4 + 2], u[4 * k4 + 3]};
+      *reinterpret_cast<f32x4*>(mine + 4 * k4) = f32x4{u[4 * k4], u[4 * k4 + 1], u[4 * k4 + 2], u[4 * k4 + 3]};
     const int row = row0 + tid;
     if (codes != nullptr && row < N) {
-      // ae_encode (k_lang_ae.hip): h1 = relu(W1 x + b1), z = W2 h1 + b2, c = z / |z|
-      float h1[LE_AH], z[LE_AC];
-#pragma unroll
-      for (int o = 0; o < LE_AH; ++o) {
-        float a = online[LE_AB1 + o];
-#pragma unroll
-        for (int i = 0; i < LE_D5; ++i) a = fmaf(online[LE_AW1 + o * LE_D5 + i], u[i], a);
-        h1[o] = fmaxf(a, 0.f);
-      }
-      double sz = 0.0;
-#pragma unroll
-      for (int o = 0; o < LE_AC; ++o) {
-        float a = online[LE_AB2 + o];
-#pragma unroll
-        for (int i = 0; i < LE_AH; ++i) a = fmaf(online[LE_AW2 + o * LE_AH + i], h1[i], a);
-        z[o] = a;
-      }
-#pragma unroll
-      for (int o = 0; o < LE_AC; ++o) sz = fma((double)z[o], (double)z[o], sz);
-      const float nz = (float)sqrt(sz);
-#pragma unroll
-      for (int o = 0; o < LE_AC; ++o) {
-        const float c = z[o] / nz;
-        if (code_layout == OLSR_LANG_AE_CODES_CHANNELS) codes[(size_t)o * N + row] = c;
-        else codes[(size_t)row * LE_AC + o] = c;
-      }
+      float h1[AE_H], c[AE_C];
+      ae_encode(online, u, h1, c);
+      ae_store_codes(codes, code_layout, N, row, c);
     }
   }
   if (features32 == nullptr) return;

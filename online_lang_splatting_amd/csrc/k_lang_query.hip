@@ -6,9 +6,9 @@
 // with the phrase embeddings, and post-processes the similarities on the host (softmax against the negatives, cv2.filter2D,
 // max / min, threshold).  Here:
 //   lang_query_sims_kernel       stage A.  64 pixels per workgroup of four waves.  The activations of the 64 pixels live in ONE
-//                                LDS image [64][516] (pixel-major); every layer is Y^T = W X^T on v_mfma_f32_16x16x4_f32 with the
-//                                weights as the A operand (straight from global memory / L2, every weight read by exactly one wave
-//                                of the workgroup, so each is read once per 64 pixels) and the activations as the B operand.  A wave
+//                                LDS image [64][516] (pixel-major); every layer is olsr_dense.h's Y^T = W X^T on
+//                                v_mfma_f32_16x16x4_f32 with the weights as the A operand (straight from global memory / L2, every
+//                                weight read by exactly one wave of the workgroup, so each is read once per 64 pixels).  A wave
 //                                owns a quarter of the layer's output neurons for all 64 pixels and keeps them in accumulators
 //                                until every wave has finished reading the layer's input, then overwrites the image in place.
 //                                The last layer (512 -> 768) is produced in blocks of 64 neurons per wave; a block's accumulators
@@ -24,16 +24,12 @@
 // Arithmetic is float32 throughout (an MFMA is a k-ordered fmaf chain); the norms and the window sums are double.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_dense.h"
+#include "olsr_lang_ae_device.h"
 
 namespace olsr {
 
-typedef float lq_f4 __attribute__((ext_vector_type(4)));
-
-// the online decoder inside the flat [2351] array of olsr_lang_ae_* (k_lang_ae.hip)
-constexpr int LQ_C = OLSR_LANG_AE_CODE, LQ_H = OLSR_LANG_AE_HIDDEN, LQ_IN = OLSR_LANG_AE_IN;
-constexpr int LQ_W3 = LQ_H * LQ_IN + LQ_H + LQ_C * LQ_H + LQ_C, LQ_B3 = LQ_W3 + LQ_H * LQ_C, LQ_W4 = LQ_B3 + LQ_H,
-              LQ_B4 = LQ_W4 + LQ_IN * LQ_H;
-static_assert(LQ_B4 + LQ_IN == OLSR_LANG_AE_PARAMS, "flat parameter layout");
+constexpr int LQ_C = AE_C, LQ_IN = AE_IN;  // the online decoder's ends (olsr_lang_ae_device.h)
 
 constexpr int LQ_M = 64;        // pixels per workgroup
 constexpr int LQ_WAVES = 4;     // 256 threads
@@ -76,95 +72,11 @@ struct LqGeom {
 
 // ---- stage A --------------------------------------------------------------------------------------------------------------
 
-// the online decoder of one pixel, operation for operation lang_ae_decode_kernel's (k_lang_ae.hip): r = y / |y|
-__device__ __forceinline__ void lq_online_decode(const float* __restrict__ P, const float (&c)[LQ_C], float* __restrict__ out) {
-  float h[LQ_H], y[LQ_IN];
-#pragma unroll
-  for (int o = 0; o < LQ_H; ++o) {
-    float a = P[LQ_B3 + o];
-#pragma unroll
-    for (int i = 0; i < LQ_C; ++i) a = fmaf(P[LQ_W3 + o * LQ_C + i], c[i], a);
-    h[o] = fmaxf(a, 0.f);
-  }
-  double s = 0.0;
-#pragma unroll
-  for (int o = 0; o < LQ_IN; ++o) {
-    float a = P[LQ_B4 + o];
-#pragma unroll
-    for (int i = 0; i < LQ_H; ++i) a = fmaf(P[LQ_W4 + o * LQ_H + i], h[i], a);
-    y[o] = a;
-    s = fma((double)a, (double)a, s);
-  }
-  const float n = (float)sqrt(s);
-#pragma unroll
-  for (int o = 0; o < LQ_IN; ++o) out[o] = y[o] / n;
-}
-
-// One 16-deep k block of Y^T[NT x 16 neurons][64 pixels] += W X^T.  Lane (li = lane & 15, q = lane >> 4) supplies, for the
-// MFMA of element j, A[i = li][k = q] = W[n + li][k0 + 4 q + j] and B[k = q][col = li] = X[pixel 16 pt + li][k0 + 4 q + j]: the
-// k order inside a block is permuted the same way on both sides, and each side is one 16-byte load.
-template <int NT>
-__device__ __forceinline__ void lq_block(const lq_f4 (&a)[NT], const float* __restrict__ xk, lq_f4 (&acc)[NT][4]) {
-  lq_f4 b[4];
-#pragma unroll
-  for (int pt = 0; pt < 4; ++pt) b[pt] = *reinterpret_cast<const lq_f4*>(xk + pt * 16 * LQ_S);
-#pragma unroll
-  for (int j = 0; j < 4; ++j)
-#pragma unroll
-    for (int t = 0; t < NT; ++t)
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt) acc[t][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(a[t][j], b[pt][j], acc[t][pt], 0, 0, 0);
-}
-
-// acc[t][pt] = the tile (neurons n0 + 16 t .. + 15) x (pixels 16 pt .. + 15) of W X^T + b over the whole KIN.  In the D layout
-// lane (li, q) holds neurons n0 + 16 t + 4 q + {0..3} of pixel 16 pt + li.  The next block's weights are loaded before this
-// block's MFMAs are issued.
-template <int KIN, int NT>
-__device__ __forceinline__ void lq_gemm(const float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
-                                        int n0, int li, int q, lq_f4 (&acc)[NT][4]) {
-  static_assert(KIN % 16 == 0, "k blocks of 16");
-#pragma unroll
-  for (int t = 0; t < NT; ++t) {
-    const lq_f4 bv = *reinterpret_cast<const lq_f4*>(bias + n0 + 16 * t + 4 * q);
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) acc[t][pt] = bv;
-  }
-  const float* wp = W + (size_t)(n0 + li) * KIN + 4 * q;
-  const float* xp = X + li * LQ_S + 4 * q;
-  lq_f4 a[NT], an[NT];
-#pragma unroll
-  for (int t = 0; t < NT; ++t) a[t] = *reinterpret_cast<const lq_f4*>(wp + (size_t)t * 16 * KIN);
-#pragma unroll 2
-  for (int k0 = 0; k0 < KIN; k0 += 16) {
-    const int kn = k0 + 16 < KIN ? k0 + 16 : k0;
-#pragma unroll
-    for (int t = 0; t < NT; ++t) an[t] = *reinterpret_cast<const lq_f4*>(wp + (size_t)t * 16 * KIN + kn);
-    lq_block<NT>(a, xp + k0, acc);
-#pragma unroll
-    for (int t = 0; t < NT; ++t) a[t] = an[t];
-  }
-}
-
-// one hidden layer in place: X[64][KIN] -> relu(W X^T + b)^T = X[64][NOUT]
+// one hidden layer in place: X[64][KIN] -> relu(W X^T + b)^T = X[64][NOUT], a quarter of the neurons per wave
 template <int KIN, int NOUT>
 __device__ __forceinline__ void lq_hidden(float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
                                           int wave, int li, int q) {
-  constexpr int NT = NOUT / (16 * LQ_WAVES);
-  static_assert(NT * 16 * LQ_WAVES == NOUT && NOUT <= LQ_S, "a quarter of the neurons per wave");
-  const int n0 = wave * NT * 16;
-  lq_f4 acc[NT][4];
-  lq_gemm<KIN, NT>(X, W, bias, n0, li, q, acc);
-  __syncthreads();  // every wave has read the layer's input
-#pragma unroll
-  for (int t = 0; t < NT; ++t)
-#pragma unroll
-    for (int pt = 0; pt < 4; ++pt) {
-      lq_f4 v = acc[t][pt];
-#pragma unroll
-      for (int r = 0; r < 4; ++r) v[r] = fmaxf(v[r], 0.f);
-      *reinterpret_cast<lq_f4*>(X + (pt * 16 + li) * LQ_S + n0 + 16 * t + 4 * q) = v;
-    }
-  __syncthreads();
+  dense_layer<KIN, NOUT, LQ_WAVES, LQ_WAVES, LQ_S, DENSE_EPI_RELU>(X, W, bias, nullptr, nullptr, wave, li, q);
 }
 
 // KT: 16-row tiles of phrases (K <= 16 KT)
@@ -192,7 +104,10 @@ __global__ __launch_bounds__(LQ_M * LQ_WAVES) void lang_query_sims_kernel(int N,
 #pragma unroll
         for (int k = 0; k < LQ_C; ++k) c[k] = codes[(size_t)k * N + row];
       }
-      lq_online_decode(online, c, X + tid * LQ_S);
+      float h2[AE_H], r[LQ_IN];
+      ae_decode(online, c, h2, r);  // r = y / |y|, as olsr_lang_ae_decode has it
+#pragma unroll
+      for (int k = 0; k < LQ_IN; ++k) X[tid * LQ_S + k] = r[k];
     } else {
 #pragma unroll
       for (int k = 0; k < LQ_IN; ++k) X[tid * LQ_S + k] = 0.f;
@@ -206,18 +121,18 @@ __global__ __launch_bounds__(LQ_M * LQ_WAVES) void lang_query_sims_kernel(int N,
   // the last layer in blocks of 4 x 16 neurons per wave, consumed as they arrive
   constexpr int NT = 4, CHUNKS = LQ_D5 / (16 * NT * LQ_WAVES);
   static_assert(CHUNKS * 16 * NT * LQ_WAVES == LQ_D5, "blocks of 64 neurons per wave");
-  lq_f4 sacc[KT][4];  // tile (phrases 16 kt ..) x (pixels 16 pt ..): lane (li, q) holds phrases 16 kt + 4 q + {0..3} of pixel 16 pt + li
+  f32x4 sacc[KT][4];  // tile (phrases 16 kt ..) x (pixels 16 pt ..): lane (li, q) holds phrases 16 kt + 4 q + {0..3} of pixel 16 pt + li
   double nrm[4];      // this lane's part of |y|^2 of pixel 16 pt + li
 #pragma unroll
   for (int pt = 0; pt < 4; ++pt) {
     nrm[pt] = 0.0;
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt) sacc[kt][pt] = lq_f4{0.f, 0.f, 0.f, 0.f};
+    for (int kt = 0; kt < KT; ++kt) sacc[kt][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
   }
   for (int ch = 0; ch < CHUNKS; ++ch) {
     const int n0 = (wave * CHUNKS + ch) * NT * 16;
-    lq_f4 acc[NT][4];
-    lq_gemm<LQ_D4, NT>(X, dec + LQ_OW5, dec + LQ_OB5, n0, li, q, acc);
+    f32x4 acc[NT][4];
+    dense_gemm<LQ_D4, NT, LQ_S>(X, dec + LQ_OW5, dec + LQ_OB5, n0, li, q, acc);
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
 #pragma unroll
@@ -228,8 +143,8 @@ __global__ __launch_bounds__(LQ_M * LQ_WAVES) void lang_query_sims_kernel(int N,
       for (int kt = 0; kt < KT; ++kt) {
         // A[i = li][k = q] = phrase 16 kt + li at neuron n0 + 16 t + 4 q + r; B[k = q][col = li] = acc[t][pt][r] as it lies
         const int ph = kt * 16 + li;
-        lq_f4 pf = lq_f4{0.f, 0.f, 0.f, 0.f};
-        if (ph < K) pf = *reinterpret_cast<const lq_f4*>(phrases + (size_t)ph * LQ_FEAT + n0 + 16 * t + 4 * q);
+        f32x4 pf = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (ph < K) pf = *reinterpret_cast<const f32x4*>(phrases + (size_t)ph * LQ_FEAT + n0 + 16 * t + 4 * q);
 #pragma unroll
         for (int r = 0; r < 4; ++r)
 #pragma unroll

@@ -37,6 +37,7 @@
 
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_dense.h"  // f32x4
 
 namespace olsr {
 
@@ -70,7 +71,6 @@ constexpr int BWD_BATCH = 128;
 #ifndef OLSR_BWD_MFMA_REDUCE
 #define OLSR_BWD_MFMA_REDUCE 0  // 1: sum the ten per-splat values over the wave with MFMAs (round-4 experiment, slower: see the kernel)
 #endif
-typedef float bwd_f32x4 __attribute__((ext_vector_type(4)));
 #ifndef OLSR_BWD_SCALAR_MAX_F
 #define OLSR_BWD_SCALAR_MAX_F 32
 #endif
@@ -469,11 +469,11 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, (PACKED && F <= 16) ? OLSR_BWD_
       // two-value tree.  Total j ends up in the lanes whose role is j (role_of below); that lane stores it.
       float rowval = 0.f;
       if constexpr (MRED) {
-        bwd_f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
+        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int m = 0; m < 10; ++m) d4 = __builtin_amdgcn_mfma_f32_16x16x4f32(sum[m], sel[m], d4, 0, 0, 0);
         const float part = (d4[0] + d4[1]) + (d4[2] + d4[3]);
-        const bwd_f32x4 t4 = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, part, bwd_f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
+        const f32x4 t4 = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, part, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
         rowval = t4[0];
       } else if constexpr (MERGED && LDSR) {
         float* wl = &s_red[w * 256];

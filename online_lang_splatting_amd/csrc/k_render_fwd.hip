@@ -30,6 +30,7 @@
 #include "olsr_device.h"
 #include "olsr_kernels.h"
 #include "olsr_loss_device.h"
+#include "olsr_dense.h"  // f32x4
 
 namespace olsr {
 
@@ -60,7 +61,6 @@ __device__ unsigned long long g_fwd_stats[8];
 // wave, beside the VALU that evaluates alpha and the transmittance; every decision stays on the VALU, bit for bit.
 // The product is then rounded as fma(alpha T, f, C) instead of the reference's fma(f alpha, T, C): images agree with the
 // oracle to ~1e-7 relative instead of bit for bit (final_T, n_contrib, radii, n_touched, flags stay bit-identical).
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 // ACC: 0 = the reference's rounding fma(f alpha, T, C) on the vector ALU (bit-identical to the oracle, default);
 //      1 = matrix cores (OLSR_FLAG_FWD_ACCUM_MFMA); 2 = w = alpha T once per pixel, then ONE fma(w, f, C) per channel on

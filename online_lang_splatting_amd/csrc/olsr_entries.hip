@@ -280,13 +280,16 @@ int olsr_lang_ae_decode(int32_t N, const float* codes, const float* params, int3
   return launch_check("lang_ae_decode");
 }
 
+// the six layer widths a caller names against the ones compiled in
+static bool widths_built(int32_t n_widths, const int32_t* widths, const int32_t (&built)[6]) {
+  return n_widths == 6 && std::equal(built, built + 6, widths);
+}
+
 // what is wrong with the sizes of a language query, or nullptr
 static const char* lang_query_params_error(const olsr_lang_query_params* p) {
-  static const int32_t built[6] = {OLSR_LANG_AE_IN, 192, 256, 384, 512, OLSR_LANG_QUERY_FEATURE_DIM};
   if (!p) return "the parameter struct is NULL";
-  if (p->n_widths != 6) return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
-  for (int k = 0; k < 6; ++k)
-    if (p->widths[k] != built[k]) return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
+  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_AE_IN, 192, 256, 384, 512, OLSR_LANG_QUERY_FEATURE_DIM}))
+    return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
   if (p->K < 1 || p->K > OLSR_LANG_QUERY_MAX_PHRASES) return "K must be between 1 and 64";
   if (p->n_pos < 0 || p->n_labels < 0 || p->n_pos + p->n_labels > p->K) return "n_pos and n_labels must be >= 0 and sum to at most K";
   if (p->in_width < 1 || p->in_height < 1 || p->dec_width < 1 || p->dec_height < 1 || p->out_width < 1 || p->out_height < 1)
@@ -309,9 +312,8 @@ int olsr_lang_query_sims(const olsr_lang_query_params* p, const float* codes, co
     return fail(OLSR_ERR_ARG, "lang_query_sims: codes, both parameter arrays, phrases and sims are required");
   if (((uintptr_t)decoder_params & 15u) || ((uintptr_t)phrases & 15u))
     return fail(OLSR_ERR_ARG, "lang_query_sims: decoder_params and phrases must be 16-byte aligned");
-  const hipError_t e = launch_lang_query_sims(*p, codes, online_params, decoder_params, phrases, sims, (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("lang_query_sims: ") + hipGetErrorString(e));
-  return launch_check("lang_query_sims");
+  return launch_check("lang_query_sims", launch_lang_query_sims(*p, codes, online_params, decoder_params, phrases, sims,
+                                                                (hipStream_t)hip_stream));
 }
 
 int olsr_lang_query_relevancy(const olsr_lang_query_params* p, const float* sims, float* relevancy, float* smoothed,
@@ -335,12 +337,9 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params* p, const float* sims
 
 int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const float* features768, const float* encoder_params,
                              const float* online_params, float* features32, float* codes, void* hip_stream) {
-  static const int32_t built[6] = {OLSR_LANG_QUERY_FEATURE_DIM, 512, 256, 128, 64, OLSR_LANG_AE_IN};
-  const char* widths_msg = "lang_encoder_encode: this build encodes the layer widths {768, 512, 256, 128, 64, 32} only";
   if (!p) return fail(OLSR_ERR_ARG, "lang_encoder_encode: the parameter struct is NULL");
-  if (p->n_widths != 6) return fail(OLSR_ERR_ARG, widths_msg);
-  for (int k = 0; k < 6; ++k)
-    if (p->widths[k] != built[k]) return fail(OLSR_ERR_ARG, widths_msg);
+  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_QUERY_FEATURE_DIM, 512, 256, 128, 64, OLSR_LANG_AE_IN}))
+    return fail(OLSR_ERR_ARG, "lang_encoder_encode: this build encodes the layer widths {768, 512, 256, 128, 64, 32} only");
   if (N < 1) return fail(OLSR_ERR_ARG, "lang_encoder_encode: N must be positive");
   if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS)
     return fail(OLSR_ERR_ARG, "lang_encoder_encode: unknown input layout");
@@ -352,10 +351,8 @@ int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const
   if (!features32 && !codes) return fail(OLSR_ERR_ARG, "lang_encoder_encode: features32 and codes are both NULL");
   if (codes && !online_params) return fail(OLSR_ERR_ARG, "lang_encoder_encode: codes need online_params");
   if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "lang_encoder_encode: encoder_params must be 16-byte aligned");
-  const hipError_t e = launch_lang_encoder(*p, N, features768, encoder_params, online_params, features32, codes,
-                                           (hipStream_t)hip_stream);
-  if (e != hipSuccess) return fail(OLSR_ERR_DEVICE, std::string("lang_encoder_encode: ") + hipGetErrorString(e));
-  return launch_check("lang_encoder_encode");
+  return launch_check("lang_encoder_encode", launch_lang_encoder(*p, N, features768, encoder_params, online_params,
+                                                                 features32, codes, (hipStream_t)hip_stream));
 }
 
 size_t olsr_hr_net_workspace_bytes(int32_t h, int32_t w, int32_t h3, int32_t w3, int32_t h2, int32_t w2) {
@@ -512,10 +509,8 @@ int olsr_keyframe_seed_plan(const olsr_keyframe_seed_params* p, const float* ima
     return fail(OLSR_ERR_ARG, "keyframe_seed_plan: image, depth, w2c, rows, pix_index, scratch, status and aux are required");
   if (!rows->means3D || !rows->shs || !rows->opacities || !rows->scales || !rows->rotations)
     return fail(OLSR_ERR_ARG, "keyframe_seed_plan: the staging rows need means3D, shs, opacities, scales and rotations");
-  const int e = launch_keyframe_seed_plan(*p, image, depth, exposure, w2c, *rows, pix_index, scratch, status, aux,
-                                          (hipStream_t)hip_stream);
-  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("keyframe_seed_plan: ") + hipGetErrorString((hipError_t)e));
-  return launch_check("keyframe_seed_plan");
+  return launch_check("keyframe_seed_plan", launch_keyframe_seed_plan(*p, image, depth, exposure, w2c, *rows, pix_index,
+                                                                      scratch, status, aux, (hipStream_t)hip_stream));
 }
 
 int olsr_keyframe_seed_finish(const olsr_keyframe_seed_params* p, int32_t n, const olsr_map_buffers* rows, const float* aux,
@@ -551,9 +546,8 @@ int olsr_grad_mask(int32_t W, int32_t H, int64_t plane_stride, int32_t mode, flo
   } else {
     return fail(OLSR_ERR_ARG, "grad_mask: mode must be OLSR_GRAD_MASK_BLOCKS or OLSR_GRAD_MASK_GLOBAL");
   }
-  const int e = launch_grad_mask(W, H, plane_stride, mode, edge_threshold, image, mask, scratch, (hipStream_t)hip_stream);
-  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("grad_mask: ") + hipGetErrorString((hipError_t)e));
-  return launch_check("grad_mask");
+  return launch_check("grad_mask", launch_grad_mask(W, H, plane_stride, mode, edge_threshold, image, mask, scratch,
+                                                    (hipStream_t)hip_stream));
 }
 
 int olsr_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch, float* median,
@@ -561,9 +555,7 @@ int olsr_median_depth(int64_t N, const float* depth, const float* opacity, const
   if (N <= 0 || N > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "median_depth: N must lie in 1 ... 2^31 - 1");
   if (!depth || !opacity || !scratch || !median || !count)
     return fail(OLSR_ERR_ARG, "median_depth: depth, opacity, scratch, median and count are required");
-  const int e = launch_median_depth(N, depth, opacity, mask, scratch, median, count, (hipStream_t)hip_stream);
-  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("median_depth: ") + hipGetErrorString((hipError_t)e));
-  return launch_check("median_depth");
+  return launch_check("median_depth", launch_median_depth(N, depth, opacity, mask, scratch, median, count, (hipStream_t)hip_stream));
 }
 
 int olsr_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views* views, uint8_t* cur_out, int64_t* counts,
@@ -573,9 +565,7 @@ int olsr_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_view
   if (views->K < 0 || views->K > OLSR_COVIS_MAX_VIEWS) return fail(OLSR_ERR_ARG, "covisibility: K must lie in 0 ... 16");
   for (int k = 0; k < views->K; ++k)
     if (!views->vis[k]) return fail(OLSR_ERR_ARG, "covisibility: a keyframe visibility is NULL");
-  const int e = launch_covisibility(P, n_touched, *views, cur_out, counts, (hipStream_t)hip_stream);
-  if (e != 0) return fail(OLSR_ERR_DEVICE, std::string("covisibility: ") + hipGetErrorString((hipError_t)e));
-  return launch_check("covisibility");
+  return launch_check("covisibility", launch_covisibility(P, n_touched, *views, cur_out, counts, (hipStream_t)hip_stream));
 }
 
 int olsr_keyframe_decide(const olsr_keyframe_decide_params* p, const int64_t* counts, const float* median,

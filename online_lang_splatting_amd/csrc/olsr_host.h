@@ -35,6 +35,15 @@ inline int launch_check(const char* what) {
   return e == hipSuccess ? OLSR_OK : fail(OLSR_ERR_DEVICE, std::string(what) + " launch: " + hipGetErrorString(e));
 }
 
+// a launch_* that makes a runtime call of its own ahead of its kernels (a memset, a function attribute) returns that
+// call's error: the entry `who` reports it, or goes on to launch_check
+inline int launch_failed(const char* who, hipError_t e) {
+  return fail(OLSR_ERR_DEVICE, std::string(who) + ": " + hipGetErrorString(e));
+}
+inline int launch_check(const char* who, hipError_t own) {
+  return own == hipSuccess ? launch_check(who) : launch_failed(who, own);
+}
+
 // profiling marks and composite stamps (olsr_diag.hip); both do nothing unless a diagnostic entry switched them on
 void mark(const char* name, hipStream_t st);
 void stamp(hipStream_t st, int kind);

@@ -236,20 +236,20 @@ void launch_map_edit_apply(int P, int M, int F, const olsr_map_edit_params& p, c
 
 // k_keyframe_seed.hip (plan: 0, or the HIP error of its memset)
 size_t keyframe_seed_scratch_bytes(int W, int H);
-int launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* image, const float* depth,
-                              const float* exposure, const float* w2c, const olsr_map_buffers& rows, int32_t* pix_index,
-                              void* scratch, int32_t* status, float* aux, hipStream_t st);
+hipError_t launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const float* image, const float* depth,
+                                     const float* exposure, const float* w2c, const olsr_map_buffers& rows,
+                                     int32_t* pix_index, void* scratch, int32_t* status, float* aux, hipStream_t st);
 void launch_keyframe_seed_finish(const olsr_keyframe_seed_params& p, int n, const olsr_map_buffers& rows, const float* aux,
                                  void* scratch, void* knn_scratch, hipStream_t st);
 
 // k_frontend.hip (the int-returning ones: 0, or the HIP error of their memset)
 size_t frontend_scratch_bytes(int64_t n);
-int launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float edge_threshold, const float* image, float* mask,
-                     void* scratch, hipStream_t st);
-int launch_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch, float* median,
-                        int32_t* count, hipStream_t st);
-int launch_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views& views, uint8_t* cur_out, int64_t* counts,
-                        hipStream_t st);
+hipError_t launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float edge_threshold, const float* image,
+                            float* mask, void* scratch, hipStream_t st);
+hipError_t launch_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch,
+                               float* median, int32_t* count, hipStream_t st);
+hipError_t launch_covisibility(int64_t P, const int32_t* n_touched, const olsr_covis_views& views, uint8_t* cur_out,
+                               int64_t* counts, hipStream_t st);
 void launch_keyframe_decide(const olsr_keyframe_decide_params& p, const int64_t* counts, const float* median,
                             const float* cur_pose, const float* kf_poses, void* record, hipStream_t st);
 

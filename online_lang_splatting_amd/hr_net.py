@@ -10,9 +10,8 @@ from collections import OrderedDict
 
 import torch
 
-from . import _abi
+from . import _abi, _flat_state
 from ._lib import check, lib
-from .lang_query import CHECKPOINT_PREFIX
 
 N_PACKED = _abi.HR_NET_PARAMS
 C_FV, C_F3, C_F2, C_OUT = _abi.HR_NET_CHANNELS
@@ -63,18 +62,9 @@ def load_hr_state(flat, state):
     """Packs a HighResLanguageFeatureNet into `flat`.  `state` is a Lightning checkpoint of LangSupervisedNet
     ({"state_dict": {"model.initial_conv.0.weight": ...}}), its state_dict, or a plain module state dict; num_batches_tracked
     is ignored, every other name and shape must be the module's."""
-    if not isinstance(state, dict):
-        raise RuntimeError(f"hr_net: a checkpoint or state dict is expected, got {type(state).__name__}")
-    if "state_dict" in state and isinstance(state["state_dict"], dict):
-        state = state["state_dict"]
-    if any(k.startswith(CHECKPOINT_PREFIX) for k in state):
-        state = {k[len(CHECKPOINT_PREFIX):]: v for k, v in state.items() if k.startswith(CHECKPOINT_PREFIX)}
-    state = {k: v for k, v in state.items() if not k.endswith("num_batches_tracked")}
-    want = dict(_abi.HR_NET_STATE)
-    missing, extra = sorted(set(want) - set(state)), sorted(set(state) - set(want))
-    if missing or extra:
-        raise RuntimeError(f"hr_net: state with missing keys {missing}, unexpected keys {extra}")
-    for k, shape in want.items():
+    state = _flat_state.unwrap(state, "hr_net")
+    # (the shape check stays here: this one also names a value that is no tensor)
+    for k, shape in _flat_state.check_keys(state, _abi.HR_NET_STATE, "hr_net", "state").items():
         if not isinstance(state[k], torch.Tensor) or tuple(state[k].shape) != tuple(shape):
             got = tuple(state[k].shape) if isinstance(state[k], torch.Tensor) else type(state[k]).__name__
             raise RuntimeError(f"hr_net: {k} has shape {got}, expected {tuple(shape)} (the channel widths are compiled into "

@@ -12,7 +12,7 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _abi
+from . import _abi, _flat_state
 from ._lib import check, lib
 
 LAYOUTS = {"rows": _abi.LANG_AE_CODES_ROWS, "channels": _abi.LANG_AE_CODES_CHANNELS}
@@ -35,32 +35,17 @@ def _rows(name, t, width, dev):
     return t.detach().contiguous()
 
 
+_WHAT = ("flat parameter array", "state_dict")
+
+
 def state_views(flat):
     """name -> view of a flat [2351] tensor in the module's shape, in state_dict order."""
-    if flat.dim() != 1 or flat.numel() != _abi.LANG_AE_PARAMS:
-        raise RuntimeError(f"lang_codec: the flat parameter array has {_abi.LANG_AE_PARAMS} elements, got {tuple(flat.shape)}")
-    out, off = OrderedDict(), 0
-    for name, shape in _abi.LANG_AE_STATE:
-        n = 1
-        for s_ in shape:
-            n *= s_
-        out[name] = flat[off:off + n].view(shape)
-        off += n
-    return out
+    return _flat_state.views(flat, _abi.LANG_AE_STATE, "lang_codec", _WHAT[0])
 
 
 def load_state(flat, state):
     """Copies a state_dict of EncoderDecoderOnline into a flat [2351] tensor; keys and shapes must be the module's."""
-    want = dict(_abi.LANG_AE_STATE)
-    missing, extra = sorted(set(want) - set(state)), sorted(set(state) - set(want))
-    if missing or extra:
-        raise RuntimeError(f"lang_codec: state_dict with missing keys {missing}, unexpected keys {extra}")
-    for k, shape in want.items():
-        if tuple(state[k].shape) != tuple(shape):
-            raise RuntimeError(f"lang_codec: {k} has shape {tuple(state[k].shape)}, expected {tuple(shape)} "
-                               "(the sizes 32 / 24 / 15 are compiled into the kernels)")
-    for k, v in state_views(flat).items():
-        v.copy_(state[k].detach().to(device=flat.device, dtype=flat.dtype))
+    _flat_state.load(flat, state, _abi.LANG_AE_STATE, "lang_codec", _WHAT, "the sizes 32 / 24 / 15 are compiled into the kernels")
 
 
 class OnlineLanguageCodec:

@@ -12,10 +12,10 @@ from typing import Tuple
 
 import torch
 
-from . import _abi
+from . import _abi, _flat_state
 from ._lib import check, lib
 from .lang_codec import OnlineLanguageCodec, _layout
-from .lang_query import CHECKPOINT_PREFIX
+from ._flat_state import CHECKPOINT_PREFIX
 
 N_ENCODER = _abi.LANG_ENCODER_PARAMS
 FEATURE_DIM = _abi.LANG_ENCODER_WIDTHS[0]
@@ -23,41 +23,20 @@ OUT_DIM = _abi.LANG_ENCODER_WIDTHS[-1]
 BN_EPS = 1e-5   # nn.BatchNorm1d's default, what the reference's module carries
 
 
+_WHAT = ("flat encoder array", "encoder state")
+
+
 def encoder_views(flat):
     """name -> view of a flat [572128] tensor in the shapes of AutoencoderMLP.encoder, in state_dict order."""
-    if flat.dim() != 1 or flat.numel() != N_ENCODER:
-        raise RuntimeError(f"lang_encoder: the flat encoder array has {N_ENCODER} elements, got {tuple(flat.shape)}")
-    out, off = OrderedDict(), 0
-    for name, shape in _abi.LANG_ENCODER_STATE:
-        n = 1
-        for s_ in shape:
-            n *= s_
-        out[name] = flat[off:off + n].view(shape)
-        off += n
-    return out
+    return _flat_state.views(flat, _abi.LANG_ENCODER_STATE, "lang_encoder", _WHAT[0])
 
 
 def load_encoder_state(flat, state):
     """Copies the encoder of an AutoencoderMLP into a flat [572128] tensor.  `state` is a Lightning checkpoint
     ({"state_dict": {"model.encoder.0.weight": ...}}), its state_dict, or a plain AutoencoderMLP state dict; decoder entries
     and num_batches_tracked are ignored, the encoder's names and shapes must be the module's."""
-    if not isinstance(state, dict):
-        raise RuntimeError(f"lang_encoder: a checkpoint or state dict is expected, got {type(state).__name__}")
-    if "state_dict" in state and isinstance(state["state_dict"], dict):
-        state = state["state_dict"]
-    if any(k.startswith(CHECKPOINT_PREFIX) for k in state):
-        state = {k[len(CHECKPOINT_PREFIX):]: v for k, v in state.items() if k.startswith(CHECKPOINT_PREFIX)}
-    enc = {k: v for k, v in state.items() if k.startswith("encoder.") and not k.endswith("num_batches_tracked")}
-    want = dict(_abi.LANG_ENCODER_STATE)
-    missing, extra = sorted(set(want) - set(enc)), sorted(set(enc) - set(want))
-    if missing or extra:
-        raise RuntimeError(f"lang_encoder: encoder state with missing keys {missing}, unexpected keys {extra}")
-    for k, shape in want.items():
-        if tuple(enc[k].shape) != tuple(shape):
-            raise RuntimeError(f"lang_encoder: {k} has shape {tuple(enc[k].shape)}, expected {tuple(shape)} "
-                               f"(the widths {_abi.LANG_ENCODER_WIDTHS} are compiled into the kernel)")
-    for k, v in encoder_views(flat).items():
-        v.copy_(enc[k].detach().to(device=flat.device, dtype=flat.dtype))
+    _flat_state.load(flat, state, _abi.LANG_ENCODER_STATE, "lang_encoder", _WHAT,
+                     f"the widths {_abi.LANG_ENCODER_WIDTHS} are compiled into the kernel", CHECKPOINT_PREFIX, "encoder.")
 
 
 class LanguageEncoder:

@@ -14,50 +14,29 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _abi
+from . import _abi, _flat_state
+from ._flat_state import CHECKPOINT_PREFIX
 from ._lib import check, lib
 from .lang_codec import OnlineLanguageCodec
 
 N_DECODER = _abi.LANG_QUERY_DECODER_PARAMS
 FEATURE_DIM = _abi.LANG_QUERY_FEATURE_DIM
-CHECKPOINT_PREFIX = "model."   # AutoencoderLight keeps the AutoencoderMLP as self.model
+
+
+_WHAT = ("flat decoder array", "decoder state")
 
 
 def decoder_views(flat):
     """name -> view of a flat [745536] tensor in the shapes of AutoencoderMLP.decoder, in state_dict order."""
-    if flat.dim() != 1 or flat.numel() != N_DECODER:
-        raise RuntimeError(f"lang_query: the flat decoder array has {N_DECODER} elements, got {tuple(flat.shape)}")
-    out, off = OrderedDict(), 0
-    for name, shape in _abi.LANG_QUERY_STATE:
-        n = 1
-        for s_ in shape:
-            n *= s_
-        out[name] = flat[off:off + n].view(shape)
-        off += n
-    return out
+    return _flat_state.views(flat, _abi.LANG_QUERY_STATE, "lang_query", _WHAT[0])
 
 
 def load_decoder_state(flat, state):
     """Copies the decoder of an AutoencoderMLP into a flat [745536] tensor.  `state` is a Lightning checkpoint
     ({"state_dict": {"model.decoder.0.weight": ...}}, what load_from_checkpoint reads), its state_dict, or a plain
     AutoencoderMLP state dict; encoder and BatchNorm entries are ignored, the decoder's names and shapes must be the module's."""
-    if not isinstance(state, dict):
-        raise RuntimeError(f"lang_query: a checkpoint or state dict is expected, got {type(state).__name__}")
-    if "state_dict" in state and isinstance(state["state_dict"], dict):
-        state = state["state_dict"]
-    if any(k.startswith(CHECKPOINT_PREFIX) for k in state):
-        state = {k[len(CHECKPOINT_PREFIX):]: v for k, v in state.items() if k.startswith(CHECKPOINT_PREFIX)}
-    dec = {k: v for k, v in state.items() if k.startswith("decoder.")}
-    want = dict(_abi.LANG_QUERY_STATE)
-    missing, extra = sorted(set(want) - set(dec)), sorted(set(dec) - set(want))
-    if missing or extra:
-        raise RuntimeError(f"lang_query: decoder state with missing keys {missing}, unexpected keys {extra}")
-    for k, shape in want.items():
-        if tuple(dec[k].shape) != tuple(shape):
-            raise RuntimeError(f"lang_query: {k} has shape {tuple(dec[k].shape)}, expected {tuple(shape)} "
-                               f"(the widths {_abi.LANG_QUERY_WIDTHS} are compiled into the kernels)")
-    for k, v in decoder_views(flat).items():
-        v.copy_(dec[k].detach().to(device=flat.device, dtype=flat.dtype))
+    _flat_state.load(flat, state, _abi.LANG_QUERY_STATE, "lang_query", _WHAT,
+                     f"the widths {_abi.LANG_QUERY_WIDTHS} are compiled into the kernels", CHECKPOINT_PREFIX, "decoder.")
 
 
 class LanguageDecoder:
