@@ -22,9 +22,9 @@
  *
  * Contents: the rasterizer itself (olsr_forward, olsr_forward_async, olsr_backward, olsr_mark_visible and
  * their size / introspection / profiling helpers — SURVEY.md section 8 rows a-e), then the callers and
- * data either side of it (rows f1-f3): olsr_mapping_loss, olsr_tracking_loss, olsr_pose_step,
+ * data either side of it (rows f1-f3): olsr_mapping_loss, olsr_tracking_loss, olsr_pose_step, olsr_window_pose_step,
  * olsr_accumulate_gradients, olsr_sparse_exchange_mask / _pack / _unpack, olsr_adam_step (and its per-group form
- * olsr_adam_step_groups), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2,
+ * olsr_adam_step_groups, olsr_adam_step_groups_reg with olsr_isotropic_reg), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2,
  * olsr_keyframe_seed_plan / _finish (a keyframe's new Gaussians from its RGB-D image), olsr_grad_mask, olsr_median_depth,
  * olsr_covisibility and olsr_keyframe_decide (the front end's frame step around the tracking loop).
  */
@@ -447,6 +447,43 @@ int olsr_adam_step_groups(int32_t P, int32_t M, int32_t F, const olsr_adam_group
                           const float *const *flats, const uint64_t *const *row_masks, float *means3D, float *shs,
                           float *opacities, float *scales, float *rotations, float *language, float *exp_avg,
                           float *exp_avg_sq, void *hip_stream);
+
+/* ---- the isotropic regulariser of the mapping loss (csrc/k_adam.hip) -------------------------------------------------
+ * The reference adds `10 * |scaling - scaling.mean(dim=1)|.mean()` to every mapping iteration's loss
+ * (utils/slam_backend.py:664-667, scaling = exp(_scaling)); autograd then adds its gradient to _scaling.grad.  It is a
+ * function of a Gaussian's own three scales, so the Adam step that already owns the row forms it itself
+ * (olsr_adam_step_groups_reg: no extra pass); olsr_isotropic_reg is the same statement on its own, with the loss value.
+ * Arithmetic, float32 unless stated, for row g with the parameter values x_k read BEFORE the step:
+ *   s_k  = (activations & OLSR_ACT_SCALE_EXP) ? expf(x_k) : x_k          (the expf of the preprocess kernel)
+ *   m    = ((s_0 + s_1) + s_2) / 3.0f,   d_k = s_k - m,   sg_k = (d_k > 0) - (d_k < 0)
+ *   q_k  = 3 sg_k - (sg_0 + sg_1 + sg_2)                                  (an integer, |q| <= 4)
+ *   w9   = (float)(weight / (9.0 * P_total))                              (formed in double on the host)
+ *   r_k  = w9 * (float)q_k, once more times s_k when the parameter is raw — autograd's weight / (3 P) (sg_k - mean_j sg_j)
+ *          through exp
+ *   loss = weight / (3 P) * sum |d_k|: the sum in double in a fixed order (a row ((|d_0| + |d_1|) + |d_2|), rows per wave,
+ *          waves per block, blocks), the same bits on every run.
+ * A NaN scale is outside the contract: every comparison with it is false, so its row's r is +-0 (NaN on the NaN element
+ * itself in raw mode) and the loss is NaN.
+ *   grad     device float[P,3] (assigned) or NULL;  loss  device double[1] or NULL;  scratch: olsr_isotropic_reg_scratch_bytes(P),
+ *            needed with loss.  P_total of the standalone entry is P.  OLSR_ERR_ARG: P < 0, NULL scales, activations outside
+ *            OLSR_ACT_*, loss without scratch. */
+size_t olsr_isotropic_reg_scratch_bytes(int32_t P);
+int olsr_isotropic_reg(int32_t P, const float *scales, int32_t activations, double weight, float *grad, double *loss,
+                       void *scratch, void *hip_stream);
+/* olsr_adam_step_groups with the regulariser inside: the gradient of a scale element is (((f0 + f1) + ...) + r_k), the
+ * regulariser added last — the bits of olsr_adam_step_groups fed one EXTRA bucket that holds olsr_isotropic_reg's gradient
+ * in its scale columns and +0.0 elsewhere.  A clear row-mask bit still skips that row's bucket reads, not r_k; a skipped
+ * scale group takes no regulariser.  P_total >= P (OLSR_ERR_ARG otherwise) keeps the 1 / P of the whole map when a row
+ * range is stepped.  reg == NULL or isotropic_weight == 0: olsr_adam_step_groups itself, bit for bit. */
+typedef struct olsr_adam_reg {
+  double isotropic_weight; /* 10 in the reference */
+  int32_t activations;     /* OLSR_ACT_* of the scene: OLSR_ACT_SCALE_EXP = `scales` holds log(scale) */
+  int32_t P_total;
+} olsr_adam_reg;
+int olsr_adam_step_groups_reg(int32_t P, int32_t M, int32_t F, const olsr_adam_group_params *params, int32_t n_flats,
+                              const float *const *flats, const uint64_t *const *row_masks, float *means3D, float *shs,
+                              float *opacities, float *scales, float *rotations, float *language, float *exp_avg,
+                              float *exp_avg_sq, const olsr_adam_reg *reg, void *hip_stream);
 
 /* ---- map edits: densify, prune and extend the Gaussian map on the fused buffers (csrc/k_map_edit.hip) --------------
  * One primitive behind GaussianModel.densify_and_prune / prune_points / extend_from_pcd
@@ -1126,6 +1163,33 @@ int olsr_pose_step(const olsr_pose_params *params, const float *dL_dtau_sum, con
 int olsr_pose_step_gated(const olsr_pose_params *params, const float *dL_dtau_sum, const float *dL_dexposure,
                          const float *projection_matrix, float *state, int32_t *status, const int32_t *frame_status,
                          void *hip_stream);
+
+/* ---- mapping's bundle adjustment: every window keyframe's pose and exposure step in ONE launch ----------------------
+ * The reference's back end builds one torch.optim.Adam (`keyframe_optimizers`, utils/slam_backend.py:933-980) at every new
+ * keyframe: cam_rot_delta / cam_trans_delta of the first `pose_window` window keyframes at HALF the tracking rates,
+ * exposure_a / exposure_b of every window keyframe at 0.01, nothing for frame 0; after each mapping iteration's backward
+ * it runs keyframe_optimizers.step() and update_pose(viewpoint) for those first views (:756-765).  Here: one wave per view,
+ * the launch shape depends on V only.  state [V,80] and status [V,2] in olsr_pose_step's layout, projection_matrix shared.
+ * params->step > 0 is one host-side count for all views; <= 0 uses each view's own status[v][1] + 1.  Per view v, flags[v]:
+ *   POSE | EXPOSURE  the bits of olsr_pose_step_gated(params, dL_dtau_sum + 6 v, dL_dexposure + 2 v, projection_matrix,
+ *                    state + 80 v, status + 2 v, frame_status ? frame_status + 2 v : NULL)
+ *   POSE             the same call with dL_dexposure == NULL
+ *   EXPOSURE         (a window keyframe beyond pose_window) only words 70..75 change, by the same Adam arithmetic; words
+ *                    0..15 and 52..69 keep their bits; the matrices are re-derived; status[v][0] = 0, status[v][1] += 1
+ *   0                (frame 0, rehearsal views) as dL_dtau_sum == NULL: only the re-derived matrices are written, no count
+ * frame_status[2 v + 1] != 0 gates view v alone, as in the single call.  A view's flags must not change between resets of
+ * its state and status: the step count is shared by its groups, so a group that joined late would run on the bias
+ * corrections of the others' count (the reference builds a fresh optimiser instead: KeyframeWindow.rebuild).
+ * OLSR_ERR_ARG before any launch: V outside 1 ... OLSR_WINDOW_MAX_VIEWS, unknown flag bits, NULL params, flags, state, status
+ * or projection_matrix, a NULL gradient array that some flag needs. */
+#define OLSR_WINDOW_MAX_VIEWS 32
+#define OLSR_WINDOW_OPT_POSE 1
+#define OLSR_WINDOW_OPT_EXPOSURE 2
+int olsr_window_pose_step(const olsr_pose_params *params, int32_t V, const int32_t *flags /* host int32[V] */,
+                          const float *dL_dtau_sum /* device [V,6] */, const float *dL_dexposure /* device [V,2] */,
+                          const float *projection_matrix /* device [16], shared */, float *state /* device [V,80] */,
+                          int32_t *status /* device [V,2] */, const int32_t *frame_status /* device [V,2] or NULL */,
+                          void *hip_stream);
 
 /* Adds one view's per-Gaussian gradients into the flat fp32 buffer
  *   flat[P][3 xyz | 3M sh | 1 opacity | 3 scale | 4 rotation | F language]

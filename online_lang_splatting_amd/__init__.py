@@ -20,8 +20,10 @@ from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_dist
                             emd_segments, evaluate_classes)                            # Chamfer and earth mover's distances)
 from .keyframe_seed import seed_rows  # noqa: F401,E402  (a keyframe's new Gaussians from its RGB-D image, on the device)
 from .frontend import KeyframeSelector, median_depth, tracking_mask  # noqa: F401,E402  (the front end's frame step)
+from .slam_iterations import KeyframeWindow  # noqa: F401,E402  (mapping's bundle adjustment: window poses and exposures)
+from .losses import isotropic_loss  # noqa: F401,E402  (the mapping loss's isotropic regulariser)
 
-__all__ = ["render", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

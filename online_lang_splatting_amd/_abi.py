@@ -97,6 +97,15 @@ class OlsrAdamGroupParams(C.Structure):
     _fields_ = [("base", OlsrAdamParams), ("group_step", C.c_int32 * 7), ("skip_mask", C.c_int32)]
 
 
+class OlsrAdamReg(C.Structure):
+    """struct olsr_adam_reg, include/olsr.h."""
+
+    _fields_ = [("isotropic_weight", C.c_double), ("activations", C.c_int32), ("P_total", C.c_int32)]
+
+
+# olsr_window_pose_step (OLSR_WINDOW_*)
+WINDOW_MAX_VIEWS, WINDOW_OPT_POSE, WINDOW_OPT_EXPOSURE = 32, 1, 2
+
 # OLSR_ADAM_GROUP_*: the reference's parameter groups (gaussian_model.py training_setup) in bucket-column order
 ADAM_GROUPS = ("xyz", "f_dc", "f_rest", "opacity", "scaling", "rotation", "f_language")
 

@@ -50,18 +50,66 @@ struct AdamBuckets {
   const unsigned long long* mask_more[OLSR_ADAM_MAX_BUCKETS - 1];
 };
 
+// The isotropic regulariser of the mapping loss (utils/slam_backend.py:664-667):
+//     loss_mapping += weight * |scaling - scaling.mean(dim=1)|.mean(),  scaling = exp(_scaling), weight = 10
+// as a function of one Gaussian's own three scales (include/olsr.h restates the arithmetic).  x: the parameter values
+// BEFORE the step; r: the gradient with respect to x; d: s_k - m.  A NaN scale is outside the contract: every comparison
+// with it is false, so the row's sign terms are all zero — r is +-0 (NaN on the NaN element itself in raw mode) and the
+// loss NaN.
+struct AdamReg {
+  float w9;  // (float)(weight / (9 P_total)), formed in double on the host
+  int raw;   // the parameter is log(scale) (OLSR_ACT_SCALE_EXP)
+};
+__device__ __forceinline__ void isotropic_row(const float x[3], int raw, float w9, float r[3], float d[3]) {
+  float s[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s[k] = raw ? expf(x[k]) : x[k];
+  const float m = ((s[0] + s[1]) + s[2]) / 3.0f;
+  int sg[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    d[k] = s[k] - m;
+    sg[k] = (d[k] > 0.f) - (d[k] < 0.f);
+  }
+  const int ssum = sg[0] + sg[1] + sg[2];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+    float rk = w9 * (float)(3 * sg[k] - ssum);
+    if (raw) rk = rk * s[k];
+    r[k] = rk;
+  }
+}
+
 // GROUPS = false: one step count for every group (olsr_adam_step / _sum / _masked, unchanged); true: the per-group form, the
-// same arithmetic with the group's own sqrt(bias_correction2) and a skip bit per group
-template <bool GROUPS>
+// same arithmetic with the group's own sqrt(bias_correction2) and a skip bit per group.
+// REG (olsr_adam_step_groups_reg): the isotropic regulariser's gradient is added last to the gradient of every scale element.
+// The loop below is element-parallel — the thread that writes scales[g][0] runs beside the threads that need its old value
+// for the row's mean — so the block first forms r of its 64 Gaussians from the pre-step scales into LDS, behind a barrier,
+// before any element of the block is written (blocks own disjoint Gaussians).
+template <bool GROUPS, bool REG>
 __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int width, const float* __restrict__ flat,
                                                         AdamBuckets extra,
                                                         float* __restrict__ means3D, float* __restrict__ shs,
                                                         float* __restrict__ opacities, float* __restrict__ scales,
                                                         float* __restrict__ rotations, float* __restrict__ language,
                                                         float* __restrict__ exp_avg, float* __restrict__ exp_avg_sq,
-                                                        AdamScalars hp, AdamGroupScalars gp) {
+                                                        AdamScalars hp, AdamGroupScalars gp, AdamReg reg) {
   const int g0 = blockIdx.x * ADAM_G;
   const int ng = min(ADAM_G, P - g0);
+  __shared__ float s_reg[REG ? 3 * ADAM_G : 1];
+  if constexpr (REG) {
+    if (!((gp.skip_mask >> OLSR_ADAM_GROUP_SCALE) & 1u)) {   // (a skipped scale group takes no regulariser)
+      if ((int)threadIdx.x < ng) {
+        const size_t g = (size_t)(g0 + (int)threadIdx.x);
+        const float x[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
+        float r[3], d[3];
+        isotropic_row(x, reg.raw, reg.w9, r, d);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) s_reg[3 * threadIdx.x + k] = r[k];
+      }
+      __syncthreads();
+    }
+  }
   const int count = ng * width;
   const int sh_w = 3 * M;
   const float inv_w = 1.0f / (float)width;
@@ -95,6 +143,8 @@ __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int
 #pragma unroll
     for (int b = 0; b < OLSR_ADAM_MAX_BUCKETS - 1; ++b)
       if ((wm[b] >> gl) & 1ull) grad += extra.more[b][base + e];
+    if constexpr (REG)
+      if (group == OLSR_ADAM_GROUP_SCALE) grad += s_reg[3 * gl + (c - 4 - sh_w)];
     float m = exp_avg[base + e], v = exp_avg_sq[base + e];
     m = m + (grad - m) * hp.one_minus_beta1;              // exp_avg.lerp_(grad, 1 - beta1)
     v = v * hp.beta2 + hp.one_minus_beta2 * grad * grad;  // exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
@@ -107,7 +157,8 @@ __global__ __launch_bounds__(256) void adam_step_kernel(int P, int M, int F, int
 
 void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const float* const* flats,
                       const unsigned long long* const* masks, int n_flats, float* means3D, float* shs, float* opacities, float* scales, float* rotations, float* language,
-                      float* exp_avg, float* exp_avg_sq, hipStream_t st, const int32_t* group_step, unsigned skip_mask) {
+                      float* exp_avg, float* exp_avg_sq, hipStream_t st, const int32_t* group_step, unsigned skip_mask,
+                      const olsr_adam_reg* reg) {
   if (P <= 0) return;
   const float* flat = flats[0];
   AdamBuckets extra{};
@@ -136,8 +187,8 @@ void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const flo
   k.neg_step_language = (float)(-(hp.lr_language / bc1));
   AdamGroupScalars gk{};
   if (!group_step) {
-    adam_step_kernel<false><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
-                                                                       scales, rotations, language, exp_avg, exp_avg_sq, k, gk);
+    adam_step_kernel<false, false><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
+                                                                       scales, rotations, language, exp_avg, exp_avg_sq, k, gk, AdamReg{});
     return;
   }
   // per group: the same double arithmetic on the group's own step count (torch/optim/adam.py: step_t is per parameter)
@@ -159,8 +210,57 @@ void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const flo
   k.neg_step_scale = neg[OLSR_ADAM_GROUP_SCALE];
   k.neg_step_rotation = neg[OLSR_ADAM_GROUP_ROTATION];
   k.neg_step_language = neg[OLSR_ADAM_GROUP_LANGUAGE];
-  adam_step_kernel<true><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
-                                                                    scales, rotations, language, exp_avg, exp_avg_sq, k, gk);
+  if (reg && reg->isotropic_weight != 0.0) {
+    const AdamReg rk{(float)(reg->isotropic_weight / (9.0 * (double)reg->P_total)), (reg->activations & OLSR_ACT_SCALE_EXP) ? 1 : 0};
+    adam_step_kernel<true, true><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
+                                                                            scales, rotations, language, exp_avg, exp_avg_sq, k, gk, rk);
+    return;
+  }
+  adam_step_kernel<true, false><<<(P + ADAM_G - 1) / ADAM_G, 256, 0, st>>>(P, M, F, width, flat, extra, means3D, shs, opacities,
+                                                                           scales, rotations, language, exp_avg, exp_avg_sq, k, gk, AdamReg{});
+}
+
+// olsr_isotropic_reg: the regulariser on its own — gradient rows and, in double, the loss.  A thread per Gaussian; a row's
+// |d| are summed ((|d0| + |d1|) + |d2|), the rows of a wave by wave_sum, the four waves of a block in order, the blocks'
+// partial sums by one more block (single_block_sum): a fixed order, the same bits on every run.
+constexpr int ISO_T = 256;
+__global__ __launch_bounds__(ISO_T) void isotropic_reg_kernel(int P, const float* __restrict__ scales, AdamReg reg,
+                                                              float* __restrict__ grad, double* __restrict__ partials) {
+  __shared__ double s_w[ISO_T / 64];
+  const size_t g = (size_t)blockIdx.x * ISO_T + threadIdx.x;
+  double a = 0.0;
+  if (g < (size_t)P) {
+    const float x[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
+    float r[3], d[3];
+    isotropic_row(x, reg.raw, reg.w9, r, d);
+    if (grad) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) grad[3 * g + k] = r[k];
+    }
+    a = ((double)fabsf(d[0]) + (double)fabsf(d[1])) + (double)fabsf(d[2]);
+  }
+  if (!partials) return;   // (uniform over the launch)
+  a = wave_sum(a);
+  if (lane_id() == 0) s_w[threadIdx.x >> 6] = a;
+  __syncthreads();
+  if (threadIdx.x == 0) partials[blockIdx.x] = ((s_w[0] + s_w[1]) + s_w[2]) + s_w[3];
+}
+__global__ __launch_bounds__(ISO_T) void isotropic_loss_kernel(int nb, const double* __restrict__ partials, double scale,
+                                                               double* __restrict__ loss) {
+  __shared__ double s_w[ISO_T / 64];
+  const double tot = single_block_sum<ISO_T / 64>(nb, partials, s_w);
+  if (threadIdx.x == 0) *loss = scale * tot;
+}
+
+size_t isotropic_reg_scratch_bytes(int P) { return (size_t)((P > 0 ? P : 0) + ISO_T - 1) / ISO_T * sizeof(double) + sizeof(double); }
+
+void launch_isotropic_reg(int P, const float* scales, int activations, double weight, float* grad, double* loss,
+                          void* scratch, hipStream_t st) {
+  const int nb = (P + ISO_T - 1) / ISO_T;
+  const AdamReg rk{(float)(weight / (9.0 * (double)P)), (activations & OLSR_ACT_SCALE_EXP) ? 1 : 0};
+  double* partials = loss ? reinterpret_cast<double*>(scratch) : nullptr;
+  isotropic_reg_kernel<<<nb, ISO_T, 0, st>>>(P, scales, rk, grad, partials);
+  if (loss) isotropic_loss_kernel<<<1, ISO_T, 0, st>>>(nb, partials, weight / (3.0 * (double)P), loss);
 }
 
 }  // namespace olsr

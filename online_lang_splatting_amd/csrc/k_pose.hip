@@ -29,32 +29,51 @@ struct PoseScalars {
   float one_minus_beta1, beta2, one_minus_beta2, bias_correction2_sqrt, eps;
   float neg_step_rot, neg_step_trans, neg_step_exposure, converged_threshold;
   int has_grad, has_exposure;
+  // exposure_only (olsr_window_pose_step, a window keyframe beyond pose_window): the exposure pair takes its Adam step and
+  // the step counts, the pose and the moments of tau keep their bits; never set together with has_grad
+  int exposure_only;
   // step_on_device: the Adam step count is status[1] + 1 (params->step <= 0), so that the same launch can be replayed
   // from a HIP graph; the bias corrections are then formed here, in double like launch_pose_step forms them on the host
   int step_on_device;
   double beta1_d, beta2_d, lr_rot_d, lr_trans_d, lr_exposure_d;
 };
 
+// Adam on the exposure pair: state words 70..75
+__device__ __forceinline__ void pose_exposure_adam(const PoseScalars& hp, const float* __restrict__ dL_dexposure,
+                                                   float* __restrict__ state) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const float grad = dL_dexposure[i];
+    float m = state[72 + i], v = state[74 + i];
+    m = m + (grad - m) * hp.one_minus_beta1;
+    v = v * hp.beta2 + hp.one_minus_beta2 * grad * grad;
+    const float denom = sqrtf(v) / hp.bias_correction2_sqrt + hp.eps;
+    state[70 + i] = state[70 + i] + hp.neg_step_exposure * (m / denom);
+    state[72 + i] = m;
+    state[74 + i] = v;
+  }
+}
+
 // state (floats): [0,16) T_w2c row-major | [16,32) world_view_transform = W2C^T | [32,48) full_proj_transform |
 // [48,52) camera_center + pad | [52,58) exp_avg of tau = [trans | rot] | [58,64) exp_avg_sq | [64,70) tau applied by
 // the last step | [70,72) exposure a, b | [72,74) their exp_avg | [74,76) exp_avg_sq | [76,80) pad
-__global__ __launch_bounds__(64) void pose_step_kernel(PoseScalars hp, const float* __restrict__ dL_dtau_sum,
-                                                       const float* __restrict__ dL_dexposure,
-                                                       const float* __restrict__ proj, float* __restrict__ state,
-                                                       int32_t* __restrict__ status,
-                                                       const int32_t* __restrict__ frame_status) {
-  if (threadIdx.x != 0) return;
+// one view's step, by one thread: the body of olsr_pose_step and, per view, of olsr_window_pose_step
+__device__ __forceinline__ void pose_step_view(PoseScalars hp, const float* __restrict__ dL_dtau_sum,
+                                               const float* __restrict__ dL_dexposure, const float* __restrict__ proj,
+                                               float* __restrict__ state, int32_t* __restrict__ status,
+                                               const int32_t* __restrict__ frame_status) {
   // olsr_pose_step_gated: the frame the gradient came from was not usable (overflow, synchronisation error, depth cut-off
   // miss) — no optimiser step, nothing of the state changes, the matrices are re-derived from the pose as it is
   if (frame_status != nullptr && frame_status[1] != 0) {
     hp.has_grad = 0;
+    hp.exposure_only = 0;
     status[0] = 0;
   }
   float T[16];
 #pragma unroll
   for (int i = 0; i < 16; ++i) T[i] = state[i];
   float tau[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  if (hp.has_grad && hp.step_on_device) {
+  if ((hp.has_grad || hp.exposure_only) && hp.step_on_device) {
     const double step = (double)(status[1] + 1);
     const double bc1 = 1.0 - pow(hp.beta1_d, step);
     const double bc2 = 1.0 - pow(hp.beta2_d, step);
@@ -62,6 +81,11 @@ __global__ __launch_bounds__(64) void pose_step_kernel(PoseScalars hp, const flo
     hp.neg_step_rot = (float)(-(hp.lr_rot_d / bc1));
     hp.neg_step_trans = (float)(-(hp.lr_trans_d / bc1));
     hp.neg_step_exposure = (float)(-(hp.lr_exposure_d / bc1));
+  }
+  if (hp.exposure_only) {
+    pose_exposure_adam(hp, dL_dexposure, state);
+    status[0] = 0;
+    status[1] = status[1] + 1;
   }
   if (hp.has_grad) {
     // the rasterizer's dL_dtau is [rho | theta] (DGR/diff_gaussian_rasterization/__init__.py:383-385): rho is the
@@ -77,19 +101,7 @@ __global__ __launch_bounds__(64) void pose_step_kernel(PoseScalars hp, const flo
       state[52 + i] = m;
       state[58 + i] = v;
     }
-    if (hp.has_exposure) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const float grad = dL_dexposure[i];
-        float m = state[72 + i], v = state[74 + i];
-        m = m + (grad - m) * hp.one_minus_beta1;
-        v = v * hp.beta2 + hp.one_minus_beta2 * grad * grad;
-        const float denom = sqrtf(v) / hp.bias_correction2_sqrt + hp.eps;
-        state[70 + i] = state[70 + i] + hp.neg_step_exposure * (m / denom);
-        state[72 + i] = m;
-        state[74 + i] = v;
-      }
-    }
+    if (hp.has_exposure) pose_exposure_adam(hp, dL_dexposure, state);
     // SE3_exp(tau): rho = tau[:3], theta = tau[3:]
     const float tx = tau[3], ty = tau[4], tz = tau[5];
     const float W[9] = {0.f, -tz, ty, tz, 0.f, -tx, -ty, tx, 0.f};  // skew_sym_mat
@@ -181,8 +193,38 @@ __global__ __launch_bounds__(64) void pose_step_kernel(PoseScalars hp, const flo
   state[51] = 0.f;
 }
 
-void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,
-                      float* state, int32_t* status, const int32_t* frame_status, hipStream_t st) {
+__global__ __launch_bounds__(64) void pose_step_kernel(PoseScalars hp, const float* __restrict__ dL_dtau_sum,
+                                                       const float* __restrict__ dL_dexposure,
+                                                       const float* __restrict__ proj, float* __restrict__ state,
+                                                       int32_t* __restrict__ status,
+                                                       const int32_t* __restrict__ frame_status) {
+  if (threadIdx.x != 0) return;
+  pose_step_view(hp, dL_dtau_sum, dL_dexposure, proj, state, status, frame_status);
+}
+
+// olsr_window_pose_step: workgroup v = one wave = view v of the mapping window, the step above on its own 80 floats.  The
+// reference runs ONE torch.optim.Adam over every window keyframe's increments and exposures and update_pose per view
+// (utils/slam_backend.py:756-765); the views do not depend on each other, so they step side by side in one launch.
+struct WindowFlags {
+  int32_t f[OLSR_WINDOW_MAX_VIEWS];
+};
+__global__ __launch_bounds__(64) void window_pose_step_kernel(PoseScalars hp, WindowFlags flags,
+                                                              const float* __restrict__ dL_dtau_sum,
+                                                              const float* __restrict__ dL_dexposure,
+                                                              const float* __restrict__ proj, float* __restrict__ state,
+                                                              int32_t* __restrict__ status,
+                                                              const int32_t* __restrict__ frame_status) {
+  if (threadIdx.x != 0) return;
+  const int v = (int)blockIdx.x;
+  const int fl = flags.f[v];
+  hp.has_grad = (fl & OLSR_WINDOW_OPT_POSE) ? 1 : 0;
+  hp.has_exposure = (fl & OLSR_WINDOW_OPT_EXPOSURE) ? 1 : 0;
+  hp.exposure_only = (!hp.has_grad && hp.has_exposure) ? 1 : 0;
+  pose_step_view(hp, hp.has_grad ? dL_dtau_sum + 6 * v : nullptr, hp.has_exposure ? dL_dexposure + 2 * v : nullptr, proj,
+                 state + 80 * v, status + 2 * v, frame_status ? frame_status + 2 * v : nullptr);
+}
+
+static PoseScalars pose_scalars(const olsr_pose_params& p) {
   PoseScalars k{};
   const int step = p.step > 0 ? p.step : 1;
   const double bc1 = 1.0 - pow(p.beta1, (double)step);
@@ -196,14 +238,29 @@ void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const
   k.neg_step_trans = (float)(-(p.lr_trans / bc1));
   k.neg_step_exposure = (float)(-(p.lr_exposure / bc1));
   k.converged_threshold = (float)p.converged_threshold;
-  k.has_grad = dL_dtau_sum != nullptr;
-  k.has_exposure = dL_dexposure != nullptr;
   k.step_on_device = (p.step <= 0) ? 1 : 0;
   k.beta1_d = p.beta1;
   k.beta2_d = p.beta2;
   k.lr_rot_d = p.lr_rot;
   k.lr_trans_d = p.lr_trans;
   k.lr_exposure_d = p.lr_exposure;
+  return k;
+}
+
+void launch_window_pose_step(const olsr_pose_params& p, int V, const int32_t* flags, const float* dL_dtau_sum,
+                             const float* dL_dexposure, const float* proj, float* state, int32_t* status,
+                             const int32_t* frame_status, hipStream_t st) {
+  WindowFlags wf{};
+  for (int v = 0; v < V; ++v) wf.f[v] = flags[v];
+  window_pose_step_kernel<<<V, 64, 0, st>>>(pose_scalars(p), wf, dL_dtau_sum, dL_dexposure, proj, state, status,
+                                            frame_status);
+}
+
+void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,
+                      float* state, int32_t* status, const int32_t* frame_status, hipStream_t st) {
+  PoseScalars k = pose_scalars(p);
+  k.has_grad = dL_dtau_sum != nullptr;
+  k.has_exposure = dL_dexposure != nullptr;
   pose_step_kernel<<<1, 64, 0, st>>>(k, dL_dtau_sum, dL_dexposure, proj, state, status, frame_status);
 }
 

@@ -19,7 +19,8 @@ namespace {
 int adam_entry(const char* who, int32_t P, int32_t M, int32_t F, const olsr_adam_params* hp, const char* params_error,
                int32_t n_flats, const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
                float* opacities, float* scales, float* rotations, float* language, float* exp_avg, float* exp_avg_sq,
-               void* hip_stream, const int32_t* group_step = nullptr, unsigned skip_mask = 0u) {
+               void* hip_stream, const int32_t* group_step = nullptr, unsigned skip_mask = 0u,
+               const olsr_adam_reg* reg = nullptr) {
   if (P < 0 || M < 0 || !supported_F(F)) return fail(OLSR_ERR_ARG, "P, M must be >= 0 and F one of 0, 3, 15, 16, 32");
   if (params_error) return fail(OLSR_ERR_ARG, params_error);
   if (who) {
@@ -33,7 +34,8 @@ int adam_entry(const char* who, int32_t P, int32_t M, int32_t F, const olsr_adam
       (F > 0 && !language))
     return fail(OLSR_ERR_ARG, std::string(who ? "" : "the bucket, ") + "every parameter array and both moment buffers are required");
   launch_adam_step(P, M, F, *hp, flats, reinterpret_cast<const unsigned long long* const*>(row_masks), n_flats, means3D, shs,
-                   opacities, scales, rotations, language, exp_avg, exp_avg_sq, (hipStream_t)hip_stream, group_step, skip_mask);
+                   opacities, scales, rotations, language, exp_avg, exp_avg_sq, (hipStream_t)hip_stream, group_step, skip_mask,
+                   reg);
   return launch_check(who ? who : "adam_step");
 }
 
@@ -149,13 +151,63 @@ int olsr_adam_step_groups(int32_t P, int32_t M, int32_t F, const olsr_adam_group
                           const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
                           float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
                           float* exp_avg_sq, void* hip_stream) {
+  return olsr_adam_step_groups_reg(P, M, F, params, n_flats, flats, row_masks, means3D, shs, opacities, scales, rotations,
+                                   language, exp_avg, exp_avg_sq, nullptr, hip_stream);
+}
+
+int olsr_adam_step_groups_reg(int32_t P, int32_t M, int32_t F, const olsr_adam_group_params* params, int32_t n_flats,
+                              const float* const* flats, const uint64_t* const* row_masks, float* means3D, float* shs,
+                              float* opacities, float* scales, float* rotations, float* language, float* exp_avg,
+                              float* exp_avg_sq, const olsr_adam_reg* reg, void* hip_stream) {
   const char* params_error = params ? nullptr : "adam group params are required";
   for (int g = 0; params && g < OLSR_ADAM_GROUPS; ++g)
     if (!((params->skip_mask >> g) & 1) && params->group_step[g] < 1)
       params_error = "adam_step_groups: the step count of every group that steps must be >= 1";
+  if (reg && reg->isotropic_weight != 0.0) {
+    if (!std::isfinite(reg->isotropic_weight)) params_error = "adam_step_groups_reg: isotropic_weight must be finite";
+    if (reg->activations & ~7) params_error = "adam_step_groups_reg: activations outside OLSR_ACT_*";
+    if (reg->P_total < P || reg->P_total < 1) params_error = "adam_step_groups_reg: P_total must be >= P and >= 1";
+  }
   return adam_entry("adam_step_groups", P, M, F, params ? &params->base : nullptr, params_error, n_flats, flats, row_masks,
                     means3D, shs, opacities, scales, rotations, language, exp_avg, exp_avg_sq, hip_stream,
-                    params ? params->group_step : nullptr, params ? (unsigned)params->skip_mask : 0u);
+                    params ? params->group_step : nullptr, params ? (unsigned)params->skip_mask : 0u, reg);
+}
+
+size_t olsr_isotropic_reg_scratch_bytes(int32_t P) { return isotropic_reg_scratch_bytes(P); }
+
+int olsr_isotropic_reg(int32_t P, const float* scales, int32_t activations, double weight, float* grad, double* loss,
+                       void* scratch, void* hip_stream) {
+  if (P < 0) return fail(OLSR_ERR_ARG, "isotropic_reg: P must be >= 0");
+  if (activations & ~7) return fail(OLSR_ERR_ARG, "isotropic_reg: activations outside OLSR_ACT_*");
+  if (!std::isfinite(weight)) return fail(OLSR_ERR_ARG, "isotropic_reg: weight must be finite");
+  if (loss && !scratch) return fail(OLSR_ERR_ARG, "isotropic_reg: the loss needs scratch");
+  if (P > 0 && !scales) return fail(OLSR_ERR_ARG, "isotropic_reg: scales are required");
+  if (P == 0) {   // (the mean over no element: the loss is written as 0)
+    if (loss) HIP_TRY(hipMemsetAsync(loss, 0, sizeof(double), (hipStream_t)hip_stream));
+    return OLSR_OK;
+  }
+  if (!grad && !loss) return OLSR_OK;
+  launch_isotropic_reg(P, scales, activations, weight, grad, loss, scratch, (hipStream_t)hip_stream);
+  return launch_check("isotropic_reg");
+}
+
+int olsr_window_pose_step(const olsr_pose_params* params, int32_t V, const int32_t* flags, const float* dL_dtau_sum,
+                          const float* dL_dexposure, const float* projection_matrix, float* state, int32_t* status,
+                          const int32_t* frame_status, void* hip_stream) {
+  if (V < 1 || V > OLSR_WINDOW_MAX_VIEWS) return fail(OLSR_ERR_ARG, "window_pose_step: V must be between 1 and 32");
+  if (!params || !flags || !projection_matrix || !state || !status)
+    return fail(OLSR_ERR_ARG, "window_pose_step: pose params, flags, projection_matrix, state and status are required");
+  for (int v = 0; v < V; ++v) {
+    if (flags[v] & ~(OLSR_WINDOW_OPT_POSE | OLSR_WINDOW_OPT_EXPOSURE))
+      return fail(OLSR_ERR_ARG, "window_pose_step: unknown flag bits");
+    if ((flags[v] & OLSR_WINDOW_OPT_POSE) && !dL_dtau_sum)
+      return fail(OLSR_ERR_ARG, "window_pose_step: a view optimises its pose but dL_dtau_sum is NULL");
+    if ((flags[v] & OLSR_WINDOW_OPT_EXPOSURE) && !dL_dexposure)
+      return fail(OLSR_ERR_ARG, "window_pose_step: a view optimises its exposure but dL_dexposure is NULL");
+  }
+  launch_window_pose_step(*params, V, flags, dL_dtau_sum, dL_dexposure, projection_matrix, state, status, frame_status,
+                          (hipStream_t)hip_stream);
+  return launch_check("window_pose_step");
 }
 
 int olsr_pose_step(const olsr_pose_params* params, const float* dL_dtau_sum, const float* dL_dexposure,

@@ -224,7 +224,10 @@ constexpr int OLSR_ADAM_MAX_BUCKETS = 8;
 void launch_adam_step(int P, int M, int F, const olsr_adam_params& hp, const float* const* flats,
                       const unsigned long long* const* masks, int n_flats, float* means3D, float* shs, float* opacities, float* scales, float* rotations, float* language,
                       float* exp_avg, float* exp_avg_sq, hipStream_t st, const int32_t* group_step = nullptr,
-                      unsigned skip_mask = 0u);
+                      unsigned skip_mask = 0u, const olsr_adam_reg* reg = nullptr);
+size_t isotropic_reg_scratch_bytes(int P);
+void launch_isotropic_reg(int P, const float* scales, int activations, double weight, float* grad, double* loss,
+                          void* scratch, hipStream_t st);
 
 // k_map_edit.hip
 size_t map_edit_scratch_bytes(int P);
@@ -256,6 +259,9 @@ void launch_keyframe_decide(const olsr_keyframe_decide_params& p, const int64_t*
 // k_pose.hip
 void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,
                       float* state, int32_t* status, const int32_t* frame_status, hipStream_t st);
+void launch_window_pose_step(const olsr_pose_params& p, int V, const int32_t* flags, const float* dL_dtau_sum,
+                             const float* dL_dexposure, const float* proj, float* state, int32_t* status,
+                             const int32_t* frame_status, hipStream_t st);
 
 // k_knn.hip
 size_t knn_scratch_bytes(int P);

@@ -515,23 +515,33 @@ class FusedAdam:
         self.group_steps = [0] * len(_abi.ADAM_GROUPS)
         self.use_row_masks = True  # (False: read every gradient row, the A/B leg of tests and bench)
 
-    def step(self, bucket, params: Dict[str, torch.Tensor], lrs: Dict[str, float], rows=None, skip=()):
+    def step(self, bucket, params: Dict[str, torch.Tensor], lrs: Dict[str, float], rows=None, skip=(), isotropic=None,
+             activations=_abi.ACT_ALL, same_step=False):
         """params: means3D [P,3], shs [P,M,3], opacities [P(,1)], scales [P,3], rotations [P,4], language [P,F]
         (contiguous fp32 on the GPU, updated in place); lrs: xyz, sh_dc, sh_rest, opacity, scale, rotation, language.
         rows = (r0, r1): update only that contiguous range of Gaussians (the rows a rank owns after a
         reduce-scatter); the moments of the other rows are left alone.
         skip: names of _abi.ADAM_GROUPS that do not step in this call (parameters, moments and step count untouched) — the
-        reference's groups whose parameter was replaced in this iteration and so has no gradient; "all" skips the call."""
+        reference's groups whose parameter was replaced in this iteration and so has no gradient; "all" skips the call.
+        isotropic: weight of the mapping loss's isotropic regulariser (10 in the reference, utils/slam_backend.py:664-667;
+        None or 0: none) — its gradient is formed inside the step from the scales as they are before it and added last to
+        the scale gradient (olsr_adam_step_groups_reg), with the 1 / P of the whole bucket also when `rows` is given;
+        activations: the scene's _abi.ACT_* bits (ACT_SCALE_EXP: params["scales"] holds log(scale)).
+        same_step: this call takes ANOTHER row range of the optimiser step the previous call began (a map stepped in
+        several `rows` calls): the step counts are not advanced again; `skip` must be what that call was given."""
         skip = set(_abi.ADAM_GROUPS) if skip == "all" else set(skip)
         unknown = skip - set(_abi.ADAM_GROUPS)
         if unknown:
             raise ValueError(f"FusedAdam.step: unknown parameter groups {sorted(unknown)}")
         if len(skip) == len(_abi.ADAM_GROUPS):
             return
-        self.step_count += 1
-        for gi, name in enumerate(_abi.ADAM_GROUPS):
-            if name not in skip:
-                self.group_steps[gi] += 1
+        if not same_step:
+            self.step_count += 1
+            for gi, name in enumerate(_abi.ADAM_GROUPS):
+                if name not in skip:
+                    self.group_steps[gi] += 1
+        elif self.step_count < 1 or any(self.group_steps[gi] < 1 for gi, n in enumerate(_abi.ADAM_GROUPS) if n not in skip):
+            raise ValueError("FusedAdam.step(same_step=True): no step was begun for these groups")
         uniform = not skip and len(set(self.group_steps)) == 1
         hp = _abi.OlsrAdamParams(lr_xyz=lrs["xyz"], lr_sh_dc=lrs["sh_dc"], lr_sh_rest=lrs["sh_rest"], lr_opacity=lrs["opacity"],
                                  lr_scale=lrs["scale"], lr_rotation=lrs["rotation"], lr_language=lrs.get("language", 0.0),
@@ -558,7 +568,10 @@ class FusedAdam:
         # rows a bucket's row mask proves zero are not read (olsr_adam_step_masked: the update stays dense, the bits are
         # torch.optim.Adam's); a row range that does not start on a mask word (64 rows) takes the unmasked step
         masked = self.use_row_masks and r0 % 64 == 0 and any(b.row_mask is not None for b in buckets)
-        if not uniform:   # (per-group step counts or skipped groups: olsr_adam_step_groups, the same arithmetic per group)
+        reg = None
+        if isotropic is not None and float(isotropic) != 0.0:
+            reg = _abi.OlsrAdamReg(isotropic_weight=float(isotropic), activations=int(activations), P_total=P)
+        if not uniform or reg is not None:   # (per-group step counts or skipped groups: olsr_adam_step_groups, the same arithmetic per group)
             gp = _abi.OlsrAdamGroupParams(base=hp, skip_mask=sum(1 << gi for gi, n in enumerate(_abi.ADAM_GROUPS) if n in skip))
             for gi in range(len(_abi.ADAM_GROUPS)):
                 gp.group_step[gi] = self.group_steps[gi]
@@ -567,10 +580,11 @@ class FusedAdam:
             if masked:
                 masks = (C.c_void_p * len(buckets))(*[(b.row_mask.data_ptr() + 8 * (r0 // 64)) if b.row_mask is not None else None
                                                       for b in buckets])
-            check(lib().olsr_adam_step_groups(r1 - r0, M, F, C.byref(gp), len(buckets), flats, masks, p("means3D"), p("shs"),
-                                              p("opacities"), p("scales"), p("rotations"), p("language"),
-                                              self.exp_avg.data_ptr() + 4 * r0 * W,
-                                              self.exp_avg_sq.data_ptr() + 4 * r0 * W, stream))
+            check(lib().olsr_adam_step_groups_reg(r1 - r0, M, F, C.byref(gp), len(buckets), flats, masks, p("means3D"), p("shs"),
+                                                  p("opacities"), p("scales"), p("rotations"), p("language"),
+                                                  self.exp_avg.data_ptr() + 4 * r0 * W,
+                                                  self.exp_avg_sq.data_ptr() + 4 * r0 * W,
+                                                  C.byref(reg) if reg is not None else None, stream))
             return
         if len(buckets) > 1 or masked:
             flats = (C.c_void_p * len(buckets))(*[b.flat.data_ptr() + 4 * r0 * W for b in buckets])
@@ -724,13 +738,16 @@ class RasterWorkspace:
         return o
 
     def forward_loss(self, gt_image, gt_depth, gt_language=None, exposure=None, grad_mask=None, *, tracking=False,
-                     alpha=0.95, rgb_boundary_threshold=0.01, lamda_lang=1.0, initialization=False, skip_images=True):
+                     alpha=0.95, rgb_boundary_threshold=0.01, lamda_lang=1.0, initialization=False, skip_images=True,
+                     dL_dexposure_out=None):
         """The forward with the mapping (tracking=False) or tracking loss evaluated in the composite kernel's epilogue
         (olsr_forward_async_loss): no separate loss kernel, the rendered images make no round trip.  Targets as
         losses.mapping_loss / losses.tracking_loss take them, already float32 and contiguous on the workspace's device.
         skip_images: the images are not written at all (self.out keeps whatever it held).
         Returns dict(loss[4], dL_dimage, dL_ddepth, dL_dlanguage or None, dL_dexposure[2]) — workspace-owned buffers that
-        the next call overwrites; hand the three cotangents to backward()."""
+        the next call overwrites; hand the three cotangents to backward().
+        dL_dexposure_out: a contiguous float32[2] on the device that receives dL_dexposure instead of the workspace's buffer
+        (a view's slot of slam_iterations.KeyframeWindow)."""
         f32 = dict(dtype=torch.float32, device=self.device)
         if getattr(self, "_fl", None) is None:
             L = lib()
@@ -742,7 +759,7 @@ class RasterWorkspace:
         fl = self._fl
         lang = (not tracking) and self.F > 0 and gt_language is not None
         for name, t in (("gt_image", gt_image), ("gt_depth", gt_depth), ("gt_language", gt_language if lang else None),
-                        ("exposure", exposure), ("grad_mask", grad_mask)):
+                        ("exposure", exposure), ("grad_mask", grad_mask), ("dL_dexposure_out", dL_dexposure_out)):
             if t is not None and (not t.is_cuda or t.dtype != torch.float32 or not t.is_contiguous()
                                   or t.device != self.device):
                 raise RuntimeError(f"forward_loss: {name} must be a contiguous float32 tensor on {self.device}")
@@ -758,11 +775,14 @@ class RasterWorkspace:
                                 alpha=float(alpha), rgb_boundary_threshold=float(rgb_boundary_threshold),
                                 lamda_lang=float(lamda_lang))
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
+        if dL_dexposure_out is not None and dL_dexposure_out.numel() != 2:
+            raise RuntimeError("forward_loss: dL_dexposure_out must hold two floats")
+        dexp = dL_dexposure_out if dL_dexposure_out is not None else fl["dL_dexposure"]
         lf = _abi.OlsrLossFusion(params=p, tracking=int(bool(tracking)), skip_images=int(bool(skip_images)),
                                  gt_image=ptr(gt_image), gt_depth=ptr(gt_depth), gt_language=ptr(gt_language) if lang else None,
                                  exposure=ptr(exposure), grad_mask=ptr(grad_mask), dL_dimage=ptr(fl["dL_dimage"]),
                                  dL_ddepth=ptr(fl["dL_ddepth"]), dL_dlanguage=ptr(fl["dL_dlanguage"]) if lang else None,
-                                 loss=ptr(fl["loss"]), dL_dexposure=ptr(fl["dL_dexposure"]), scratch=ptr(fl["scratch"]))
+                                 loss=ptr(fl["loss"]), dL_dexposure=ptr(dexp), scratch=ptr(fl["scratch"]))
         o = self.out
         check(lib().olsr_forward_async_loss(
             C.byref(self._scene), self.geom.data_ptr(), self.binning.data_ptr(), self.capacity, self.img.data_ptr(),
@@ -770,16 +790,23 @@ class RasterWorkspace:
             o["opacity"].data_ptr(), o["radii"].data_ptr(), o["n_touched"].data_ptr(), self.num_rendered.data_ptr(),
             self.tile_order.data_ptr(), C.byref(lf), self._stream()))
         return dict(loss=fl["loss"], dL_dimage=fl["dL_dimage"], dL_ddepth=fl["dL_ddepth"],
-                    dL_dlanguage=fl["dL_dlanguage"] if lang else None, dL_dexposure=fl["dL_dexposure"])
+                    dL_dlanguage=fl["dL_dlanguage"] if lang else None, dL_dexposure=dexp)
 
     def backward(self, dL_dcolor, dL_dlanguage, dL_ddepth, bucket=None, first=False, bucket_only=False,
-                 pose_only=False):
+                 pose_only=False, tau_sum_out=None):
         """Backward of the last forward.  With `bucket` (a GradientBucket) the per-Gaussian backward kernel also
         writes (first=True) or adds this view's gradients into the bucket — the fused form of
         bucket.accumulate(); `bucket_only` additionally skips the separate per-Gaussian gradient arrays
         (a mapping step only consumes the bucket and dL_dtau_sum).  `pose_only`: tracking — only dL_dtau_sum
-        ([rho | theta] of the camera) is produced, no per-Gaussian array is written."""
+        ([rho | theta] of the camera) is produced, no per-Gaussian array is written.  `tau_sum_out`: a contiguous
+        float32[6] on the device that receives dL_dtau_sum instead of the workspace's buffer (a view's slot of
+        slam_iterations.KeyframeWindow)."""
         g = self.grads
+        if tau_sum_out is not None:
+            if (not tau_sum_out.is_cuda or tau_sum_out.device != self.device or tau_sum_out.dtype != torch.float32
+                    or tau_sum_out.numel() != 6 or not tau_sum_out.is_contiguous()):
+                raise RuntimeError(f"backward: tau_sum_out must be a contiguous float32[6] on {self.device}")
+            g = dict(g, dL_dtau_sum=tau_sum_out)
 
         def p(t):
             return t.data_ptr() if t is not None and t.numel() > 0 else None

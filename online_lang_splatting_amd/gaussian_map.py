@@ -513,13 +513,15 @@ class GaussianMap:
         self.stats.add_(bucket.densify)
         torch.maximum(self.max_radii, bucket.max_radii, out=self.max_radii)
 
-    def step(self, buckets, lrs: Optional[Dict[str, float]] = None, skip=()):
+    def step(self, buckets, lrs: Optional[Dict[str, float]] = None, skip=(), isotropic=None, activations=_abi.ACT_ALL):
         """FusedAdam over the map's parameters; the groups an edit since the last step replaced (pending_skip) and `skip`
-        do not step.  Returns the set of groups that skipped."""
+        do not step.  isotropic / activations: FusedAdam.step's (the mapping loss's isotropic regulariser, formed inside
+        the step).  Returns the set of groups that skipped."""
         sk = set(self.pending_skip) | (set(GROUPS) if skip == "all" else set(skip))
         self.pending_skip = set()
         if self.P > 0:
-            self.adam.step(buckets, self.params, lrs if lrs is not None else self.lrs, skip=sk)
+            self.adam.step(buckets, self.params, lrs if lrs is not None else self.lrs, skip=sk, isotropic=isotropic,
+                           activations=activations)
         return sk
 
     @property

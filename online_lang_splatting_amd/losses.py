@@ -57,11 +57,20 @@ def _exposure(exposure, dev):
     return _target("exposure", exposure.reshape(-1), (2,), dev)
 
 
+def _exposure_slot(who, t, dev):
+    if (not isinstance(t, torch.Tensor) or t.device != dev or t.dtype != torch.float32 or t.numel() != 2
+            or not t.is_contiguous()):
+        raise RuntimeError(f"{who}: dL_dexposure_out must be a contiguous float32[2] on {dev}")
+    return t
+
+
 def mapping_loss(image, depth, language, gt_image, gt_depth, gt_language=None, exposure=None, *, alpha=0.95,
-                 rgb_boundary_threshold=0.01, lamda_lang=1.0, initialization=False):
+                 rgb_boundary_threshold=0.01, lamda_lang=1.0, initialization=False, dL_dexposure_out=None):
     """image [3,H,W], depth [1,H,W], language [F,H,W] or None, gt_image [3,H,W], gt_depth [H,W],
     gt_language [F,h,w] or None, exposure = device tensor [2] {exposure_a, exposure_b} or None.
-    Returns dict(loss[4] = {total, rgb, depth, language terms}, dL_dimage, dL_ddepth, dL_dlanguage, dL_dexposure[2])."""
+    Returns dict(loss[4] = {total, rgb, depth, language terms}, dL_dimage, dL_ddepth, dL_dlanguage, dL_dexposure[2]).
+    dL_dexposure_out: a contiguous float32[2] on the image's device that receives dL_dexposure instead of a fresh tensor (a
+    view's slot of slam_iterations.KeyframeWindow)."""
     image = _image3("mapping_loss: image", image)
     dev = image.device
     H, W = image.shape[1], image.shape[2]
@@ -83,7 +92,9 @@ def mapping_loss(image, depth, language, gt_image, gt_depth, gt_language=None, e
                             initialization=int(bool(initialization)), alpha=float(alpha),
                             rgb_boundary_threshold=float(rgb_boundary_threshold), lamda_lang=float(lamda_lang))
     out = dict(loss=torch.empty(4, **f32), dL_dimage=torch.empty(3, H, W, **f32), dL_ddepth=torch.empty(1, H, W, **f32),
-               dL_dlanguage=torch.empty(F, H, W, **f32), dL_dexposure=torch.empty(2, **f32))
+               dL_dlanguage=torch.empty(F, H, W, **f32),
+               dL_dexposure=(torch.empty(2, **f32) if dL_dexposure_out is None
+                             else _exposure_slot("mapping_loss", dL_dexposure_out, dev)))
     L = lib()
     scratch = torch.empty(L.olsr_mapping_loss_scratch_bytes(W, H), dtype=torch.uint8, device=dev)
     ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
@@ -161,6 +172,27 @@ def refinement_loss(image, gt_image, *, lambda_dssim=0.2, want_grad=True, buffer
                                      out["dL_dimage"].data_ptr() if want_grad else None, out["loss"].data_ptr(),
                                      scratch.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return out
+
+
+def isotropic_loss(scales, activations=0, weight=10.0, want_grad=False):
+    """The mapping loss's isotropic regulariser (utils/slam_backend.py:664-667) on its own (olsr_isotropic_reg):
+    weight * |s - s.mean(dim=1)|.mean() of scales [P,3], contiguous float32 on the GPU; activations & ACT_SCALE_EXP: `scales`
+    holds log(scale) and the gradient is with respect to it.  Returns the loss, a 0-d float64 tensor on the device (the same
+    bits on every run), or with want_grad (loss, gradient [P,3]).  Inside a mapping iteration the Adam step forms the same
+    gradient itself (FusedAdam.step(isotropic=...)): this entry is for the value and for tests."""
+    if (not isinstance(scales, torch.Tensor) or not scales.is_cuda or scales.dtype != torch.float32 or scales.dim() != 2
+            or scales.shape[1] != 3 or not scales.is_contiguous()):
+        raise RuntimeError("isotropic_loss: scales must be a contiguous float32 [P,3] tensor on the GPU")
+    dev, P = scales.device, int(scales.shape[0])
+    L = lib()
+    loss = torch.empty((), dtype=torch.float64, device=dev)
+    grad = torch.empty_like(scales) if want_grad else None
+    scratch = torch.empty(L.olsr_isotropic_reg_scratch_bytes(P), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        check(L.olsr_isotropic_reg(P, scales.data_ptr() if P else None, int(activations), float(weight),
+                                   grad.data_ptr() if want_grad and P else None, loss.data_ptr(), scratch.data_ptr(),
+                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return (loss, grad) if want_grad else loss
 
 
 class _Ssim(torch.autograd.Function):

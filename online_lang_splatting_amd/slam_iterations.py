@@ -9,6 +9,9 @@ TrackingLoop   front end, utils/slam_frontend.py:tracking() (:160-275): up to 10
                Iterations depend on each other through the pose: this is the single-frame LATENCY of the path.
 MappingStep    back end, utils/slam_backend.py:map() (:499-760): 12 views of the same Gaussians (10 window keyframes +
                2 random), mapping loss incl. the language L1 (:579-597), gradients summed over the views, ONE Adam step.
+KeyframeWindow back end, the bundle adjustment of map(): `keyframe_optimizers` (:933-980) — poses of the first pose_window
+               window keyframes at half the tracking rates, exposures of every window keyframe, nothing for frame 0 — stepped
+               once per mapping iteration with update_pose (:756-765), in ONE launch (olsr_window_pose_step).
 
 OnlineLanguageTargets  back end, the language targets of map(): train_online_autoencoder (:266-323) once per new keyframe
                (:562-576, the returned codes are the keyframe's gt_lang_feat) and once per rehearsal view (:640-648).
@@ -96,6 +99,114 @@ class PoseState:
     def camera(self) -> Dict:
         return dict(viewmatrix=self.viewmatrix, projmatrix=self.projmatrix, projmatrix_raw=self.proj,
                     campos=self.campos, tanfovx=self.tanfovx, tanfovy=self.tanfovy)
+
+
+class KeyframeWindow:
+    """The mapping window's keyframes — pose, exposure and their optimiser — resident on the GPU as [V,80] pose states
+    (olsr_pose_step's layout) and advanced by ONE kernel per mapping iteration (olsr_window_pose_step, one wave per view).
+    It is the reference's `keyframe_optimizers` (utils/slam_backend.py:933-980) plus the update_pose calls after its step
+    (:756-765): view v of the window optimises pose and exposure when v < pose_window, its exposure alone beyond, and
+    nothing when its id is frozen (frame 0, which anchors the map).  MappingStep(window=...) writes every view's
+    dL_dtau_sum and dL_dexposure straight into `grad_tau[v]` / `grad_exposure[v]` and calls step() once per iteration.
+
+    A view's flags are fixed between two rebuilds: its pose and exposure groups share one step count, so a group that
+    joined later would run on the others' bias corrections.  The reference builds a fresh optimiser at every new keyframe
+    instead, and so does rebuild()."""
+
+    def __init__(self, T_w2c, ids: Sequence[int], projection_matrix: torch.Tensor, tanfovx: float, tanfovy: float,
+                 exposures=None, pose_window=5, frozen_ids=(0,), lr_rot=0.0015, lr_trans=0.0005, lr_exposure=0.01,
+                 betas=(0.9, 0.999), eps=1e-8, converged_threshold=1e-4, device_step_count=False):
+        """T_w2c: [V,4,4] (or a sequence of [4,4]) on the GPU, the window's poses in window order; ids: a stable id per view
+        (the keyframe's frame index); exposures: [V,2] {a, b} per view or None (zeros); device_step_count: as in PoseState
+        (every view counts its own steps in status[v][1]; needed for a gated step)."""
+        if not isinstance(projection_matrix, torch.Tensor) or not projection_matrix.is_cuda:
+            raise RuntimeError("KeyframeWindow: the projection matrix and the poses live on the GPU (there is no CPU path)")
+        self.proj = projection_matrix.detach().to(dtype=torch.float32).contiguous()
+        self.device = self.proj.device
+        self.tanfovx, self.tanfovy = float(tanfovx), float(tanfovy)
+        self.pose_window, self.frozen_ids = int(pose_window), tuple(frozen_ids)
+        self.device_step_count = bool(device_step_count)
+        self.hp = _abi.OlsrPoseParams(lr_rot=lr_rot, lr_trans=lr_trans, lr_exposure=lr_exposure, beta1=betas[0],
+                                      beta2=betas[1], eps=eps, converged_threshold=converged_threshold, step=0)
+        self.ids = []
+        self.rebuild(ids, T_w2c, exposures)
+
+    def __len__(self):
+        return len(self.ids)
+
+    def rebuild(self, ids: Sequence[int], T_w2c=None, exposures=None):
+        """The window changed (a new keyframe): the reference's re-creation of keyframe_optimizers.  ids: the new window in
+        order; T_w2c / exposures: sequences aligned with ids — an entry (or the whole argument) may be None for an id that
+        was in the window before, which keeps the pose / exposure it has; a new id needs its pose (exposure: zeros).  Every
+        optimiser word and count starts from zero.  Views handed out by camera() / exposure() before this call are stale."""
+        ids = [int(i) for i in ids]
+        V = len(ids)
+        if not 1 <= V <= _abi.WINDOW_MAX_VIEWS or len(set(ids)) != V:
+            raise ValueError(f"KeyframeWindow: between 1 and {_abi.WINDOW_MAX_VIEWS} distinct view ids")
+        f32 = dict(dtype=torch.float32, device=self.device)
+        old = {i: v for v, i in enumerate(self.ids)}
+        state = torch.zeros(V, 80, **f32)
+        for v, i in enumerate(ids):
+            T = T_w2c[v] if T_w2c is not None else None
+            e = exposures[v] if exposures is not None else None
+            if T is None:
+                if i not in old:
+                    raise ValueError(f"KeyframeWindow: view {i} is new to the window and needs a pose")
+                state[v, 0:16] = self.state[old[i], 0:16]
+            else:
+                state[v, 0:16] = torch.as_tensor(T).detach().to(**f32).reshape(16)
+            if e is not None:
+                state[v, 70:72] = torch.as_tensor(e, dtype=torch.float32).detach().to(**f32).reshape(2)
+            elif i in old:
+                state[v, 70:72] = self.state[old[i], 70:72]
+        self.ids = ids
+        self.state = state
+        self.status = torch.zeros(V, 2, dtype=torch.int32, device=self.device)
+        self.grad_tau = torch.zeros(V, 6, **f32)        # [rho | theta] per view, as olsr_backward leaves it
+        self.grad_exposure = torch.zeros(V, 2, **f32)
+        self.flags = [0 if i in self.frozen_ids else
+                      (_abi.WINDOW_OPT_POSE | _abi.WINDOW_OPT_EXPOSURE if v < self.pose_window else _abi.WINDOW_OPT_EXPOSURE)
+                      for v, i in enumerate(ids)]
+        self._flags_c = (C.c_int32 * V)(*self.flags)
+        self._zero_flags = (C.c_int32 * V)()
+        self.hp.step = 0
+        # (the views are made once: a mapping iteration asks for every view's camera)
+        self._cameras = [dict(viewmatrix=st[16:32].view(4, 4), projmatrix=st[32:48].view(4, 4), projmatrix_raw=self.proj,
+                              campos=st[48:51], tanfovx=self.tanfovx, tanfovy=self.tanfovy) for st in state]
+        self._exposures = [st[70:72] for st in state]
+        self._call(self._zero_flags, None)   # the matrices of the poses as they are (no flags: no step)
+
+    def _call(self, flags, frame_status):
+        check(lib().olsr_window_pose_step(C.byref(self.hp), len(self.ids), flags, self.grad_tau.data_ptr(),
+                                          self.grad_exposure.data_ptr(), self.proj.data_ptr(), self.state.data_ptr(),
+                                          self.status.data_ptr(),
+                                          frame_status.data_ptr() if frame_status is not None else None,
+                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+
+    def step(self, frame_status: Optional[torch.Tensor] = None):
+        """keyframe_optimizers.step() and update_pose of every view, from the gradients in grad_tau / grad_exposure.
+        frame_status: device int32[V,2], per view the {R, status} of the forward its gradient came from — a view whose frame
+        was not usable takes no step (needs device_step_count, as PoseState.step)."""
+        if frame_status is not None:
+            if not self.device_step_count:
+                raise ValueError("a gated window step needs KeyframeWindow(device_step_count=True)")
+            if (not frame_status.is_cuda or frame_status.dtype != torch.int32 or tuple(frame_status.shape) != (len(self.ids), 2)
+                    or not frame_status.is_contiguous()):
+                raise RuntimeError("KeyframeWindow.step: frame_status must be a contiguous int32 [V,2] tensor on the GPU")
+        if not self.device_step_count:
+            self.hp.step += 1
+        self._call(self._flags_c, frame_status)
+
+    def camera(self, v: int) -> Dict:
+        """View v's camera as views of its state (the dict shape of PoseState.camera()): always the current pose."""
+        return self._cameras[v]
+
+    def exposure(self, v: int) -> torch.Tensor:
+        """View v's {exposure_a, exposure_b}, a view of its state."""
+        return self._exposures[v]
+
+    def T_w2c(self, v: int) -> torch.Tensor:
+        return self.state[v, 0:16].view(4, 4)
 
 
 class TrackingLoop:
@@ -234,7 +345,8 @@ class MappingStep:
     def __init__(self, lanes: FrameLanes, params: Dict[str, torch.Tensor], bg: torch.Tensor, sh_degree: int,
                  cameras: Sequence[Dict], targets: Sequence, lrs: Dict[str, float], exposure=None,
                  activations=_abi.ACT_ALL, fused_loss="auto", view_ids: Optional[Sequence] = None, carry_order: Optional[bool] = None,
-                 gaussian_map=None, edit_hook: Optional[Callable] = None, record_visibility: bool = False):
+                 gaussian_map=None, edit_hook: Optional[Callable] = None, record_visibility: bool = False,
+                 window: Optional[KeyframeWindow] = None, isotropic_weight: Optional[float] = None):
         """targets[v] = (gt_image [3,H,W], gt_depth [H,W], gt_language [F,h,w] or None).
         fused_loss: True — the mapping loss is evaluated in the forward composite's epilogue (olsr_forward_async_loss); False —
         olsr_forward_async + olsr_mapping_loss (two kernels; the same cotangents bit for bit, the loss value to summation order);
@@ -262,7 +374,19 @@ class MappingStep:
         opacity group after a reset).  The hook may return "all" or a collection of group names to skip besides.  The next
         iteration follows the map's new P (FrameLanes.resize; carried depth orders start again, tile-order hints stay).
         record_visibility: keep each view's radii > 0 and n_touched > 0 of the last iteration (self.visibility[view id],
-        self.touched[view id]): the visibility filters of reset_opacity_nonvisible and the co-visibility count."""
+        self.touched[view id]): the visibility filters of reset_opacity_nonvisible and the co-visibility count.
+        window (a KeyframeWindow): the bundle adjustment of the reference's map().  The window's views come FIRST in
+        `targets` / `view_ids` (len(window) of them, in window order) and are rendered from the window's own cameras and
+        exposures; `cameras` holds only the remaining (rehearsal) views, which use the shared `exposure` and get no update,
+        as in the reference.  Each window view's dL_dtau_sum and dL_dexposure are written by the kernels straight into its
+        slot of the window, and after the lanes have joined ONE window step runs on the caller's stream, beside the Adam
+        step (keyframe_optimizers.step() + update_pose, utils/slam_backend.py:756-765).
+        isotropic_weight: the reference's `loss_mapping += 10 * |scaling - scaling.mean(dim=1)|.mean()` (:664-667) with that
+        weight (the reference's: 10); its gradient is formed inside the Adam step (FusedAdam.step(isotropic=...)), its value
+        is not part of `last_loss` (losses.isotropic_loss gives it).  None: no regulariser.
+        With both left at None every path is what it was without them."""
+        self.window = window
+        self.isotropic_weight = None if isotropic_weight is None else float(isotropic_weight)
         self.map, self.edit_hook, self.record_visibility = gaussian_map, edit_hook, bool(record_visibility)
         self.visibility: Dict = {}
         self.touched: Dict = {}
@@ -368,7 +492,12 @@ class MappingStep:
         for _, _, st in lanes.lanes:  # the parameters (and, the first time, the targets) were written on the caller's stream
             if st != main:
                 st.wait_stream(main)
-        for v, cam in enumerate(self.cameras):
+        win = self.window
+        nw = len(win) if win is not None else 0
+        for v in range(nw + len(self.cameras)):
+            cam = win.camera(v) if v < nw else self.cameras[v - nw]
+            exposure = win.exposure(v) if v < nw else self.exposure
+            dexp_out = win.grad_exposure[v] if v < nw else None
             ws, bucket, stream = lanes.next_lane()
             first = bucket not in used
             if first:
@@ -386,12 +515,12 @@ class MappingStep:
                 ws.depth_order_carry = self.view_orders[vid] if self.carry_order else None
                 if self.fused:
                     ws.set_scene(bg=self.bg, sh_degree=self.sh_degree, activations=self.act, **cam, **self.params)
-                    lo = ws.forward_loss(*self.targets[v], self.exposure, skip_images=True)
+                    lo = ws.forward_loss(*self.targets[v], exposure, skip_images=True, dL_dexposure_out=dexp_out)
                 else:
                     out = self.render(ws, cam)
                     mark("loss:begin", stream)
                     lo = losses.mapping_loss(out["color"], out["depth"], out["language"] if ws.F > 0 else None,
-                                             *self.targets[v], self.exposure)
+                                             *self.targets[v], exposure, dL_dexposure_out=dexp_out)
                     mark("loss:end", stream)
                     if ws.F > 0 and self.targets[v][2] is None:
                         lo["dL_dlanguage"] = None
@@ -399,7 +528,7 @@ class MappingStep:
                     self.visibility[vid] = ws.out["radii"] > 0
                     self.touched[vid] = ws.out["n_touched"] > 0
                 ws.backward(lo["dL_dimage"], lo["dL_dlanguage"], lo["dL_ddepth"], bucket=bucket, first=first,
-                            bucket_only=True)
+                            bucket_only=True, tau_sum_out=win.grad_tau[v] if v < nw else None)
                 self.last_loss = lo["loss"]
         for _, _, st in lanes.lanes:
             main.wait_stream(st)
@@ -423,14 +552,18 @@ class MappingStep:
                 used[0].add_bucket(b)
             used = used[:8]
         if self.map is None:
-            self.adam.step(total if multi else used, self.params, self.lrs)
+            self.adam.step(total if multi else used, self.params, self.lrs, isotropic=self.isotropic_weight,
+                           activations=self.act)
         else:
             if stats:
                 self.map.add_densification_stats(total)
             skip = self.edit_hook(self, total) if self.edit_hook is not None else None
-            self.map.step(total if multi else used, self.lrs, skip=skip or ())
+            self.map.step(total if multi else used, self.lrs, skip=skip or (), isotropic=self.isotropic_weight,
+                          activations=self.act)
             self.params = self.map.params
         mark("adam:end", main)
+        if win is not None:   # (the lanes have joined: every view's gradient slots are written)
+            win.step()
         if cal_ev is not None:
             end = torch.cuda.Event(enable_timing=True)
             end.record(main)
