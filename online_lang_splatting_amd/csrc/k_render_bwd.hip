@@ -10,8 +10,8 @@
 // per lane, wave w = the forward's slot w — one quadrant of the tile, slot_rank in olsr_device.h):
 //   * no barrier per splat: the forward composite recorded, per (tile, splat) instance, which
 //     slots blended it (flags[] bit w).  A wave skips instances its slot never touched with a
-//     uniform branch, and the four waves of a tile only meet when the next batch of 128 list
-//     entries is staged into LDS;
+//     uniform branch, and the four waves of a tile only meet when the next batch of 64 or 128
+//     list entries is staged into LDS;
 //   * the per-splat reduction never leaves the wave and never touches LDS: gfx950's
 //     v_permlane32_swap / v_permlane16_swap fold the lane dimension for two values per swap,
 //     DPP row rotations finish inside rows of 16 (10 instructions per 4 values).  The totals are
@@ -64,7 +64,6 @@ __device__ __forceinline__ constexpr bool own_lanes_clear(int first, int end, in
   return true;
 }
 
-constexpr int BWD_BATCH = 128;
 #ifndef OLSR_BWD_LDS_REDUCE
 #define OLSR_BWD_LDS_REDUCE 1  // fold the lanes of the per-splat sums through LDS (olsr_device.h) instead of permlane swaps
 #endif
@@ -105,11 +104,22 @@ struct bwd_pair {
 // PACKED (reference mode, 15x15 tiles): the workgroup is the 128 survivors of the reference's reduction
 // tree in two full waves (ref15_rank_of_packed); the 97 other pixels of the tile are not evaluated at all —
 // nothing they compute reaches an output of the reference's backward.
-#ifndef OLSR_BWD_MIN_WAVES
-#define OLSR_BWD_MIN_WAVES 5  // waves per SIMD the packed reference-mode instantiations with F <= 16 are compiled for
-#endif
-template <int TILE, int F, int MODE, bool PACKED>
-__global__ __launch_bounds__(PACKED ? 128 : 256, (PACKED && F <= 16) ? OLSR_BWD_MIN_WAVES : 1) void render_bwd_kernel(
+//
+// B: the staging batch, list entries per fill of the LDS tables; WAVES: the waves per SIMD the instantiation is compiled for.
+// Both are chosen per instantiation (bwd_shape).  The LDS of a workgroup is almost all staging (80 B of features per entry at
+// F = 15), so B decides how many workgroups a CU holds; the per-pixel state lives in registers across batches, a smaller batch
+// only meets the other waves of its tile more often.
+template <int F, int MODE>
+struct bwd_shape {
+  // reference mode, at most 16 language channels: 64 entries (9 - 11 KB of LDS instead of 16 - 18) and seven waves per SIMD,
+  // so that nearly the whole grid of config 3 is resident at once (3.6 -> 5.5 resident waves per SIMD, 172 -> 163 us; DESIGN
+  // 12.8).  F = 32 is register-bound at four waves whatever the batch, and the exact mode has not been measured at 64: 128.
+  static constexpr bool SMALL = (MODE == OLSR_BWD_REFERENCE) && (F <= 16);
+  static constexpr int B = SMALL ? 64 : 128;
+  static constexpr int WAVES = SMALL ? 7 : 1;
+};
+template <int TILE, int F, int MODE, bool PACKED, int B, int WAVES>
+__global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
     const u32* __restrict__ ranges, const u32* __restrict__ inst_gid, const u32* __restrict__ src,
     const uint8_t* __restrict__ flags, const u32* __restrict__ rowbase, const int32_t* __restrict__ counters,
     const u32* __restrict__ tile_order, int W, int H, int gx, int ntiles, const float* __restrict__ bg,
@@ -133,9 +143,15 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, (PACKED && F <= 16) ? OLSR_BWD_
   constexpr int FX = (F > 0) ? F : 1;
   constexpr int F2 = (F + 1) / 2;        // packed pairs of language channels
   constexpr int F2X = (F2 > 0) ? F2 : 1;
-  constexpr int B = BWD_BATCH;
   constexpr int NT = PACKED ? 128 : 256;  // threads
   constexpr int NWV = NT / 64;            // waves
+  constexpr int NH = B / 64;              // 64-bit masks per batch
+  // staging: TPS threads per slot.  One alone stages the whole entry; of several, the first takes the entry's scalars and
+  // the others share its feature row in runs of FPER floats (whole float4s), so that no two threads write one word
+  constexpr int TPS = NT / B;
+  constexpr int FPT = (TPS > 1) ? TPS - 1 : 1;
+  constexpr int FPER = ((FR + FPT - 1) / FPT + 3) / 4 * 4;
+  static_assert(B % 64 == 0 && NT % B == 0, "whole masks per batch, whole threads per slot");
   static_assert(ROW <= 64, "one lane per row element");
   static_assert(!PACKED || (REF && TILE == 15), "survivor packing is the reference mode of 15x15 tiles");
 
@@ -301,36 +317,41 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, (PACKED && F <= 16) ? OLSR_BWD_
         const u32 sp = r0 + (u32)(kstart - e);
         const u32 u = src[sp];        // emission index of the instance
         const u32 gid = inst_gid[u];  // its Gaussian
-        if (PACKED || tid < B) {
+        const int part = tid / B;  // (wave-uniform: B is a multiple of 64)
+        if (TPS == 1 || part == 0) {
           s_row[e] = rowbase[u];
           s_flag[e] = flags[u];
           s_xy[e] = reinterpret_cast<const float2*>(means2D)[gid];
           s_co[e] = reinterpret_cast<const float4*>(conic_opacity)[gid];
         }
-        if (PACKED || tid >= B) {
+        if (TPS == 1 || part > 0) {
           float* fr = &s_feat[e * FR];
-          fr[0] = colors[3 * (size_t)gid + 0];
-          fr[1] = colors[3 * (size_t)gid + 1];
-          fr[2] = colors[3 * (size_t)gid + 2];
-          fr[3] = depths[gid];
+          const int run = (TPS == 1) ? 0 : part - 1;  // this thread's run of the row
 #pragma unroll
-          for (int ch = 0; ch < F; ++ch) fr[4 + ch] = lang[(size_t)gid * F + ch];
-#pragma unroll
-          for (int ch = 4 + F; ch < FR; ++ch) fr[ch] = 0.f;  // the packed dot product reads the padding
+          for (int ch = 0; ch < FR; ++ch) {
+            if (ch / FPER != run) continue;
+            if (ch < 3)
+              fr[ch] = colors[3 * (size_t)gid + ch];
+            else if (ch == 3)
+              fr[ch] = depths[gid];
+            else if (ch < 4 + F)
+              fr[ch] = lang[(size_t)gid * F + (ch - 4)];
+            else
+              fr[ch] = 0.f;  // the packed dot product reads the padding
+          }
         }
       }
     }
     __syncthreads();
 
     // From here to the next batch the four waves run independently: no barrier per splat.
-    // The flags of the staged entries become wave-uniform 64-bit masks (one ballot per half batch): which entries the
+    // The flags of the staged entries become wave-uniform 64-bit masks (one ballot per 64 entries): which entries the
     // tile as a whole does not skip (bits 0-3: the forward's slots) and which ones THIS wave blended (bits 4-5: the
     // packed survivor waves).  The loop then walks set bits with scalar instructions; an entry nobody blended — most
     // of every list — costs nothing (it used to cost a dependent LDS read and a v_readfirstlane each).
-    static_assert(B == 128, "two 64-bit masks per batch");
-    u64 m_any[2], m_mine[2], m_w0[2];
+    u64 m_any[NH], m_mine[NH], m_w0[NH];
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < NH; ++h) {
       const int e = lane + 64 * h;
       const u32 f = (e < cnt) ? s_flag[e] : 0u;
       m_any[h] = ballot((f & 15u) != 0u);
@@ -338,7 +359,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, (PACKED && F <= 16) ? OLSR_BWD_
       m_w0[h] = ballot(((f >> 4) & 1u) != 0u);
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
+    for (int h = 0; h < NH; ++h) {
     // reference mode with language channels: the recursion also advances on entries another wave blended
     u64 todo = (REF && F > 0) ? m_any[h] : m_mine[h];
     while (todo != 0ull) {
@@ -544,7 +565,8 @@ static void launch_bwd_t(const olsr_scene& s, const FrameDims& d, const Geometry
                          hipStream_t st) {
   const float* colors = s.colors_precomp ? s.colors_precomp : g.rgb;
   constexpr bool PACKED = (MODE == OLSR_BWD_REFERENCE && TILE == 15);
-  render_bwd_kernel<TILE, F, MODE, PACKED><<<d.ntiles, PACKED ? 128 : 256, 0, st>>>(
+  typedef bwd_shape<F, MODE> shape;
+  render_bwd_kernel<TILE, F, MODE, PACKED, shape::B, shape::WAVES><<<d.ntiles, PACKED ? 128 : 256, 0, st>>>(
       im.ranges, b.inst_gid, b.src, b.flags, b.rowbase, g.counters, im.tile_order, d.W, d.H, d.gx, d.ntiles,
       s.background,
       g.means2D, g.conic_opacity, colors, s.language_precomp, g.depths, im.final_T, im.n_contrib, dc, dl, dd, rows,
