@@ -1122,6 +1122,57 @@ int olsr_chamfer(int32_t B, const int32_t *off1, const int32_t *off2, int32_t ma
                  const float *xyz1, const float *xyz2, float *min_d2_1, int32_t *nn_1, float *min_d2_2, int32_t *nn_2,
                  double *mean /*[B,2]: x->y, y->x*/, int32_t *valid, void *scratch, void *hip_stream);
 
+/* ---- scoring text queries: mask smoothing, IoU, localisation, masked PSNR (the reference's 2-D evaluation) ----------------
+ * What eval/evaluate_onlinelangslam.py does with the maps olsr_lang_query_relevancy returns, up to the counts its two reported
+ * figures (mean IoU, localisation accuracy) are formed from, and the masked PSNR of utils/eval_utils.py:171-173.  Everything but
+ * the PSNR is integer arithmetic without atomics: the results are exact and the same on every run.  One head only: the online
+ * pipeline has one level, so the reference's choice among heads (:165-172, :208) has nothing to choose from.
+ *
+ * olsr_mask_smooth: `smooth` of eval/utils.py:47-56, a 7 x 7 majority vote, in one launch.
+ *   mask_in       device uint8[P,H,W], read as it lies: no alignment of planes or rows is assumed.  A byte != 0 counts as 1
+ *   mask_out      device uint8[P,H,W] of 0 / 1, out of place (mask_out == mask_in is OLSR_ERR_ARG; overlapping is undefined)
+ * For pixel (i, j) the window is rows max(0, i-3) .. min(i+4, H-1) - 1 and columns max(0, j-3) .. min(j+4, W-1) - 1: the
+ * reference's slice, its quirk kept — the upper bound is clamped to H-1 / W-1, so the last row and the last column never
+ * enter any window.  out = 1 iff 2 * ones > area of that window; a tie gives 0, as np.argmax(np.bincount(.)) takes the first
+ * maximum.  Deviations: H < 2 or W < 2 is OLSR_ERR_ARG where the reference raises on the empty window; a mask that is not
+ * binary is binarised first, where the reference would vote over the byte values.  1 <= P <= 65535, H, W <= 2^20,
+ * H W < 2^31.
+ *
+ * olsr_query_eval: the same pass with the counts of :160-161 and :203-223 in its epilogue, then one launch that adds the
+ * workgroups' partial counts per phrase.  Nothing is read back; the caller reads 16 P bytes.
+ *   mask          device uint8[P,H,W]: the mask BEFORE smoothing, as olsr_lang_query_relevancy wrote it
+ *   smoothed      device float[P,H,W] and score float[P] (its maximum), as olsr_lang_query_relevancy wrote them
+ *   gt_mask       device uint8[P,H,W]: the annotated masks, already at the map's size (the reference's cv2.resize of the
+ *                 annotation, :157, stays with the caller); != 0 counts as set
+ *   boxes         device float[B,4] = (x1, y1, x2, y2) in pixels of the map, or NULL if there is none
+ *   box_offsets   int32[P+1], non-decreasing from >= 0: phrase p owns boxes box_offsets[p] .. box_offsets[p+1] - 1, possibly
+ *                 none.  Host or device memory, checked on the host before anything is launched (a device table costs one
+ *                 small read and a synchronisation of the stream, a host table one small upload into the scratch)
+ *   result        device int32[P,4] = {intersection, union, n_max, hit}: the counts of gt & s and gt | s with s the smoothed
+ *                 mask (IoU = intersection / union; 0 / 0 is the reference's NaN and left to the caller); the number of
+ *                 pixels with smoothed == score[p]; 1 iff any of THOSE pixels (x = column, y = row) lies in any of the
+ *                 phrase's boxes, min(x1,x2) <= x <= max(x1,x2) and likewise y, bounds included.  Every pixel that attains
+ *                 the maximum is tested, as the reference does — olsr_lang_query_relevancy's coord is only the first of
+ *                 them.  No box: hit = 0.  A NaN score: n_max = 0, hit = 0
+ *   mask_smoothed device uint8[P,H,W] or NULL: the smoothed masks, if wanted (never mask itself)
+ *   scratch       device, olsr_query_eval_scratch_bytes(P, H, W) bytes: 16 bytes per phrase and 64 x 64 tile
+ *
+ * olsr_image_psnr: image, gt device float[C,H,W] (C H W < 2^31) -> out double[2] = {sum of (clamp(image, 0, 1) - gt)^2 over the
+ * ELEMENTS with gt > 0, their number} — image[mask] with mask = gt_image > 0 is per element in the reference, not per pixel.
+ * The difference is float32 as the reference's, its square and the sums are double in an order that depends on C H W alone.
+ * The caller forms mse = sum / count and 20 log10(1 / sqrt(mse)); a count of 0 gives the reference's NaN.  Two launches.
+ *   scratch       device, olsr_image_psnr_scratch_bytes() bytes */
+#define OLSR_QUERY_EVAL_MAX_PLANES 65535
+#define OLSR_QUERY_EVAL_MAX_EXTENT 1048576
+int olsr_mask_smooth(int32_t P, int32_t H, int32_t W, const uint8_t *mask_in, uint8_t *mask_out, void *hip_stream);
+size_t olsr_query_eval_scratch_bytes(int32_t P, int32_t H, int32_t W);
+int olsr_query_eval(int32_t P, int32_t H, int32_t W, const uint8_t *mask, const float *smoothed, const float *score,
+                    const uint8_t *gt_mask, const float *boxes, const int32_t *box_offsets,
+                    int32_t *result /*[P,4]*/, uint8_t *mask_smoothed /*may be NULL*/, void *scratch, void *hip_stream);
+size_t olsr_image_psnr_scratch_bytes(void);
+int olsr_image_psnr(int32_t C, int32_t H, int32_t W, const float *image, const float *gt, double *out /*[2]*/,
+                    void *scratch, void *hip_stream);
+
 /* ---- one tracking iteration's pose update (the front end) ----------------------
  * Replaces, per iteration of the reference's tracking loop (utils/slam_frontend.py:216-243),
  *   pose_optimizer.step()           torch.optim.Adam over cam_rot_delta (lr config Training.lr.cam_rot_delta = 0.003),

@@ -18,13 +18,15 @@ from .hr_net import HighResLanguageNet  # noqa: F401,E402  (the high-resolution 
 from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and language maps into a 3-D map)
 from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_distance,  # noqa: F401,E402  (the 3-D evaluation's
                             emd_segments, evaluate_classes)                            # Chamfer and earth mover's distances)
+from . import query_eval  # noqa: F401,E402  (the 2-D evaluation: mask smoothing, IoU, localisation, masked PSNR)
+from .query_eval import QueryEvaluator, frame_metrics, smooth_masks  # noqa: F401,E402
 from .keyframe_seed import seed_rows  # noqa: F401,E402  (a keyframe's new Gaussians from its RGB-D image, on the device)
 from .frontend import KeyframeSelector, median_depth, tracking_mask  # noqa: F401,E402  (the front end's frame step)
 from .slam_iterations import KeyframeWindow  # noqa: F401,E402  (mapping's bundle adjustment: window poses and exposures)
 from .losses import isotropic_loss  # noqa: F401,E402  (the mapping loss's isotropic regulariser)
 
 __all__ = ["render", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
-           "chamfer_distance", "chamfer_segments", "evaluate_classes", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
+           "chamfer_distance", "chamfer_segments", "evaluate_classes", "query_eval", "QueryEvaluator", "smooth_masks", "frame_metrics", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]
 

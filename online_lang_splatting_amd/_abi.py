@@ -266,6 +266,10 @@ class OlsrHrNetParams(C.Structure):
 # point-cloud metrics (OLSR_CLOUD_*)
 CLOUD_MAX_SEGMENTS = 32767
 
+# scoring text queries (OLSR_QUERY_EVAL_*); the columns of olsr_query_eval's result
+QUERY_EVAL_MAX_PLANES, QUERY_EVAL_MAX_EXTENT = 65535, 1 << 20
+QUERY_EVAL_RESULT = ("intersection", "union", "n_max", "hit")
+
 # TSDF fusion (OLSR_TSDF_*)
 TSDF_MAX_VIEWS = 16
 TSDF_FEAT_FLOAT, TSDF_FEAT_PACKED_RGB = 0, 1

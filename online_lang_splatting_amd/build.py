@@ -50,6 +50,7 @@ UNITS = [
     ("k_pose.hip", "k_pose.o", []),
     ("k_tsdf.hip", "k_tsdf.o", []),
     ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),
+    ("k_query_eval.hip", "k_query_eval.o", []),
 ]
 HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", os.path.join("..", "..", "include", "olsr.h")]
 

@@ -1,5 +1,5 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, TSDF fusion, point-cloud metrics.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, TSDF fusion, point-cloud metrics, the 2-D evaluation's query scoring.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -108,6 +108,15 @@ int cloud_segments(const char* who_c, int32_t B, const int32_t* off1, const int3
   out->dev1 = dev[0];
   out->dev2 = dev[1];
   return OLSR_OK;
+}
+
+// what is wrong with the sizes of olsr_mask_smooth / olsr_query_eval, if anything
+const char* query_eval_size_error(int32_t P, int32_t H, int32_t W) {
+  if (P < 1 || P > OLSR_QUERY_EVAL_MAX_PLANES) return "P must be between 1 and 65535";
+  if (H < 2 || W < 2) return "H and W must be >= 2 (the reference's window is empty below that)";
+  if (H > OLSR_QUERY_EVAL_MAX_EXTENT || W > OLSR_QUERY_EVAL_MAX_EXTENT || (int64_t)H * (int64_t)W > (int64_t)0x7FFFFFFF)
+    return "H and W must be <= 2^20 and H * W must fit an int32";
+  return nullptr;
 }
 
 }  // namespace
@@ -719,6 +728,54 @@ int olsr_chamfer(int32_t B, const int32_t* off1, const int32_t* off2, int32_t ma
   launch_chamfer(B, seg.dev1, seg.dev2, seg.total1, seg.total2, max_n1, max_n2, xyz1, xyz2, min_d2_1, nn_1, min_d2_2, nn_2,
                  mean, valid, scratch, (hipStream_t)hip_stream);
   return launch_check("chamfer");
+}
+
+int olsr_mask_smooth(int32_t P, int32_t H, int32_t W, const uint8_t* mask_in, uint8_t* mask_out, void* hip_stream) {
+  if (const char* e = query_eval_size_error(P, H, W)) return fail(OLSR_ERR_ARG, std::string("mask_smooth: ") + e);
+  if (!mask_in || !mask_out) return fail(OLSR_ERR_ARG, "mask_smooth: mask_in and mask_out are required");
+  if (mask_in == mask_out) return fail(OLSR_ERR_ARG, "mask_smooth: mask_out must not be mask_in (a tile reads its neighbours' pixels)");
+  launch_mask_smooth(P, H, W, mask_in, mask_out, (hipStream_t)hip_stream);
+  return launch_check("mask_smooth");
+}
+
+size_t olsr_query_eval_scratch_bytes(int32_t P, int32_t H, int32_t W) {
+  return query_eval_size_error(P, H, W) ? ALIGN : query_eval_scratch_bytes(P, H, W);
+}
+
+int olsr_query_eval(int32_t P, int32_t H, int32_t W, const uint8_t* mask, const float* smoothed, const float* score,
+                    const uint8_t* gt_mask, const float* boxes, const int32_t* box_offsets, int32_t* result,
+                    uint8_t* mask_smoothed, void* scratch, void* hip_stream) {
+  const hipStream_t st = (hipStream_t)hip_stream;
+  if (const char* e = query_eval_size_error(P, H, W)) return fail(OLSR_ERR_ARG, std::string("query_eval: ") + e);
+  if (!mask || !smoothed || !score || !gt_mask) return fail(OLSR_ERR_ARG, "query_eval: mask, smoothed, score and gt_mask are required");
+  if (!box_offsets) return fail(OLSR_ERR_ARG, "query_eval: box_offsets is required");
+  if (!result || !scratch) return fail(OLSR_ERR_ARG, "query_eval: result and scratch are required");
+  if (mask_smoothed == mask) return fail(OLSR_ERR_ARG, "query_eval: mask_smoothed must not be mask (a tile reads its neighbours' pixels)");
+  std::vector<int32_t> h;
+  bool on_device;
+  OLSR_TRY(cloud_offsets("query_eval", "box_offsets", P, box_offsets, 0x7FFFFFFF, st, h, &on_device));
+  if (h[P] > 0 && !boxes) return fail(OLSR_ERR_ARG, "query_eval: boxes is required when box_offsets lists any");
+  const int32_t* dev = box_offsets;
+  if (!on_device) {
+    int32_t* park = query_eval_scratch_offsets(scratch, P, H, W);
+    HIP_TRY(hipMemcpyAsync(park, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipStreamSynchronize(st));   // h goes away
+    dev = park;
+  }
+  launch_query_eval(P, H, W, mask, smoothed, score, gt_mask, boxes, dev, result, mask_smoothed, scratch, st);
+  return launch_check("query_eval");
+}
+
+size_t olsr_image_psnr_scratch_bytes(void) { return image_psnr_scratch_bytes(); }
+
+int olsr_image_psnr(int32_t C, int32_t H, int32_t W, const float* image, const float* gt, double* out, void* scratch,
+                    void* hip_stream) {
+  if (C < 1 || H < 1 || W < 1) return fail(OLSR_ERR_ARG, "image_psnr: C, H and W must be >= 1");
+  const int64_t n = (int64_t)C * (int64_t)H * (int64_t)W;
+  if (n > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "image_psnr: C * H * W must fit an int32");
+  if (!image || !gt || !out || !scratch) return fail(OLSR_ERR_ARG, "image_psnr: image, gt, out and scratch are required");
+  launch_image_psnr(n, image, gt, out, scratch, (hipStream_t)hip_stream);
+  return launch_check("image_psnr");
 }
 
 }  // extern "C"

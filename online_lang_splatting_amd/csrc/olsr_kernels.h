@@ -331,4 +331,16 @@ void launch_chamfer(int B, const int32_t* off1, const int32_t* off2, long long t
                     const float* xyz1, const float* xyz2, float* min_d2_1, int32_t* nn_1, float* min_d2_2, int32_t* nn_2,
                     double* mean, int32_t* valid, void* scratch, hipStream_t st);
 
+// k_query_eval.hip: the 2-D evaluation behind a text query (include/olsr.h): mask smoothing, IoU and localisation counts,
+// masked PSNR.  box_offsets_dev is a device pointer here; query_eval_scratch_offsets: where in the scratch the entry parks
+// offsets that arrived in host memory.
+void launch_mask_smooth(int P, int H, int W, const uint8_t* mask_in, uint8_t* mask_out, hipStream_t st);
+size_t query_eval_scratch_bytes(int P, int H, int W);
+int32_t* query_eval_scratch_offsets(void* scratch, int P, int H, int W);
+void launch_query_eval(int P, int H, int W, const uint8_t* mask, const float* smoothed, const float* score,
+                       const uint8_t* gt_mask, const float* boxes, const int32_t* box_offsets_dev, int32_t* result,
+                       uint8_t* mask_smoothed, void* scratch, hipStream_t st);
+size_t image_psnr_scratch_bytes();
+void launch_image_psnr(long long n, const float* image, const float* gt, double* out, void* scratch, hipStream_t st);
+
 }  // namespace olsr
