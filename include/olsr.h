@@ -1406,6 +1406,16 @@ int olsr_debug_sort_threads(int threads);
  * Synchronous, on the null stream. */
 int olsr_debug_exp_sweep(uint32_t first_bits, uint64_t count, uint64_t out[4]);
 
+/* Test instrument (never on a product path): the activations the preprocess kernels apply to raw parameters (OLSR_ACT_*),
+ * evaluated by the device functions those kernels call (csrc/olsr_device.h: act_sigmoid, expf, act_normalize4), one thread per
+ * Gaussian.  For each (raw, out) pair — opacities [P], scales [P,3], rotations [P,4], device memory — an array whose bit is set
+ * in `activations` gets sigmoid / exp / normalize, an array whose bit is clear is copied; a pair with a NULL end is skipped.
+ * With these values as an activations = 0 scene, every other step of the raw-parameter path can be held to an equality
+ * (tests/test_gpu_activations.py).  OLSR_ERR_ARG: P < 0, bits outside OLSR_ACT_*.  Asynchronous on hip_stream. */
+int olsr_debug_activate(int32_t P, int32_t activations, const float *opacities_raw, const float *scales_raw,
+                        const float *rotations_raw, float *opacities_out, float *scales_out, float *rotations_out,
+                        void *hip_stream);
+
 const char *olsr_last_error(void);
 const char *olsr_version(void);
 

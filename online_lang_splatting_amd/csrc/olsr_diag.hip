@@ -1,5 +1,5 @@
 // olsr_diag.hip — diagnostics and test hooks of the C-ABI: profiling marks, composite stamps, the radix passes' knobs and
-// their seeding from the environment, the state buffers' fields by name, and the olsr_debug_* setters.
+// their seeding from the environment, the state buffers' fields by name, the olsr_debug_* setters and the activation hook.
 #include <hip/hip_runtime.h>
 
 #include <cstdlib>
@@ -67,6 +67,40 @@ __global__ __launch_bounds__(256) void exp_sweep_kernel(u32 first, unsigned long
   if (bad_x) atomicAdd(acc + 1, bad_x);
   if (bad_y) atomicAdd(acc + 2, bad_y);
   if (first_bad != ~0ull) atomicMin(acc + 3, first_bad);
+}
+
+// olsr_debug_activate: the activations the preprocess kernels fold in (OLSR_ACT_*), through the very device functions they
+// call — act_sigmoid / expf / act_normalize4 of olsr_device.h —, a Gaussian per thread.  An array whose flag is off is copied.
+__global__ __launch_bounds__(256) void debug_activate_kernel(int P, int act, const float* __restrict__ opacities_raw,
+                                                             const float* __restrict__ scales_raw,
+                                                             const float* __restrict__ rotations_raw,
+                                                             float* __restrict__ opacities_out, float* __restrict__ scales_out,
+                                                             float* __restrict__ rotations_out) {
+  const int r = blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= P) return;
+  const size_t idx = (size_t)r;
+  if (opacities_raw) {
+    const float x = opacities_raw[idx];
+    opacities_out[idx] = (act & OLSR_ACT_OPACITY_SIGMOID) ? act_sigmoid(x) : x;
+  }
+  if (scales_raw) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+      const float v = scales_raw[3 * idx + k];
+      scales_out[3 * idx + k] = (act & OLSR_ACT_SCALE_EXP) ? expf(v) : v;
+    }
+  }
+  if (rotations_raw) {
+    float q4[4];
+    if (act & OLSR_ACT_ROTATION_NORMALIZE) {
+      act_normalize4(rotations_raw + 4 * idx, q4);
+    } else {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) q4[k] = rotations_raw[4 * idx + k];
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k) rotations_out[4 * idx + k] = q4[k];
+  }
 }
 
 }  // namespace
@@ -238,6 +272,21 @@ int olsr_debug_exp_sweep(uint32_t first_bits, uint64_t count, uint64_t* out) {
   if (!ok) return OLSR_ERR_DEVICE;
   for (int i = 0; i < 4; ++i) out[i] = host[i];
   return OLSR_OK;
+}
+
+int olsr_debug_activate(int32_t P, int32_t activations, const float* opacities_raw, const float* scales_raw,
+                        const float* rotations_raw, float* opacities_out, float* scales_out, float* rotations_out,
+                        void* hip_stream) {
+  if (P < 0) return fail(OLSR_ERR_ARG, "debug_activate: P must be >= 0");
+  if (activations & ~(OLSR_ACT_OPACITY_SIGMOID | OLSR_ACT_SCALE_EXP | OLSR_ACT_ROTATION_NORMALIZE))
+    return fail(OLSR_ERR_ARG, "debug_activate: activations holds unknown OLSR_ACT_* bits");
+  // a pair of which either end is NULL is skipped
+  const bool op = opacities_raw && opacities_out, sc = scales_raw && scales_out, rot = rotations_raw && rotations_out;
+  if (P == 0 || !(op || sc || rot)) return OLSR_OK;
+  debug_activate_kernel<<<(unsigned)(((int64_t)P + 255) / 256), 256, 0, (hipStream_t)hip_stream>>>(
+      P, activations, op ? opacities_raw : nullptr, sc ? scales_raw : nullptr, rot ? rotations_raw : nullptr, opacities_out,
+      scales_out, rotations_out);
+  return launch_check("debug_activate");
 }
 
 size_t olsr_debug_backward_ordered_scratch_bytes(int64_t num_rendered, int32_t F) {
