@@ -999,8 +999,8 @@ int olsr_hr_net_forward(const olsr_hr_net_params *params, const float *fv, const
 /* ---- TSDF fusion of depth and language maps into a 3-D map (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) ---------------
  * The reference's 3-D evaluation fuses, per keyframe, a depth image and a feature image (packed 8-bit colour in fusion.py, 3
  * float channels in fusion2.py, 15 in fusion3.py) into a truncated signed distance volume with one CUDA launch per frame, 16
- * image uploads per frame and 15 separate feature volumes, and takes the surface points of that volume from skimage's marching
- * cubes on the host.  Here the volume stays on the device:
+ * image uploads per frame and 15 separate feature volumes, and takes the surface points and the mesh of that volume from
+ * skimage's marching cubes on the host.  Here the volume stays on the device:
  *   tsdf   float[X,Y,Z] (z fastest), 1 where nothing was observed;  weight float[X,Y,Z], 0 there
  *   feat   OLSR_TSDF_FEAT_FLOAT: float[F,X,Y,Z], planar (the running mean of every channel; F = 0: geometry only, feat unused)
  *          OLSR_TSDF_FEAT_PACKED_RGB: float[X,Y,Z], one float b * 65536 + g * 256 + r per voxel as in fusion.py (F must be 1)
@@ -1041,8 +1041,29 @@ int olsr_hr_net_forward(const olsr_hr_net_params *params, const float *fv, const
  *   - its features are those of the voxel rintf(pos) (the reference's np.round(verts).astype(int)); packed mode emits r, g, b;
  *   - order: voxel linear index, then axis.
  *   points float[N,3];  feats float[N,F] (packed: [N,3]; F = 0: may be NULL);  voxel_index int32[N] or NULL: the owner's linear index
- * These are the edge vertices of marching cubes at level 0.  Faces, normals and the interior vertices Lewiner's variant adds in
- * ambiguous cells are not produced: this is a point cloud, and no parity with skimage's mesh is claimed.
+ * These are the edge vertices of marching cubes at level 0, and the vertices of the mesh below.
+ * olsr_tsdf_mesh_plan / olsr_tsdf_mesh_emit extract the surface as a triangle mesh, by the same pattern (count, prefix in block
+ * order, emit; no atomics, deterministic order, one host read): plan writes status = {n_verts, n_faces, 0, 0} (n_faces clamped
+ * to 2^31 - 1), the caller reads those, allocates, and emit writes the mesh.
+ *   - the vertices are olsr_tsdf_surface_emit's: same rule, same order, same bits of points, feats and voxel_index;
+ *   - a cube is owned by its lowest voxel v (x + 1 < X, y + 1 < Y, z + 1 < Z); its configuration has bit c set when the corner
+ *     v + (c & 1, c >> 1 & 1, c >> 2 & 1) has tsdf < 0 (a NaN is not negative); with min_weight > 0 a cube is triangulated only
+ *     when all eight corners have weight >= min_weight;
+ *   - its triangles come from a generated table (csrc/olsr_mc_table.h, scripts/gen_mc_table.py states the rule: marching squares
+ *     on every face, a face whose signs alternate cuts its two negative corners off separately, the closed loops fanned).  Two
+ *     cubes that share a face draw the same segments on it, so the mesh is closed away from the volume's boundary and from
+ *     cubes left out by min_weight.  No interior vertices and no asymptotic decider (Lewiner's variant, which skimage uses, has
+ *     both): no parity with skimage's faces, vertex order or winding is claimed;
+ *   - faces int32[M,3] index the vertex list, in cube linear order (z fastest), then table order; a face (i, j, k) is wound so
+ *     that cross(v_j - v_i, v_k - v_i) points to the positive-distance (free-space) side;
+ *   - normals float[N,3], per vertex: g(v) = the gradient of tsdf by central differences 0.5f * (t[+1] - t[-1]), one-sided
+ *     (t[+1] - t[0], t[0] - t[-1]) on the grid's border and 0 along an axis of one voxel;  n = g0 + (g1 - g0) * mu at the edge's two
+ *     voxels with the vertex's mu = t0 / (t0 - t1);  normal = n / sqrtf(nx * nx + ny * ny + nz * nz) (summed left to right), (0, 0, 0)
+ *     where that length is 0.  It points to free space, like the winding.  float32 without contraction: a numpy restatement
+ *     gives the same bits;
+ *   - emit writes vertices below vert_capacity and faces below face_capacity only; its min_weight is the plan's (the plan's
+ *     scratch holds what it decided).  3 * face_capacity must fit an int32: OLSR_ERR_ARG otherwise.
+ *   scratch: olsr_tsdf_mesh_scratch_bytes = 4 bytes per voxel, four 32-bit words per block of 256 voxels, and 16.
  * Limits: X * Y * Z < 2^31 for integrate and init, 3 * X * Y * Z < 2^31 for the extraction. */
 #define OLSR_TSDF_MAX_VIEWS 16
 #define OLSR_TSDF_FEAT_FLOAT 0
@@ -1074,6 +1095,12 @@ int olsr_tsdf_surface_plan(const olsr_tsdf_volume *volume, float min_weight, voi
                            void *hip_stream);
 int olsr_tsdf_surface_emit(const olsr_tsdf_volume *volume, float min_weight, const void *scratch, int32_t capacity,
                            float *points, float *feats, int32_t *voxel_index, void *hip_stream);
+size_t olsr_tsdf_mesh_scratch_bytes(int32_t X, int32_t Y, int32_t Z);
+int olsr_tsdf_mesh_plan(const olsr_tsdf_volume *volume, float min_weight, void *scratch, int32_t *status /* [4] */,
+                        void *hip_stream);
+int olsr_tsdf_mesh_emit(const olsr_tsdf_volume *volume, float min_weight, const void *scratch, int32_t vert_capacity,
+                        int32_t face_capacity, float *points, float *normals, float *feats, int32_t *voxel_index,
+                        int32_t *faces /* [M,3] */, void *hip_stream);
 
 /* ---- point-cloud metrics: approximate earth mover's distance and Chamfer distance (the reference's 3-D evaluation) ----------
  * The two numbers tsdf-fusion/3d_evaluation_and_visualize_langslam_dim15.py:396-423 reports per queried class, for ragged

@@ -1,4 +1,4 @@
-// k_tsdf.hip — TSDF fusion of depth and feature images into a voxel volume, and its surface point cloud (include/olsr.h,
+// k_tsdf.hip — TSDF fusion of depth and feature images into a voxel volume, its surface point cloud and mesh (include/olsr.h,
 // "TSDF fusion").
 //
 // The reference (tsdf-fusion/fusion.py, fusion2.py, fusion3.py) launches one `integrate` kernel per frame after uploading the
@@ -13,6 +13,9 @@
 //   tsdf_surface_count / tsdf_surface_prefix / tsdf_surface_emit
 //                              count the zero crossings each voxel owns, prefix the block counts in block order, write the
 //                              points: the pattern of k_map_edit.hip, no atomics, output in voxel order then axis.
+//   tsdf_mesh_count / tsdf_mesh_prefix / tsdf_mesh_emit
+//                              the same vertices with their normals and the triangles between them, from the generated table of
+//                              olsr_mc_table.h: the same pattern, one 32-bit word per voxel between the passes.
 //
 // Per voxel and view the float32 expressions are the reference kernel's, in its order (fusion.py:93-139, fusion3.py:181-290);
 // the translation unit is compiled without FMA contraction (build.py) and float division is correctly rounded, so the volume
@@ -31,6 +34,7 @@
 // of views; the image gathers of neighbouring voxels fall on neighbouring pixels and are served by the caches.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_mc_table.h"
 
 namespace olsr {
 
@@ -157,6 +161,36 @@ __device__ inline int ts_crossings(const olsr_tsdf_volume& vol, float min_weight
   return bits;
 }
 
+// vertex k: the zero crossing of the edge from voxel i = (x, y, z) along axis a (its other end: i + stride); t0 = tsdf[i]
+__device__ __forceinline__ void ts_write_vertex(const olsr_tsdf_volume& vol, int N, int i, int a, int stride, int x, int y, int z, float t0,
+                                       int k, float* __restrict__ points, float* __restrict__ feats,
+                                       int32_t* __restrict__ voxel_index) {
+  const int planes = vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB ? 3 : vol.F;
+  const float t1 = vol.tsdf[i + stride];
+  const float v[3] = {(float)x, (float)y, (float)z};
+  float pos[3] = {v[0], v[1], v[2]};
+  pos[a] = v[a] + t0 / (t0 - t1);
+  // the voxel the reference reads the vertex's colour from: np.round(verts).astype(int) — the owner or its neighbour
+  // (a NaN position, from a NaN or infinite distance, stays with the owner)
+  const int nearest = rintf(pos[a]) == v[a] + 1.0f ? i + stride : i;
+#pragma unroll
+  for (int d = 0; d < 3; ++d) points[(size_t)3 * k + d] = pos[d] * vol.voxel_size + vol.origin[d];
+  if (voxel_index) voxel_index[k] = i;
+  if (feats) {
+    if (vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB) {
+      const float rgb_val = vol.feat[nearest];
+      const float b = floorf(rgb_val / 65536.0f);
+      const float g = floorf((rgb_val - b * 65536.0f) / 256.0f);
+      const float r = rgb_val - b * 65536.0f - g * 256.0f;
+      feats[(size_t)3 * k] = r;
+      feats[(size_t)3 * k + 1] = g;
+      feats[(size_t)3 * k + 2] = b;
+    } else {
+      for (int c = 0; c < planes; ++c) feats[(size_t)planes * k + c] = vol.feat[(size_t)c * N + nearest];
+    }
+  }
+}
+
 template <bool EMIT>
 __global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol, float min_weight, int32_t* __restrict__ counts,
                                                            const int32_t* __restrict__ offsets, int capacity,
@@ -185,34 +219,11 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_surface(olsr_tsdf_volume vol,
     if (!bits) return;
     int k = offsets[blockIdx.x] + rank;
     const int stride[3] = {YZ, vol.Z, 1};
-    const int planes = vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB ? 3 : vol.F;
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
       if (!(bits & (1 << a))) continue;
       if (k >= capacity) return;
-      const float t1 = vol.tsdf[i + stride[a]];
-      const float v[3] = {(float)x, (float)y, (float)z};
-      float pos[3] = {v[0], v[1], v[2]};
-      pos[a] = v[a] + t0 / (t0 - t1);
-      // the voxel the reference reads the vertex's colour from: np.round(verts).astype(int) — the owner or its neighbour
-      // (a NaN position, from a NaN or infinite distance, stays with the owner)
-      const int nearest = rintf(pos[a]) == v[a] + 1.0f ? i + stride[a] : i;
-#pragma unroll
-      for (int d = 0; d < 3; ++d) points[(size_t)3 * k + d] = pos[d] * vol.voxel_size + vol.origin[d];
-      if (voxel_index) voxel_index[k] = i;
-      if (feats) {
-        if (vol.feat_mode == OLSR_TSDF_FEAT_PACKED_RGB) {
-          const float rgb_val = vol.feat[nearest];
-          const float b = floorf(rgb_val / 65536.0f);
-          const float g = floorf((rgb_val - b * 65536.0f) / 256.0f);
-          const float r = rgb_val - b * 65536.0f - g * 256.0f;
-          feats[(size_t)3 * k] = r;
-          feats[(size_t)3 * k + 1] = g;
-          feats[(size_t)3 * k + 2] = b;
-        } else {
-          for (int c = 0; c < planes; ++c) feats[(size_t)planes * k + c] = vol.feat[(size_t)c * N + nearest];
-        }
-      }
+      ts_write_vertex(vol, N, i, a, stride[a], x, y, z, t0, k, points, feats, voxel_index);
       ++k;
     }
   }
@@ -227,6 +238,167 @@ __global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_surface_prefix(int nb,
   if (threadIdx.x == 0) {
     status[0] = total;
     status[1] = 0;
+  }
+}
+
+// ---- the mesh: the same vertices, their normals, and the triangles between them ------------------------------------------------
+// One thread per voxel, as above.  A voxel owns up to three vertices (ts_crossings' rule) and, when x + 1 < X, y + 1 < Y and
+// z + 1 < Z, the cube whose lowest corner it is.  The count pass leaves one word per voxel,
+//   bits 0-9 the rank of its first vertex within its block (< 3 * 256), 10-12 its crossing bits,
+//   13-23 the rank of its cube's first face within the block (<= 5 * 256), 24-31 the cube's sign configuration (0: no faces),
+// and the per-block totals; after the prefix a vertex's id is offsets[block] + rank + popc(crossing bits below its axis), for
+// the voxel's own edges and for the neighbours' edges a cube's faces name alike.  The emit pass reads that word first: a voxel
+// away from the surface costs it 4 bytes.  The triangle table (olsr_mc_table.h, 2 KiB) is copied to LDS by every workgroup:
+// each lane indexes it with its own configuration, which through the scalar constant path would be one load per lane.
+// scratch: [vertex counts nb] [vertex offsets nb] [face counts nb] [face offsets nb] [voxel words X*Y*Z], 32 bits each
+static_assert(TS_THREADS == 256, "the table copy and the word's rank fields assume 256 voxels per block");
+
+size_t tsdf_mesh_scratch_bytes(int X, int Y, int Z) {
+  const size_t N = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
+  return (4 * ts_blocks(N) + N) * sizeof(u32) + 16;
+}
+
+// bits: ts_crossings' result for voxel i; config: bit c set when corner c = (c & 1, c >> 1 & 1, c >> 2 & 1) of the cube the
+// voxel owns is negative, 0 when it owns none or (min_weight > 0) a corner has less than that weight.  A NaN is not negative.
+__device__ inline void ts_mesh_voxel(const olsr_tsdf_volume& vol, float min_weight, int i, int x, int y, int z, int* bits,
+                                     int* config) {
+  const int YZ = vol.Y * vol.Z;
+  const bool use_w = min_weight > 0.0f;
+  const bool inside[3] = {x + 1 < vol.X, y + 1 < vol.Y, z + 1 < vol.Z};
+  int neg = 0, seen = 0;
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const int dx = c & 1, dy = (c >> 1) & 1, dz = c >> 2;
+    if ((dx && !inside[0]) || (dy && !inside[1]) || (dz && !inside[2])) continue;
+    const int j = i + dx * YZ + dy * vol.Z + dz;
+    if (vol.tsdf[j] < 0.0f) neg |= 1 << c;
+    if (!use_w || vol.weight[j] >= min_weight) seen |= 1 << c;
+  }
+  int b = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const int c = 1 << a;  // the corner one step along axis a
+    if (inside[a] && (seen & 1) && (seen & (1 << c)) && ((neg >> c) & 1) != (neg & 1)) b |= 1 << a;
+  }
+  *bits = b;
+  *config = (inside[0] && inside[1] && inside[2] && seen == 0xff) ? neg : 0;
+}
+
+__global__ __launch_bounds__(TS_THREADS) void tsdf_mesh_count(olsr_tsdf_volume vol, float min_weight, u32* __restrict__ vcounts,
+                                                              u32* __restrict__ fcounts, u32* __restrict__ words) {
+  __shared__ u32 wave_sums[TS_WAVES];
+  __shared__ u64 table[256];
+  table[threadIdx.x] = MC_TABLE[threadIdx.x];
+  const int N = vol.X * vol.Y * vol.Z;
+  const int YZ = vol.Y * vol.Z;
+  const int i = blockIdx.x * TS_THREADS + threadIdx.x;
+  int bits = 0, config = 0;
+  if (i < N) {
+    const int x = i / YZ, rem = i - x * YZ;
+    const int y = rem / vol.Z, z = rem - y * vol.Z;
+    ts_mesh_voxel(vol, min_weight, i, x, y, z, &bits, &config);
+  }
+  __syncthreads();
+  const u32 n_faces = (u32)(table[config] & 15u);
+  if (!n_faces) config = 0;
+  // one scan for both counts: the vertices in the low half (<= 768 per block), the faces in the high half (<= 1280)
+  u32 total;
+  const u32 rank = block_excl_scan<TS_WAVES>((u32)__popc(bits) | n_faces << 16, wave_sums, &total);
+  if (i < N) words[i] = (rank & 0xffffu) | (u32)bits << 10 | (rank >> 16) << 13 | (u32)config << 24;
+  if (threadIdx.x == 0) {
+    vcounts[blockIdx.x] = total & 0xffffu;
+    fcounts[blockIdx.x] = total >> 16;
+  }
+}
+
+// exclusive prefixes of the vertex and the face counts in block order; status = {vertices, faces, 0, 0}.  The faces are summed
+// without sign (up to 5 per voxel: beyond 2^31 in the largest volumes) and reported clamped; the emit entry refuses a
+// face_capacity whose 3-fold does not fit an int32.
+__global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_mesh_prefix(int nb, u32* __restrict__ scratch,
+                                                                       int32_t* __restrict__ status) {
+  __shared__ u32 s_w[TS_PREFIX_THREADS / 64];
+  const u32 n_verts = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, scratch, scratch + nb, s_w);
+  const u32 n_faces = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, scratch + 2 * (size_t)nb, scratch + 3 * (size_t)nb, s_w);
+  if (threadIdx.x == 0) {
+    status[0] = (int32_t)n_verts;
+    status[1] = (int32_t)(n_faces < 0x7fffffffu ? n_faces : 0x7fffffffu);
+    status[2] = 0;
+    status[3] = 0;
+  }
+}
+
+// d tsdf / d axis at voxel j, whose coordinate along that axis is c of n: central, one-sided on the border
+__device__ __forceinline__ float ts_gradient(const float* __restrict__ t, int j, int c, int n, int stride) {
+  if (n < 2) return 0.0f;
+  if (c == 0) return t[j + stride] - t[j];
+  if (c == n - 1) return t[j] - t[j - stride];
+  return 0.5f * (t[j + stride] - t[j - stride]);
+}
+
+__global__ __launch_bounds__(TS_THREADS) void tsdf_mesh_emit(olsr_tsdf_volume vol, const u32* __restrict__ scratch, int nb,
+                                                             int vert_capacity, int face_capacity, float* __restrict__ points,
+                                                             float* __restrict__ normals, float* __restrict__ feats,
+                                                             int32_t* __restrict__ voxel_index, int32_t* __restrict__ faces) {
+  __shared__ u64 table[256];
+  table[threadIdx.x] = MC_TABLE[threadIdx.x];
+  __syncthreads();
+  const u32* voffsets = scratch + nb;
+  const u32* foffsets = scratch + 3 * (size_t)nb;
+  const u32* words = scratch + 4 * (size_t)nb;
+  const int N = vol.X * vol.Y * vol.Z;
+  const int YZ = vol.Y * vol.Z;
+  const int i = blockIdx.x * TS_THREADS + threadIdx.x;
+  if (i >= N) return;
+  const u32 word = words[i];
+  const int bits = (word >> 10) & 7, config = word >> 24;
+  if (!bits && !config) return;
+  const int stride[3] = {YZ, vol.Z, 1};
+  if (bits) {
+    const int x = i / YZ, rem = i - x * YZ;
+    const int y = rem / vol.Z, z = rem - y * vol.Z;
+    const int coord[3] = {x, y, z}, dim[3] = {vol.X, vol.Y, vol.Z};
+    const float t0 = vol.tsdf[i];
+    float g0[3];
+#pragma unroll
+    for (int d = 0; d < 3; ++d) g0[d] = ts_gradient(vol.tsdf, i, coord[d], dim[d], stride[d]);
+    int k = (int)(voffsets[blockIdx.x] + (word & 1023u));
+#pragma unroll
+    for (int a = 0; a < 3; ++a) {
+      if (!(bits & (1 << a))) continue;
+      if (k >= vert_capacity) break;
+      ts_write_vertex(vol, N, i, a, stride[a], x, y, z, t0, k, points, feats, voxel_index);
+      // the normal: the two voxels' gradients, interpolated with the vertex's own mu, over their length
+      const int j = i + stride[a];
+      const float mu = t0 / (t0 - vol.tsdf[j]);
+      float n[3];
+#pragma unroll
+      for (int d = 0; d < 3; ++d) {
+        const float g1 = ts_gradient(vol.tsdf, j, coord[d] + (d == a ? 1 : 0), dim[d], stride[d]);
+        n[d] = g0[d] + (g1 - g0[d]) * mu;
+      }
+      const float len = sqrtf(n[0] * n[0] + n[1] * n[1] + n[2] * n[2]);
+#pragma unroll
+      for (int d = 0; d < 3; ++d) normals[(size_t)3 * k + d] = len == 0.0f ? 0.0f : n[d] / len;
+      ++k;
+    }
+  }
+  if (config) {
+    const u64 entry = table[config];
+    const u32 n_faces = (u32)(entry & 15u);
+    const u32 f0 = foffsets[blockIdx.x] + ((word >> 13) & 2047u);
+    for (u32 t = 0; t < n_faces; ++t) {
+      const u32 f = f0 + t;
+      if (f >= (u32)face_capacity) break;
+#pragma unroll
+      for (int c = 0; c < 3; ++c) {
+        // edge 4 * axis + k: owned by the corner whose two other coordinates, in ascending axis order, are (k & 1, k >> 1)
+        const int e = (int)(entry >> (4 + 4 * (3 * t + c))) & 15;
+        const int axis = e >> 2, lo = e & 1, hi = (e >> 1) & 1;
+        const int owner = i + lo * (axis == 0 ? vol.Z : YZ) + hi * (axis == 2 ? vol.Z : 1);
+        const u32 w = words[owner];
+        faces[(size_t)3 * f + c] = (int32_t)(voffsets[owner / TS_THREADS] + (w & 1023u) + __popc((w >> 10) & ((1u << axis) - 1u)));
+      }
+    }
   }
 }
 
@@ -270,6 +442,20 @@ void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, con
   const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
   const int32_t* offsets = reinterpret_cast<const int32_t*>(scratch) + nb;
   tsdf_surface<true><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, nullptr, offsets, capacity, points, feats, voxel_index);
+}
+
+void launch_tsdf_mesh_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st) {
+  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
+  u32* s = reinterpret_cast<u32*>(scratch);
+  tsdf_mesh_count<<<nb, TS_THREADS, 0, st>>>(vol, min_weight, s, s + 2 * (size_t)nb, s + 4 * (size_t)nb);
+  tsdf_mesh_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, s, status);
+}
+
+void launch_tsdf_mesh_emit(const olsr_tsdf_volume& vol, const void* scratch, int vert_capacity, int face_capacity, float* points,
+                           float* normals, float* feats, int32_t* voxel_index, int32_t* faces, hipStream_t st) {
+  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
+  tsdf_mesh_emit<<<nb, TS_THREADS, 0, st>>>(vol, reinterpret_cast<const u32*>(scratch), nb, vert_capacity, face_capacity, points,
+                                            normals, feats, voxel_index, faces);
 }
 
 }  // namespace olsr

@@ -702,6 +702,32 @@ int olsr_tsdf_surface_emit(const olsr_tsdf_volume* volume, float min_weight, con
   return launch_check("tsdf_surface_emit");
 }
 
+size_t olsr_tsdf_mesh_scratch_bytes(int32_t X, int32_t Y, int32_t Z) { return tsdf_mesh_scratch_bytes(X, Y, Z); }
+
+int olsr_tsdf_mesh_plan(const olsr_tsdf_volume* volume, float min_weight, void* scratch, int32_t* status, void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, true)) return fail(OLSR_ERR_ARG, std::string("tsdf_mesh_plan: ") + e);
+  if (!scratch || !status) return fail(OLSR_ERR_ARG, "tsdf_mesh_plan: scratch and status are required");
+  launch_tsdf_mesh_plan(*volume, min_weight, scratch, status, (hipStream_t)hip_stream);
+  return launch_check("tsdf_mesh_plan");
+}
+
+int olsr_tsdf_mesh_emit(const olsr_tsdf_volume* volume, float min_weight, const void* scratch, int32_t vert_capacity,
+                        int32_t face_capacity, float* points, float* normals, float* feats, int32_t* voxel_index, int32_t* faces,
+                        void* hip_stream) {
+  if (const char* e = tsdf_volume_error(volume, true)) return fail(OLSR_ERR_ARG, std::string("tsdf_mesh_emit: ") + e);
+  if (vert_capacity < 0 || face_capacity < 0 || !scratch)
+    return fail(OLSR_ERR_ARG, "tsdf_mesh_emit: scratch, vert_capacity >= 0 and face_capacity >= 0 are required");
+  if (face_capacity > INT32_MAX / 3) return fail(OLSR_ERR_ARG, "tsdf_mesh_emit: 3 face_capacity must be below 2^31");
+  if (vert_capacity == 0 && face_capacity == 0) return OLSR_OK;
+  if (vert_capacity > 0 && (!points || !normals || (volume->F > 0 && !feats)))
+    return fail(OLSR_ERR_ARG, "tsdf_mesh_emit: points, normals and (F > 0) feats are required");
+  if (face_capacity > 0 && !faces) return fail(OLSR_ERR_ARG, "tsdf_mesh_emit: faces is required");
+  (void)min_weight;  // (the plan's words hold what it decided)
+  launch_tsdf_mesh_emit(*volume, scratch, vert_capacity, face_capacity, points, normals, volume->F > 0 ? feats : nullptr,
+                        voxel_index, faces, (hipStream_t)hip_stream);
+  return launch_check("tsdf_mesh_emit");
+}
+
 size_t olsr_emd_scratch_bytes(int32_t B, int64_t total1, int64_t total2) { return emd_scratch_bytes(B, total1, total2); }
 
 int olsr_emd_cost(int32_t B, const int32_t* off1, const int32_t* off2, int32_t max_n1, int32_t max_n2, const float* xyz1,

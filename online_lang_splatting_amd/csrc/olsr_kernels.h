@@ -309,13 +309,17 @@ size_t hr_net_workspace_bytes(long long h, long long w);
 void launch_hr_net(const olsr_hr_net_params& p, const float* fv, const float* f3, const float* f2, const float* packed,
                    float* workspace, float* out, hipStream_t st);
 
-// k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface point cloud (include/olsr.h)
+// k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface as a point cloud and as a mesh (include/olsr.h)
 void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st);
 void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_tsdf_view* views, hipStream_t st);
 size_t tsdf_surface_scratch_bytes(int X, int Y, int Z);
 void launch_tsdf_surface_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st);
 void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, const void* scratch, int capacity, float* points,
                               float* feats, int32_t* voxel_index, hipStream_t st);
+size_t tsdf_mesh_scratch_bytes(int X, int Y, int Z);
+void launch_tsdf_mesh_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st);
+void launch_tsdf_mesh_emit(const olsr_tsdf_volume& vol, const void* scratch, int vert_capacity, int face_capacity, float* points,
+                           float* normals, float* feats, int32_t* voxel_index, int32_t* faces, hipStream_t st);
 
 // k_cloud_metrics.hip: approximate earth mover's distance and Chamfer distance of ragged batches of point clouds
 // (include/olsr.h).  off1 / off2 are device pointers here; *_scratch_offsets: where in the scratch the entries park offsets

@@ -4,9 +4,11 @@ Counterpart of the reference's tsdf-fusion/fusion.py (packed 8-bit colour), fusi
 float channels, what tsdf-fusion/dim15_recon.py fuses): `TSDFVolume(vol_bnds, voxel_size)` with `integrate(color_im, depth_im,
 cam_intr, cam_pose, obs_weight)`, `get_volume()` and `get_point_cloud()`.  The volume lives on the GPU, rendered maps go in as
 the device tensors the rasteriser returned (integrate_render), several views are fused in one launch (integrate_views), and
-the surface points come from the device as well.  get_point_cloud returns the zero crossings of the grid edges — the edge
-vertices of marching cubes at level 0 — not skimage's mesh: there are no faces or normals, and no parity with skimage's vertex
-list is claimed.  GPU only; there is no torch fallback.
+the surface comes from the device as well.  get_point_cloud returns the zero crossings of the grid edges — the edge vertices
+of marching cubes at level 0; get_mesh returns the same vertices with faces and normals, the triangles from a generated table
+(scripts/gen_mc_table.py) without Lewiner's interior vertices: no parity with skimage's vertex order, faces or winding is
+claimed.  meshwrite, meshwrite_color and pcwrite write the ASCII PLY files of fusion3.py (tsdf-fusion/dim15_recon.py:86-97), which
+the reference's 3-D evaluation reads back.  GPU only; there is no torch fallback.
 """
 import ctypes as C
 
@@ -93,7 +95,7 @@ class TSDFVolume:
         for k in range(3):
             self._vol.origin[k] = float(self._vol_origin[k])
         self._scratch = None
-        self._status = torch.zeros(2, dtype=torch.int32, device=self.device)
+        self._status = torch.zeros(4, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
             check(lib().olsr_tsdf_init(C.byref(self._vol), self._stream()))
 
@@ -266,12 +268,106 @@ class TSDFVolume:
                                            index.data_ptr() if n else None, self._stream()))
         return points, feats, index
 
+    def get_mesh(self, min_weight=0.0):
+        """-> (verts [N,3], faces int32 [M,3], norms [N,3], colors [N,F] or None), the reference's order, on the device.  The
+        vertices and colours are surface_points' (same order, same bits); a face (i, j, k) indexes them, wound so that
+        cross(v_j - v_i, v_k - v_i) points to free space, as the per-vertex normals do (the normalised gradient of the
+        distance).  min_weight > 0 triangulates only cubes whose eight voxels have at least that weight.  One host read of 16
+        bytes."""
+        return self._mesh(min_weight)[:4]
+
+    def _mesh(self, min_weight):
+        """get_mesh's tuple and voxel_index int32 [N], the owner of every vertex as surface_points returns it."""
+        L = lib()
+        X, Y, Z = self.vol_dim
+        nbytes = L.olsr_tsdf_mesh_scratch_bytes(X, Y, Z)
+        if self._scratch is None or self._scratch.numel() < nbytes:
+            self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        with torch.cuda.device(self.device):
+            check(L.olsr_tsdf_mesh_plan(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(),
+                                        self._status.data_ptr(), self._stream()))
+            n, m = self._status.tolist()[:2]   # the extraction's one host synchronisation: 16 bytes
+            if m > (2 ** 31 - 1) // 3:
+                raise RuntimeError(f"get_mesh: {m} or more faces, 3 * faces must stay below 2^31")
+            F = self.feature_dim
+            verts = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            norms = torch.empty((n, 3), dtype=torch.float32, device=self.device)
+            colors = torch.empty((n, F), dtype=torch.float32, device=self.device) if F > 0 else None
+            faces = torch.empty((m, 3), dtype=torch.int32, device=self.device)
+            index = torch.empty((n,), dtype=torch.int32, device=self.device)
+            check(L.olsr_tsdf_mesh_emit(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(), n, m,
+                                        verts.data_ptr() if n else None, norms.data_ptr() if n else None,
+                                        colors.data_ptr() if F > 0 and n else None, index.data_ptr() if n else None,
+                                        faces.data_ptr() if m else None, self._stream()))
+        return verts, faces, norms, colors, index
+
     def get_point_cloud(self, min_weight=0.0):
         """[N,3+F]: surface_points' points and features side by side (an "rgb" volume: x, y, z, r, g, b as floats)."""
         points, feats, _ = self.surface_points(min_weight)
         return points if feats is None else torch.cat([points, feats], dim=1)
 
     get_view_frustum = staticmethod(get_view_frustum)
+
+
+# ---- the PLY files of the reference's 3-D evaluation (fusion3.py meshwrite, meshwrite_color, pcwrite) ---------------------------
+_FEATURE_NAMES = ("red", "green", "blue") + tuple(f"f{k}" for k in range(4, 16))
+
+
+def _array(name, a, cols, dtype=np.float64):
+    if isinstance(a, torch.Tensor):
+        a = a.detach().cpu().numpy()
+    a = np.asarray(a)
+    if a.ndim != 2 or (cols is not None and a.shape[1] < cols):
+        raise RuntimeError(f"{name} has shape {tuple(a.shape)}, expected [N,{cols if cols is not None else 'C'}]")
+    return a if dtype is None else a.astype(dtype)
+
+
+def _write_ply(filename, vertex_properties, rows, faces=None):
+    lines = ["ply", "format ascii 1.0", f"element vertex {len(rows)}"] + [f"property {p}" for p in vertex_properties]
+    if faces is not None:
+        lines += [f"element face {len(faces)}", "property list uchar int vertex_index"]
+    lines.append("end_header")
+    lines += rows
+    if faces is not None:
+        lines += ["3 %d %d %d" % (f[0], f[1], f[2]) for f in faces.tolist()]
+    with open(filename, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
+def _mesh_arrays(who, verts, faces, norms, colors, n_colors):
+    verts, norms = _array(f"{who}: verts", verts, 3), _array(f"{who}: norms", norms, 3)
+    faces = _array(f"{who}: faces", faces, 3, np.int64)
+    colors = _array(f"{who}: colors", colors, n_colors, None)
+    if not (len(verts) == len(norms) == len(colors)):
+        raise RuntimeError(f"{who}: {len(verts)} verts, {len(norms)} norms and {len(colors)} colors")
+    return verts, faces, norms, colors
+
+
+def meshwrite(filename, verts, faces, norms, colors):
+    """The 15-feature mesh (semantic_mesh.ply): x y z nx ny nz and the features as floats named red, green, blue, f4 ... f15,
+    every number as "%f"; then "3 i j k" per face.  Tensors or arrays."""
+    verts, faces, norms, colors = _mesh_arrays("meshwrite", verts, faces, norms, colors, 15)
+    fmt = " ".join(["%f"] * 21)
+    rows = [fmt % tuple(r) for r in np.concatenate([verts, norms, colors[:, :15].astype(np.float64)], axis=1).tolist()]
+    _write_ply(filename, [f"float {n}" for n in ("x", "y", "z", "nx", "ny", "nz") + _FEATURE_NAMES], rows, faces)
+
+
+def meshwrite_color(filename, verts, faces, norms, colors):
+    """The coloured mesh (semantic_mesh_color.ply, one per queried class): x y z nx ny nz as "%f" and the first three colour
+    columns converted to uint8, "%d"."""
+    verts, faces, norms, colors = _mesh_arrays("meshwrite_color", verts, faces, norms, colors, 3)
+    rgb = colors.astype(np.uint8)
+    fmt = " ".join(["%f"] * 6 + ["%d"] * 3)
+    rows = [fmt % (tuple(a) + tuple(b)) for a, b in zip(np.concatenate([verts, norms], axis=1).tolist(), rgb[:, :3].tolist())]
+    _write_ply(filename, [f"float {n}" for n in ("x", "y", "z", "nx", "ny", "nz")] + [f"uchar {n}" for n in _FEATURE_NAMES[:3]],
+               rows, faces)
+
+
+def pcwrite(filename, xyzfeat):
+    """The 15-feature point cloud (semantic_pc.ply) from get_point_cloud's [N,18]: x y z and the features, "%f"."""
+    a = _array("pcwrite: xyzfeat", xyzfeat, 18)
+    fmt = " ".join(["%f"] * 18)
+    _write_ply(filename, [f"float {n}" for n in ("x", "y", "z") + _FEATURE_NAMES], [fmt % tuple(r) for r in a[:, :18].tolist()])
 
 
 def label_points(query, feats):

@@ -8,13 +8,19 @@ the torch-ops path alternating inside one repetition:
   twelve_singles    twelve launches of one view each
   batch_of_twelve   one launch of twelve views: the volume is read and written once per touched voxel, not twelve times
   extraction        TSDFVolume.surface_points (count, prefix, the 4-byte host read, emit), on a host clock around a synchronise
+  mesh              TSDFVolume.get_mesh on the same fused volume (count, prefix, the 16-byte host read, emit: the same vertices,
+                    their normals and the faces), on the same clock, alternating with `extraction` inside one repetition
   torch_ops_one_view / torch_ops_twelve_views
                     the same update written in torch ops on the device, vectorised over the voxels like the reference's CPU
                     path (tsdf-fusion/fusion.py:250-293) with the 15 channels of fusion3.py
 Bytes per the touched-voxel model: a voxel some view of a launch reaches costs one read and one write of its 2 + F floats;
-the images are read once (H W (2 + F) floats per view).  `share_of_8_TBps` is those bytes over the median time over the
+the images are read once (H W (2 + F) floats per view).  The two extractions: the distance of every voxel is read once per pass
+(the neighbours a voxel looks at are its block's or the next rows': cache hits), surface_points makes two such passes, get_mesh
+one and then writes and reads back 4 bytes per voxel; a point costs its 3 + F floats and its index written and F floats read, a
+vertex 3 floats more (the normal), a face 12 bytes.  `share_of_8_TBps` is those bytes over the median time over the
 8 TB/s HBM peak of the data sheet (a float4 copy measures 6.3 TB/s on this part).  Nothing is asserted: the numbers are
-what they are, and whether the batch beats twelve launches is one of them.
+what they are, and whether the batch beats twelve launches is one of them; the mesh pass contains the point pass, so
+`mesh_over_extraction` is the finding there.
 usage: bench_tsdf.py [--reps N] [--warmup N] [--gaussians P] [--out PATH]"""
 import argparse
 import json
@@ -165,7 +171,7 @@ model = {"one_view": touched_single[0] * voxel_bytes + image_bytes,
          "batch_of_twelve": touched_batch * voxel_bytes + V * image_bytes}
 
 ev = {k: [] for k in ("one_view", "twelve_singles", "batch_of_twelve", "torch_ops_one_view", "torch_ops_twelve_views")}
-extraction = []
+extraction, mesh_ms = [], []
 for rep in range(args.warmup + args.reps):
     cur = {"one_view": timed(lambda: vol.integrate_views(frames[:1])),
            "torch_ops_one_view": timed(lambda: ref.integrate(frames[0])),
@@ -173,10 +179,12 @@ for rep in range(args.warmup + args.reps):
            "torch_ops_twelve_views": timed(lambda: [ref.integrate(f) for f in frames]),
            "batch_of_twelve": timed(lambda: vol.integrate_views(frames))}
     ms, cloud = host_timed(vol.surface_points)
+    ms_mesh, mesh = host_timed(vol.get_mesh)
     if rep >= args.warmup:
         for k, pair in cur.items():
             ev[k].append(pair)
         extraction.append(ms)
+        mesh_ms.append(ms_mesh)
 torch.cuda.synchronize()
 
 out = {"what": "TSDF fusion of rendered language maps: fused HIP (one launch per batch of views) against the same update in "
@@ -191,7 +199,17 @@ for k, pairs in ev.items():
         out[k]["model_bytes"] = model[k]
         out[k]["model_TBps"] = round(model[k] / (out[k]["ms_median"] * 1e-3) / 1e12, 3)
         out[k]["share_of_8_TBps"] = round(model[k] / (out[k]["ms_median"] * 1e-3) / HBM_PEAK, 4)
-out["extraction"] = summary(extraction)
+n_points, n_faces = int(cloud[0].shape[0]), int(mesh[1].shape[0])
+assert int(mesh[0].shape[0]) == n_points and torch.equal(mesh[0], cloud[0])
+point_bytes = (3 + F) * 4 + 4 + F * 4
+model.update(extraction=2 * 4 * n_vox + n_points * point_bytes,
+             mesh=3 * 4 * n_vox + n_points * (point_bytes + 3 * 4) + n_faces * 3 * 4)
+for k, ts in (("extraction", extraction), ("mesh", mesh_ms)):   # (host clock: the launches, the host read and the allocations included)
+    out[k] = summary(ts)
+    out[k]["model_bytes"] = model[k]
+    out[k]["model_TBps"] = round(model[k] / (out[k]["ms_median"] * 1e-3) / 1e12, 3)
+out["mesh"].update(vertices=n_points, faces=n_faces)
+out["mesh_over_extraction"] = round(out["mesh"]["ms_median"] / out["extraction"]["ms_median"], 4)
 out["batch_over_twelve_singles"] = round(out["batch_of_twelve"]["ms_median"] / out["twelve_singles"]["ms_median"], 4)
 line = json.dumps(out)
 print(line)
