@@ -1091,7 +1091,7 @@ typedef struct olsr_tsdf_view {
 int olsr_tsdf_init(const olsr_tsdf_volume *volume, void *hip_stream);
 int olsr_tsdf_integrate(const olsr_tsdf_volume *volume, int32_t n_views, const olsr_tsdf_view *views, void *hip_stream);
 size_t olsr_tsdf_surface_scratch_bytes(int32_t X, int32_t Y, int32_t Z);
-int olsr_tsdf_surface_plan(const olsr_tsdf_volume *volume, float min_weight, void *scratch, int32_t *status,
+int olsr_tsdf_surface_plan(const olsr_tsdf_volume *volume, float min_weight, void *scratch, int32_t *status /* [2] = {N, 0} */,
                            void *hip_stream);
 int olsr_tsdf_surface_emit(const olsr_tsdf_volume *volume, float min_weight, const void *scratch, int32_t capacity,
                            float *points, float *feats, int32_t *voxel_index, void *hip_stream);
@@ -1424,6 +1424,19 @@ int olsr_debug_backward_ordered(const olsr_scene *scene, const void *geometry_bu
  * Any other argument only reads the value back.  Same lists bit for bit.  Process-wide; seeded once from OLSR_SORT_THREADS.
  * Returns the value in force. */
 int olsr_debug_sort_threads(int threads);
+
+/* Test hook: the carve log.  While it is on for the calling thread, every sub-array that a sizing function or an entry
+ * carves out of a state or scratch buffer is recorded as (base rounded up to 256 bytes, or 0 for a sizing carve; offset
+ * from that base; bytes).  olsr_debug_carve_log(enable) clears the log and switches it on (!= 0) or off (0);
+ * olsr_debug_carve_log_read copies up to `max` records to `out` (may be NULL) and returns how many the log holds.  Off
+ * (the default) it costs one branch per sub-array and allocates nothing. */
+void olsr_debug_carve_log(int enable);
+int olsr_debug_carve_log_read(uint64_t *out /* [3 * max] */, int max);
+
+/* Test hook, host only: the 32-bit words the carve of the geometry state (binning == 0, n Gaussians) or of the binning state
+ * (binning != 0, n instances) leaves for the status rows of the one-kernel radix passes, behind the tickets, the digit totals
+ * and the look-back words of its synchronisation area.  0 for n < 0. */
+int64_t olsr_debug_sort_status_room(int64_t n, int binning);
 
 /* Test instrument: the composites' exp (csrc/olsr_device.h, pinned_expf and its packed form) against the sequence it replaced
  * (pinned_expf_ref), bit for bit, on the GPU.  For each of the `count` float32 bit patterns from first_bits on (first_bits +

@@ -15,7 +15,7 @@ LIB_PATH = os.environ.get("OLSR_LIB") or os.path.join(_HERE, "libolsr.so")
 EXPORTS = (
     "olsr_geometry_bytes", "olsr_image_bytes", "olsr_binning_bytes", "olsr_backward_scratch_bytes", "olsr_last_forward_token", "olsr_live_rows", "olsr_forward", "olsr_forward_async", "olsr_forward_async_loss", "olsr_fused_loss_scratch_bytes",
     "olsr_backward", "olsr_accumulate_gradients", "olsr_sparse_exchange_mask", "olsr_sparse_exchange_scratch_ints", "olsr_sparse_exchange_pack", "olsr_sparse_exchange_unpack", "olsr_mapping_loss", "olsr_mapping_loss_scratch_bytes", "olsr_tracking_loss", "olsr_refinement_loss", "olsr_refinement_loss_scratch_bytes", "olsr_lang_ae_scratch_bytes", "olsr_lang_ae_train_step", "olsr_lang_ae_encode", "olsr_lang_ae_decode", "olsr_lang_query_scratch_bytes", "olsr_lang_query_sims", "olsr_lang_query_relevancy", "olsr_lang_encoder_encode", "olsr_hr_net_workspace_bytes", "olsr_hr_net_forward", "olsr_tsdf_init", "olsr_tsdf_integrate", "olsr_tsdf_surface_scratch_bytes", "olsr_tsdf_surface_plan", "olsr_tsdf_surface_emit", "olsr_tsdf_mesh_scratch_bytes", "olsr_tsdf_mesh_plan", "olsr_tsdf_mesh_emit", "olsr_emd_scratch_bytes", "olsr_emd_cost", "olsr_chamfer_scratch_bytes", "olsr_chamfer", "olsr_mask_smooth", "olsr_query_eval_scratch_bytes", "olsr_query_eval", "olsr_image_psnr_scratch_bytes", "olsr_image_psnr", "olsr_pose_step", "olsr_pose_step_gated", "olsr_window_pose_step", "olsr_knn_mean_dist2", "olsr_knn_scratch_bytes", "olsr_adam_step", "olsr_adam_step_sum", "olsr_adam_step_masked", "olsr_adam_step_groups", "olsr_adam_step_groups_reg", "olsr_isotropic_reg_scratch_bytes", "olsr_isotropic_reg", "olsr_map_edit_scratch_bytes", "olsr_map_edit_plan", "olsr_map_edit_apply", "olsr_keyframe_seed_scratch_bytes", "olsr_keyframe_seed_plan", "olsr_keyframe_seed_finish", "olsr_frontend_scratch_bytes", "olsr_grad_mask", "olsr_median_depth", "olsr_covisibility", "olsr_keyframe_decide", "olsr_bucket_add", "olsr_mark_visible", "olsr_geometry_field", "olsr_binning_field", "olsr_image_field",
-    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_debug_exp_sweep", "olsr_debug_activate", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
+    "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_debug_exp_sweep", "olsr_debug_activate", "olsr_debug_carve_log", "olsr_debug_carve_log_read", "olsr_debug_sort_status_room", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
 )
 
 _lib = None
@@ -166,6 +166,9 @@ def lib():
     L.olsr_debug_backward_ordered.restype = C.c_int
     L.olsr_debug_exp_sweep.argtypes, L.olsr_debug_exp_sweep.restype = [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint64)], C.c_int
     L.olsr_debug_activate.argtypes, L.olsr_debug_activate.restype = [i32, i32] + [vp] * 3 + [vp] * 3 + [vp], C.c_int
+    L.olsr_debug_carve_log.argtypes, L.olsr_debug_carve_log.restype = [C.c_int], None
+    L.olsr_debug_carve_log_read.argtypes, L.olsr_debug_carve_log_read.restype = [C.POINTER(C.c_uint64), C.c_int], C.c_int
+    L.olsr_debug_sort_status_room.argtypes, L.olsr_debug_sort_status_room.restype = [i64, C.c_int], i64
     L.olsr_last_error.argtypes, L.olsr_last_error.restype = [], C.c_char_p
     L.olsr_version.argtypes, L.olsr_version.restype = [], C.c_char_p
     _lib = L
@@ -213,6 +216,19 @@ def debug_activate(activations, opacities=None, scales=None, rotations=None):
     check(lib().olsr_debug_activate(P, int(activations), p(opacities), p(scales), p(rotations), p(out[0]), p(out[1]), p(out[2]),
                                     C.c_void_p(torch.cuda.current_stream(given[0].device).cuda_stream)))
     return tuple(out)
+
+
+def carve_log(enable):
+    """olsr_debug_carve_log: clear this thread's carve log and switch it on or off."""
+    lib().olsr_debug_carve_log(1 if enable else 0)
+
+
+def carve_log_read():
+    """[(base, offset, bytes)] of every Carver::take since carve_log(True) on this thread (base 0: a sizing carve)."""
+    n = lib().olsr_debug_carve_log_read(None, 0)
+    out = (C.c_uint64 * (3 * max(n, 1)))()
+    n = min(n, lib().olsr_debug_carve_log_read(out, n))
+    return [(int(out[3 * i]), int(out[3 * i + 1]), int(out[3 * i + 2])) for i in range(n)]
 
 
 def set_profiling(enable):

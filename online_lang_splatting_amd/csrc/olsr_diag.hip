@@ -122,6 +122,19 @@ void stamp(hipStream_t st, int kind) {
   stamp_kernel<<<1, 1, 0, st>>>(g_stamps.buf + 2 * (size_t)i, ((unsigned long long)(uintptr_t)st << 8) | (unsigned)kind);
 }
 
+// The carve log (olsr_state.h): per thread, three words per Carver::take
+thread_local bool g_carve_log_on = false;
+namespace {
+thread_local std::vector<uint64_t> g_carve_log;
+constexpr size_t CARVE_LOG_MAX_WORDS = 3u << 16;
+}  // namespace
+void carve_log_append(const void* base, size_t offset, size_t bytes) {
+  if (g_carve_log.size() >= CARVE_LOG_MAX_WORDS) return;
+  g_carve_log.push_back((uint64_t)(uintptr_t)base);
+  g_carve_log.push_back((uint64_t)offset);
+  g_carve_log.push_back((uint64_t)bytes);
+}
+
 // The radix passes' knobs (olsr_state.h): seeded from the environment once, when the library is loaded
 SortKnobs& sort_knobs() {
   static SortKnobs k;
@@ -213,6 +226,31 @@ int olsr_get_stage_times(const char** names, float* ms, int max) {
     ++n;
   }
   return n;
+}
+
+void olsr_debug_carve_log(int enable) {
+  g_carve_log_on = enable != 0;
+  g_carve_log.clear();
+  if (!g_carve_log_on) g_carve_log.shrink_to_fit();
+}
+
+int olsr_debug_carve_log_read(uint64_t* out, int max) {
+  const int n = (int)(g_carve_log.size() / 3);
+  for (int i = 0; out && i < n && i < max; ++i)
+    for (int k = 0; k < 3; ++k) out[3 * i + k] = g_carve_log[3 * (size_t)i + k];
+  return n;
+}
+
+int64_t olsr_debug_sort_status_room(int64_t n, int binning) {
+  if (n < 0) return 0;
+  // (a base that is never dereferenced: the carve only adds offsets to it)
+  void* base = reinterpret_cast<void*>((uintptr_t)ALIGN);
+  if (binning) {
+    const BinningState b = BinningState::carve(base, (size_t)n);
+    return (int64_t)((b.sync_words + b.sync_count) - b.tile_status);
+  }
+  const GeometryState g = GeometryState::carve(base, (size_t)n, grad_row(0));
+  return (int64_t)((g.sync_words + g.sync_count) - g.sort_status);
 }
 
 void olsr_debug_sort_timing(unsigned long long* device_buffer, int max_blocks, int max_launches) {

@@ -137,6 +137,12 @@ __host__ __device__ inline unsigned long long emit_total_pack(uint32_t instances
 #endif
 constexpr int ROWS_CHUNK = 16 * OLSR_ROWS_THREADS;
 
+// The carve log (olsr_debug_carve_log, olsr_diag.hip): while it is on for the calling thread every Carver::take records
+// (aligned base or null, offset, bytes), so that a test can tell the sub-arrays of a carved buffer from the gaps between
+// them.  Off, it costs take() one branch on a thread-local flag; nothing is allocated unless it is on.
+extern thread_local bool g_carve_log_on;
+void carve_log_append(const void* base, size_t offset, size_t bytes);
+
 struct Carver {
   char* base;
   size_t off = 0;
@@ -146,6 +152,7 @@ struct Carver {
   T* take(size_t count) {
     off = align_up(off);
     T* p = base ? (T*)(base + off) : nullptr;
+    if (__builtin_expect(g_carve_log_on, 0)) carve_log_append(base, off, count * sizeof(T));
     off += count * sizeof(T);
     return p;
   }

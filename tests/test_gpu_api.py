@@ -12,6 +12,7 @@ from parity_common import fwd_args, rel_err, run_backend
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
+ACCUMULATE_TOL = 1e-6   # rtol = atol of the fused accumulate against GradientBucket's torch formulation
 
 
 def _settings(sc, dev):
@@ -561,8 +562,8 @@ def test_fused_accumulate_matches_torch_formulation(hip):
     for _ in range(3):
         ref.accumulate(grads, radii)
         got.accumulate({k: v.to(dev) for k, v in grads.items()}, radii.to(dev))
-    torch.testing.assert_close(got.flat.cpu(), ref.flat, rtol=1e-6, atol=1e-6)
-    torch.testing.assert_close(got.densify.cpu(), ref.densify, rtol=1e-6, atol=1e-6)
+    torch.testing.assert_close(got.flat.cpu(), ref.flat, rtol=ACCUMULATE_TOL, atol=ACCUMULATE_TOL)
+    torch.testing.assert_close(got.densify.cpu(), ref.densify, rtol=ACCUMULATE_TOL, atol=ACCUMULATE_TOL)
     assert torch.equal(got.max_radii.cpu(), ref.max_radii)
 
 

@@ -29,6 +29,11 @@ NAMES = sorted(CASES)
 ULP = 2.0 ** -24
 
 
+def mean_bound(n, want):
+    """A Chamfer mean over n points: per-tile partial sums of 256 in double, added in tile order."""
+    return (n / 256 + 32) * 2.0 ** -53 * want
+
+
 def _M():
     from online_lang_splatting_amd import cloud_metrics
     return cloud_metrics
@@ -313,7 +318,7 @@ def test_chamfer_points_equal_the_float32_brute_force(name):
     # numpy's pairwise sum at most 128 terms and then its tree: relative bounds (n / 256 + 8) and under 24 units of 2^-53
     got = mean.cpu().numpy()[0]
     for k, (key, n) in enumerate((("x_to_y", len(x)), ("y_to_x", len(y)))):
-        assert abs(got[k] - want[key]) <= (n / 256 + 32) * 2.0 ** -53 * want[key], (key, got[k], want[key])
+        assert abs(got[k] - want[key]) <= mean_bound(n, want[key]), (key, got[k], want[key])
 
 
 @pytest.mark.parametrize("name", NAMES)

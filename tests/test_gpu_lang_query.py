@@ -68,6 +68,12 @@ def _check(label, case, decode_hw=None, out_hw=None, truth=None):
     out = q.relevancy(case["codes"].to(DEV), out_hw=out_hw, decode_hw=decode_hw)
     torch.cuda.synchronize()
     hip = {k: v.cpu().clone() for k, v in out.items()}
+    _check_outputs(label, case, hip, t64, t32)
+    return q, hip
+
+
+def _check_outputs(label, case, hip, t64, t32):
+    """hip: the outputs of one query (relevancy()'s dict, on the CPU) against the reference's statements."""
     P, H, W = hip["relevancy"].shape
     assert tuple(hip["similarities"].shape) == tuple(t64["sims_dec"].shape)
     _ratio_rule(f"{label} similarities", hip["similarities"], t64["sims_dec"], t32["sims_dec"])
@@ -100,7 +106,6 @@ def _check(label, case, decode_hw=None, out_hw=None, truth=None):
                         _tolerance(t64["sims"], t32["sims"]), H * W)
     else:
         assert "labels" not in hip
-    return q, hip
 
 
 def _golden_case(key):

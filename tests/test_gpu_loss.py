@@ -16,6 +16,9 @@ from test_loss_oracle_golden import golden_cases, golden_tracking_cases, run_ora
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
 RTOL = 1e-5
+EXPOSURE_ATOL = 2e-6        # the exposure gradient against the oracle: sums of +-1 with heavy cancellation
+FUSED_EXPOSURE_ATOL = 1e-6  # the fused loss against the two-kernel path: another summation order
+LANG_FLIPS = 3              # language cotangents whose sign a bilinear sample within rounding of the rendered value may flip
 
 
 def _close(a, b, name, atol_scale=1.0):
@@ -81,9 +84,9 @@ def test_against_the_oracle(hip, F, H, W, lh, lw):
         # a bilinear sample that lands within rounding of the rendered value flips a sign: allow a handful
         d = (o["dL_dlanguage"].cpu() - ref["dL_dlanguage"]).abs()
         bad = int((d > RTOL * float(ref["dL_dlanguage"].abs().max())).sum())
-        assert bad <= 3, bad
-    assert abs(float(o["dL_dexposure"][0]) - float(ref["dL_da"])) <= 2e-6
-    assert abs(float(o["dL_dexposure"][1]) - float(ref["dL_db"])) <= 2e-6
+        assert bad <= LANG_FLIPS, bad
+    assert abs(float(o["dL_dexposure"][0]) - float(ref["dL_da"])) <= EXPOSURE_ATOL
+    assert abs(float(o["dL_dexposure"][1]) - float(ref["dL_db"])) <= EXPOSURE_ATOL
     # without a language target the language cotangent is zero-filled; initialization skips the exposure
     c2 = dict(c, gt_lang=None)
     o2 = _run_hip(c2, losses, initialization=True, **kw)
@@ -159,7 +162,7 @@ def test_tracking_loss_golden_and_oracle(hip):
     _close(o["loss"][0], ref["loss"], "loss")
     _close(o["dL_dimage"], ref["dL_dimage"], "dL_dimage")
     _close(o["dL_ddepth"], ref["dL_ddepth"], "dL_ddepth")
-    assert abs(float(o["dL_dexposure"][0]) - float(ref["dL_da"])) <= 2e-6
+    assert abs(float(o["dL_dexposure"][0]) - float(ref["dL_da"])) <= EXPOSURE_ATOL
 
 
 def test_mapping_iterations_reduce_the_loss(hip):
@@ -273,7 +276,7 @@ def test_fused_mapping_loss_equals_the_two_kernel_path(hip, F, W, H, tile, lang_
             assert fu["dL_dlanguage"] is None
         _close(fu["loss"], two["loss"], "loss")
         assert float(two["loss"][0]) > 0 and (F == 0 or float(two["loss"][3]) > 0)
-        assert float((fu["dL_dexposure"] - two["dL_dexposure"]).abs().max()) <= 1e-6
+        assert float((fu["dL_dexposure"] - two["dL_dexposure"]).abs().max()) <= FUSED_EXPOSURE_ATOL
         gf = ws.backward(fu["dL_dimage"], fu["dL_dlanguage"], fu["dL_ddepth"])
         for k in g2:
             assert torch.equal(gf[k], g2[k]), k
@@ -292,7 +295,7 @@ def test_fused_tracking_loss_equals_the_two_kernel_path(hip, F, W, H, tile, mask
     assert fu["dL_dlanguage"] is None
     assert torch.equal(fu["dL_dimage"], two["dL_dimage"]) and torch.equal(fu["dL_ddepth"], two["dL_ddepth"])
     _close(fu["loss"], two["loss"], "loss")
-    assert float((fu["dL_dexposure"] - two["dL_dexposure"]).abs().max()) <= 1e-6
+    assert float((fu["dL_dexposure"] - two["dL_dexposure"]).abs().max()) <= FUSED_EXPOSURE_ATOL
     gf = ws.backward(fu["dL_dimage"], None, fu["dL_ddepth"], pose_only=True)["dL_dtau_sum"]
     assert torch.equal(gf, g2) and float(g2.abs().max()) > 0
 
