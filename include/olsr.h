@@ -233,6 +233,15 @@ size_t olsr_binning_bytes(int64_t num_rendered, int32_t F);
  * binning).  Outputs: out_color[3,H,W], out_language[F,H,W] (ignored when F == 0),
  * out_depth[H,W], out_opacity[H,W], radii[P] (int32), n_touched[P] (int32).
  * *num_rendered receives R, the number of (Gaussian, tile) instances. */
+/* Non-finite Gaussians ("Non-finite inputs"; tests/test_gpu_nonfinite.py).  No input value can make a
+ * kernel index out of bounds: every float that becomes a tile, a row or a count is converted saturating (NaN -> 0) and
+ * clamped.  A Gaussian whose mean, scale, rotation or covariance is NaN or overflows to a NaN eigenvalue has radius 0 and
+ * holds NO instance (the reference counts one uninitialised list slot for it: undefined there, culled here); radii[] is 0
+ * for it.  A radius saturates at 2^31 - 1.  An opacity <= 0 is listed and never blended; a NaN opacity blends alpha = 0.99
+ * wherever power <= 0, as in the reference.  A non-finite colour or language value makes exactly the pixels that blend it
+ * non-finite.  A NaN conic (the covariance of a scale of 1e10 or more has overflowed) blends alpha = 0.99 in every pixel
+ * of its rect, the reference's min(0.99f, opacity * exp(NaN)).  The outputs
+ * are the reference's, bit for bit, NaN where it has NaN. */
 /* Process-wide state olsr_forward keeps (results never depend on it; tested): per (device, stream, tile count) the
  * heaviest-first tile orders of up to 16 VIEWS the stream has rendered (launch-order hints: a one-wave kernel in front of the
  * composite picks the stored view matrix nearest to this frame's, else recycles the least recently used slot — the
@@ -360,6 +369,12 @@ int32_t olsr_live_rows_overwritten(int32_t token);
 /* The last step of the drop-in olsr_backward's choice of rows (scratch_alloc != NULL), when it does not guess: the posted
  * count of (token, R instances, F), waited for when the bound would cost more than 64 MB, else the bound. */
 int64_t olsr_backward_rows(int32_t token, int32_t packed_survivor_waves, int64_t num_rendered, int32_t F);
+/* Non-finite Gaussians in the backward ("Non-finite inputs").  A culled Gaussian (radius 0) has zero
+ * gradients.  A row the reference has finite stays finite and within the usual tolerance; a row it has NaN or infinite is NaN
+ * or infinite element by element (OLSR_BWD_EXACT) — with two deviations, both towards "assumes finite values": (1) a
+ * Gaussian no pixel blended skips the per-Gaussian chain and gets exact zeros where the reference multiplies a zero by its NaN
+ * covariance; (2) in OLSR_BWD_REFERENCE the skipped recursion-only visits leave some rows finite that the reference has NaN.
+ * A caller that must not step on NaNs masks non-finite rows itself. */
 int olsr_backward(const olsr_scene *scene, const int32_t *radii,
                   void *geometry_buffer, int32_t num_rendered,
                   void *binning_buffer, const void *image_buffer,

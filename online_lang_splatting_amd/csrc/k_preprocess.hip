@@ -229,6 +229,9 @@ __device__ __forceinline__ u32 preprocess_one(
     if (act & (OLSR_FLAG_SIGNED_EMPTY_RADII << 16)) radii[idx] = -irad;
     return 0;
   }
+  // a radius that is not positive (a NaN eigenvalue; a finite covariance gives at least 2) holds no instance: the
+  // reference counts its one tile but writes no key for it, an uninitialised list slot
+  if (!(irad > 0)) return 0;
 
   if (colors_precomp == nullptr) {
     const f3 c = color_from_sh(idx, D, M, p_orig, cam_pos, shs, clamped);
@@ -241,7 +244,14 @@ __device__ __forceinline__ u32 preprocess_one(
   radii[idx] = irad;
   means2D[2 * (size_t)idx + 0] = pix_x;
   means2D[2 * (size_t)idx + 1] = pix_y;
-  float4 co = make_float4(conic.x, conic.y, conic.z, opacity);
+  float4 co = make_float4((conic.x == 0.0f) ? 0.0f : conic.x, conic.y, conic.z, opacity);  // (a zero a is +0: -0 is the mark)
+  // A NaN conic (the covariance has overflowed: radius saturated, det inf - inf) makes `power` NaN in every pixel, and the
+  // reference then blends alpha = min(0.99f, opacity * exp(NaN)) = 0.99 whatever the opacity is.  pinned_expf's clamp would
+  // turn the NaN into exp(-87) instead, so the composites get a record that takes the reference's decisions through their
+  // existing instructions: conic (-0, 0, 0) gives power = -0 (not > 0), exp = 1, and opacity 1 gives alpha = 0.99.  The
+  // -0 in `a` marks the record: the per-Gaussian backward turns the gradients the reference has NaN (through G = NaN) into
+  // NaN (conic_record_is_nan, olsr_device.h).  The binning below keeps the NaN conic: full rect, as before.
+  if (conic.x != conic.x || conic.y != conic.y || conic.z != conic.z) co = make_float4(-0.0f, 0.0f, 0.0f, 1.0f);
   reinterpret_cast<float4*>(conic_opacity)[idx] = co;
 
   u32 count = area;

@@ -528,7 +528,8 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     float* __restrict__ dL_dtau, float* __restrict__ tau_partials, float* __restrict__ bucket_flat,
     float* __restrict__ bucket_densify, int32_t* __restrict__ bucket_max_radii, int bucket_assign, int act,
     const float* __restrict__ opacities_raw, int F_out, u64* __restrict__ bucket_row_mask, float* gacc_park,
-    u32* __restrict__ act_list, u32* __restrict__ act_count, const uint8_t* __restrict__ blended, int rows_stamp) {
+    u32* __restrict__ act_list, u32* __restrict__ act_count, const uint8_t* __restrict__ blended, int rows_stamp,
+    const float* __restrict__ conic_opacity) {
   // F: language channels of the partial-gradient rows; F_out: the scene's (width of dL_dlanguage and of the bucket's
   // language columns).  F == 0 < F_out: the backward ran without a language cotangent, those gradients are zero.
   constexpr int ROW = grad_row(F);
@@ -571,6 +572,13 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
       const u32 first = rowbase[u0], nrows = rowbase[u0 + ntiles_g] - first;
       for (u32 t = 0; t < nrows; ++t) add_row<F, NVAL>(rows, first + t, acc);
       has_rows = nrows > 0;
+    }
+    // A Gaussian with a NaN conic was composited through preprocess's stand-in record (exp = 1, alpha = 0.99).  In the reference
+    // its G is exp(NaN): every visit that does not skip adds a NaN to dL_dmean2D, dL_dconic and dL_dopacity (and nothing else).
+    // Looked up for Gaussians with rows only.
+    if (has_rows && conic_record_is_nan(conic_opacity[4 * (size_t)idx])) {
+#pragma unroll
+      for (int v = 0; v < 6; ++v) acc[v] = __builtin_nanf("");
     }
     // bucket row of this Gaussian, staged in LDS: a lane's 116-byte row would be 29 scattered 4-byte stores,
     // the block's rows together are one contiguous span that is written (or added) coalesced at the end
@@ -975,7 +983,8 @@ static void launch_pb_t(const olsr_scene& s, const FrameDims& d, const GeometryS
     int32_t* total = &g.counters[CNT_EMITTERS];
     preprocess_bwd_kernel<F, true><<<nb, PB_THREADS, bucket_lds, st>>>(
         OLSR_PB_ARGS, nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii, o.bucket_assign, s.activations,
-        s.opacities, F_out, o.bucket_row_mask, g.gacc, act_list, act_count, g.blended, rows_stamp_of(s.backward_row_capacity));
+        s.opacities, F_out, o.bucket_row_mask, g.gacc, act_list, act_count, g.blended, rows_stamp_of(s.backward_row_capacity),
+        g.conic_opacity);
     pb_compact_kernel<<<1, PC_THREADS, 0, st>>>(nb, act_count, act_list, compact, total);
     n_partials = std::min(nb, 256);
     pb_chain_kernel<<<n_partials, CH_THREADS, 0, st>>>(
@@ -988,7 +997,7 @@ static void launch_pb_t(const olsr_scene& s, const FrameDims& d, const GeometryS
   preprocess_bwd_kernel<F, false><<<nb, PB_THREADS, bucket_lds, st>>>(
       OLSR_PB_ARGS, o.dL_dtau_sum ? tau_partials : nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii,
       o.bucket_assign, s.activations, s.opacities, F_out, o.bucket_row_mask, nullptr, nullptr, nullptr, g.blended,
-      rows_stamp_of(s.backward_row_capacity));
+      rows_stamp_of(s.backward_row_capacity), g.conic_opacity);
 #endif
 #undef OLSR_PB_ARGS
   if (o.dL_dtau_sum)

@@ -421,8 +421,8 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
           A_f = last_alpha * D_last + (1.f - last_alpha) * A_f;
           D_last = D_cur;
         }
-        // Everything a skipping pixel must not do hangs off two masked factors: alpha_eff = 0 leaves Z unchanged and
-        // zeroes alpha * T, inv_eff = 1 leaves T unchanged.  Colour and depth run on packed fp32 pairs — an
+        // Everything a skipping pixel must not do hangs off two masked factors and one select: alpha_eff = 0 zeroes
+        // alpha * T, inv_eff = 1 leaves T unchanged, Z is selected.  Colour and depth run on packed fp32 pairs — an
         // instruction holds the SIMD's issue for one quad-cycle whether it is packed or not.
         const float one_m_alpha = 1.f - alpha;  // in [0.01, 1] for every pixel that does not skip
         float inv = __builtin_amdgcn_rcpf(one_m_alpha);
@@ -434,9 +434,12 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         const bv2 d01 = bv2{f4.x, f4.y} - Z01, d23 = bv2{f4.z, f4.w} - Z23;
         const bv2 dd = d01 * dL01 + d23 * dL23;
         float dL_dalpha = dd.x + dd.y;
-        const bv2 a2 = {alpha_eff, alpha_eff};
-        Z01 = Z01 + a2 * d01;
-        Z23 = Z23 + a2 * d23;
+        // (a select, not alpha_eff * d: a skipping pixel must keep Z also when the splat's colour is infinite or NaN —
+        //  0 * inf would hand a NaN to every Gaussian in front of it in this pixel, which the reference's guarded update does not)
+        const bv2 a2 = {alpha, alpha};
+        const bv2 Zn01 = Z01 + a2 * d01, Zn23 = Z23 + a2 * d23;
+        Z01 = bv2{skip ? Z01.x : Zn01.x, skip ? Z01.y : Zn01.y};
+        Z23 = bv2{skip ? Z23.x : Zn23.x, skip ? Z23.y : Zn23.y};
         if constexpr (F > 0) {
           if constexpr (!REF) {  // guarded like colour
             const float A_new = last_alpha * D_last + (1.f - last_alpha) * A_f;

@@ -91,9 +91,11 @@ __global__ __launch_bounds__(256) void render_bwd_ordered_kernel(
     const float dx = xyx - pixfx, dy = xyy - pixfy;
     const float power = -0.5f * (co0 * dx * dx + co2 * dy * dy) - co1 * dx * dy;
     skip |= power > 0.0f;
-    const float G = pinned_expf(power);
-    const float alpha = fminf_ref(0.99f, co3 * G);
+    const float G1 = pinned_expf(power);
+    const float alpha = fminf_ref(0.99f, co3 * G1);
     skip |= alpha < 1.0f / 255.0f;
+    // the record of a NaN conic (k_preprocess.hip) decides like the reference; its G is the reference's exp(NaN)
+    const float G = conic_record_is_nan(co0) ? __builtin_nanf("") : G1;
     // (idle threads of the block vote "skip" too: the count is compared with the 256 of the launch)
     if (__syncthreads_count(skip ? 1 : 0) == (int)blockDim.x) continue;  // :1091-1093
     const float depth = depths[gid];

@@ -185,6 +185,8 @@ __device__ __forceinline__ float lane_read(float v, int lane) {
 // max(x, -87) as ONE v_max_f32.  __builtin_fmaxf costs two: the compiler puts a canonicalising v_max_f32 x, x in front, because
 // maxNum must quiet a signalling NaN operand and it cannot see that x is an arithmetic result; the instruction itself, in the
 // IEEE mode kernels run in, returns the other operand for any NaN.  Same bits for every input that is not a signalling NaN.
+// So exp(NaN) = exp(-87) here where the reference's exp(NaN) is NaN.  No composite meets a NaN `power`: it comes from a NaN
+// conic, for which preprocess stores a record that takes the reference's decisions (k_preprocess.hip, conic_record_is_nan).
 __device__ __forceinline__ float max_m87(float x) {
   float r;
   asm("v_max_f32 %0, 0xc2ae0000, %1" : "=v"(r) : "v"(x));
@@ -291,6 +293,9 @@ __device__ __forceinline__ int f2i_sat(float v) {
 __device__ __forceinline__ float fminf_ref(float a, float b) { return (b < a) ? b : a; }  // std::min(a,b)
 __device__ __forceinline__ float fmaxf_ref(float a, float b) { return (a < b) ? b : a; }  // std::max(a,b)
 
+// preprocess stores conic (-0, 0, 0), opacity 1 for a Gaussian whose conic is NaN (k_preprocess.hip); a real `a` is never -0
+__device__ __forceinline__ bool conic_record_is_nan(float a) { return f2bits(a) == 0x80000000u; }
+
 // ---- geometry helpers (CR/auxiliary.h:41-97) ---------------------------------------------
 __device__ __forceinline__ float ndc2Pix(float v, int S) { return (float)((((double)v + 1.0) * (double)S - 1.0) * 0.5); }
 
@@ -326,8 +331,9 @@ __device__ __forceinline__ Rect get_rect(float px, float py, int max_radius, int
 // and two sums of the composite's `power` at distances up to D = radius + TILE + 1.  Negative:
 // no pixel can pass.
 __device__ __forceinline__ float cull_threshold(float a, float b, float c, float opacity, int radius, int tile) {
-  // not-a-number anywhere: the composite's comparisons then all fail and it blends alpha = 0.99 (fminf_ref): keep
-  // every tile of the rect (3e38 makes cull_setup fall back to the full spans)
+  // not-a-number anywhere: no bound holds, keep every tile of the rect (3e38 makes cull_setup fall back to the full spans).
+  // A NaN opacity blends alpha = 0.99 wherever power <= 0 (fminf_ref(0.99f, NaN)); a NaN conic blends 0.99 in every pixel of
+  // the rect (the reference's min(0.99f, opacity * exp(NaN)); preprocess stores the record that does so, k_preprocess.hip).
   if (a != a || b != b || c != c || opacity != opacity) return 3e38f;
   const float o255 = 255.0f * opacity;
   if (!(o255 > 0.0f)) return -1.0f;

@@ -91,6 +91,15 @@ const float SH_C2[] = {1.0925484305920792f, -1.0925484305920792f, 0.315391565252
 const float SH_C3[] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                        -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
+// float -> int conversion with the GPU's saturating semantics (cvt.rzi.s32.f32 on the
+// reference's hardware, v_cvt_i32_f32 on gfx950): truncate toward zero, clamp, NaN -> 0.
+static inline int f2i_sat(float v) {
+  if (v != v) return 0;
+  if (v >= 2147483648.0f) return 2147483647;
+  if (v <= -2147483648.0f) return (int)0x80000000;
+  return (int)v;
+}
+
 // The pinned exp (see header).  Valid for x <= 88; x is clamped below at -87 (the result,
 // ~1.6e-38, times any opacity <= 1 is far under the 1/255 alpha floor).
 static inline float bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
@@ -112,17 +121,10 @@ static float oracle_expf(float x) {
   p = __builtin_fmaf(p, r, 1.6666665459e-1f);
   p = __builtin_fmaf(p, r, 5.0000001201e-1f);
   float e = __builtin_fmaf(p, r * r, r) + 1.0f;
-  int ni = (int)n;
+  // (n is NaN for a NaN argument: `(int)n` would be undefined.  f2i_sat is the device's v_cvt_i32_f32, 0 for a NaN, and
+  //  e * 2^0 is still NaN; for every other argument n is an integer in [-126, 127] and the conversion is exact)
+  int ni = f2i_sat(n);
   return e * bits2f((uint32_t)(ni + 127) << 23);
-}
-
-// float -> int conversion with the GPU's saturating semantics (cvt.rzi.s32.f32 on the
-// reference's hardware, v_cvt_i32_f32 on gfx950): truncate toward zero, clamp, NaN -> 0.
-static inline int f2i_sat(float v) {
-  if (v != v) return 0;
-  if (v >= 2147483648.0f) return 2147483647;
-  if (v <= -2147483648.0f) return (int)0x80000000;
-  return (int)v;
 }
 
 // CR/auxiliary.h:41-44 — evaluated in double (the literals are double), then narrowed.
@@ -292,6 +294,11 @@ static void preprocess(const olsr_scene& s, State& st, int* radii_out) {
       if (s.flags & OLSR_FLAG_SIGNED_EMPTY_RADII) radii_out[idx] = -f2i_sat(my_radius);
       continue;
     }
+    // A radius that is not positive (reachable only through a NaN eigenvalue: a finite covariance gives at least
+    // ceil(3 sqrt(0.3)) = 2) holds no instance.  The reference counts the tiles of its radius-0 square all the same, but
+    // duplicateWithKeys (`if (radii[idx] > 0)`) writes no key for it: the slot it counted stays uninitialised memory
+    // there, i.e. undefined.  Defined here as culled ("Non-finite inputs").
+    if (!(f2i_sat(my_radius) > 0)) continue;
     if (s.colors_precomp == nullptr) {
       f3 c = computeColorFromSH(idx, s.D, s.M, s.means3D, s.cam_pos, s.shs, st.clamped.data());
       st.rgb[3 * (size_t)idx + 0] = c.x;

@@ -15,6 +15,7 @@ Shapes straddle the kernels' block quanta; each row of the table names the quant
 | entry | shapes | quanta (source) | scratch |
 |---|---|---|---|
 | olsr_forward + olsr_backward | P 1..8193 on 45x30; 157x101, 15x15, 16x16 at P 257; F 0/3/15/16/32 at P 1025; all culled; screen-filling x 300; every one with both binnings, both tiles and both modes | preprocess 256 Gaussians / block (part_* sums), one-launch depth sort <= 8192, EMIT_CHUNK 1024, tau_partials 128, wave 64 | three state buffers: Carver (log); row scratch: by hand in olsr_api.hip (outer guards only), served by the callback, and caller-provided with exactly olsr_backward_scratch_bytes(rows) for rows = olsr_live_rows and for the 2 / 4 rows per instance bound |
+| olsr_forward + olsr_backward, non-finite rows | the mixture scene of tests/nonfinite_scenes.py at P 257: 45x30 with 15 language channels (tile 15), 64x48 with none (tile 16); both binnings and modes, misaligned as well | as above; radii 0, 2^20 - 1, 2^20 and 2^31 - 1, NaN and infinite means, depths and conics | as above |
 | forced sort paths | P 1025, both tiles and modes | legacy passes, kpt 2/4/8/12/16 x 256/1024 threads, one-launch sort off, compaction off | as above |
 | olsr_forward_async | binning sized for R, R + 1, R - 1 (overflow) | carve by capacity | state: Carver |
 | olsr_debug_backward_ordered | P 257 | one row per instance | by hand in olsr_diag.hip (outer guards only) |
@@ -281,6 +282,28 @@ def test_forward_backward_over_the_block_quanta(hip, oracle_runs, P, tile):
     sc = make_scene(P, 45, 30, 15, seed=100 + P)
     for mode in MODES:
         _raster_case(oracle_runs, f"P{P}", sc, 3, tile, mode, misaligned=(P == 257))
+
+
+@pytest.mark.parametrize("tile", [15, 16])
+def test_forward_backward_non_finite_gaussians(hip, oracle, tile):
+    """The mixture scene of tests/nonfinite_scenes.py (NaN, infinite, overflowing and saturating rows among ordinary ones) at
+    P = 257: a saturated radius or a NaN that escaped a clamp on its way to an index shows here as a changed guard byte or a
+    touched carve gap.  The forward is the oracle's by bits (NaN where it has NaN); tests/test_gpu_nonfinite.py holds the rest."""
+    import nonfinite_scenes as NF
+    from parity_common import same_bits
+    p = NF.planted_scene("mix_all", 257, 45 if tile == 15 else 64, 30 if tile == 15 else 48, 15 if tile == 15 else 0, seed=11)
+    want = NF.oracle_forward(p.scene, tile)
+    assert int((want["radii"][p.idx] == (1 << 31) - 1).sum()) > 0 and int((want["radii"][p.idx] == 0).sum()) > 0
+    for mode in MODES:
+        for binning in (_abi.BINNING_RECT, _abi.BINNING_ELLIPSE):
+            out = three_ways(lambda c: raster(c, p.scene, tile, mode, binning, 3), misaligned=True)
+            name = f"tile {tile} mode {mode} binning {binning}"
+            assert int(out["R"]) == want["R"] if binning == _abi.BINNING_RECT else int(out["R"]) <= want["R"], name
+            assert torch.equal(out["radii"].cpu(), want["radii"]) and torch.equal(out["n_touched"].cpu(), want["n_touched"]), name
+            for k in ("color", "language", "depth", "opacity"):
+                if want[k] is not None and want[k].numel():
+                    assert same_bits(out[k], want[k]), f"{name}: forward {k}"
+            assert int(out["status"][1]) == 0, name
 
 
 @pytest.mark.parametrize("W,Hh,tile", [(157, 101, 15), (157, 101, 16), (15, 15, 15), (16, 16, 16), (16, 16, 15), (15, 15, 16)])
