@@ -31,10 +31,6 @@ namespace olsr {
 #ifndef OLSR_PB_THREADS
 #define OLSR_PB_THREADS 128
 #endif
-#ifndef OLSR_PB_SPLIT
-#define OLSR_PB_SPLIT 0  // 1: row sums for every Gaussian, the chain only for those with rows (three kernels: built and measured
-                         // late in round 4 - same headline, the isolated stage 63 -> 84 us; profiles/r4_experiments.json); 0: one kernel
-#endif
 constexpr int PB_THREADS = OLSR_PB_THREADS;
 int tau_partial_blocks(int P) { return (P + PB_THREADS - 1) / PB_THREADS; }
 
@@ -308,8 +304,8 @@ __device__ __forceinline__ void cov3d_backward(const float* scale, float mod, co
 // conic.w, (opacity), colour r g b, depth} to dL_dmean3D, dL_dcov3D, dL_dscale, dL_drotation, the SH rows and the pose
 // (computeCov2DCUDA, preprocessCUDA / language_preprocessCUDA, computeCov3D, computeColorFromSH backward: CR/backward.cu:21-145,
 // 150-346, 350-413, 418-682).  dmean / dcov / dscale / drot must come in zeroed; tau is accumulated into; sh_row is the
-// Gaussian's row of 3 M SH gradients (NULL: not wanted), written or — sh_add — added to.  Used by the one-kernel form and by
-// the compacted chain kernel below.
+// Gaussian's row of 3 M SH gradients (NULL: not wanted), written or — sh_add — added to.  Used by
+// preprocess_bwd_kernel and by pb_chain_kernel below.
 template <int N>
 __device__ __forceinline__ void pb_chain(u32 idx, const float (&acc)[N], int D, int M, const float* __restrict__ means3D,
                                          const float* __restrict__ shs, const uint8_t* __restrict__ clamped,
@@ -505,15 +501,7 @@ __device__ __forceinline__ void pb_chain(u32 idx, const float (&acc)[N], int D, 
   
 }
 
-// SPLIT (OLSR_PB_SPLIT=1, an experiment that is OFF: see the macro): the chain does not run here.  Saturation leaves ~2 % of a view's Gaussians with a
-// partial-gradient row (config 3: 9 471 of 500 000) and every other Gaussian's chain is a product with zeros, yet in index
-// order nearly every wave holds one of the 2 % and issued the chain's ~800 instructions for all 64 lanes.  With SPLIT this
-// kernel sums the rows, writes the composite-level gradients, the statistics, the bucket's opacity / language columns and zeros
-// everywhere else, parks the ten sums of a Gaussian WITH rows in its gacc row and lists it (per block, ascending);
-// pb_compact_kernel concatenates the blocks' lists and pb_chain_kernel runs the chain for the listed Gaussians only, a lane
-// each, overwriting (or adding to) what this kernel left.  Same operations on the same values: the results are the one-kernel
-// form's, bit for bit, up to the sign of zeros; dL_dtau's device-side sum is taken over the listed Gaussians in ascending order.
-template <int F, bool SPLIT>
+template <int F>
 __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     int P, int D, int M, const float* __restrict__ gacc, const u32* __restrict__ tiles_touched,
     const u32* __restrict__ inst_start, const u32* __restrict__ rowbase, const float* __restrict__ rows,
@@ -527,9 +515,8 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     float* __restrict__ dL_dsh, float* __restrict__ dL_dscales, float* __restrict__ dL_drotations,
     float* __restrict__ dL_dtau, float* __restrict__ tau_partials, float* __restrict__ bucket_flat,
     float* __restrict__ bucket_densify, int32_t* __restrict__ bucket_max_radii, int bucket_assign, int act,
-    const float* __restrict__ opacities_raw, int F_out, u64* __restrict__ bucket_row_mask, float* gacc_park,
-    u32* __restrict__ act_list, u32* __restrict__ act_count, const uint8_t* __restrict__ blended, int rows_stamp,
-    const float* __restrict__ conic_opacity) {
+    const float* __restrict__ opacities_raw, int F_out, u64* __restrict__ bucket_row_mask,
+    const uint8_t* __restrict__ blended, int rows_stamp, const float* __restrict__ conic_opacity) {
   // F: language channels of the partial-gradient rows; F_out: the scene's (width of dL_dlanguage and of the bucket's
   // language columns).  F == 0 < F_out: the backward ran without a language cotangent, those gradients are zero.
   constexpr int ROW = grad_row(F);
@@ -650,14 +637,7 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     // finite parameters), which is what the defaults above and the zero fill of dL_dsh below leave.  Saturation leaves 98 % of
     // a view's visible Gaussians without a row (config 3), so a wave whose 64 Gaussians are all such skips the chain's ~800
     // instructions (three waves in ten do; the branch is uniform for them, the other lanes ride along as before).
-    if constexpr (SPLIT) {
-      if (vis && has_rows) {  // park the sums for pb_chain_kernel (a large footprint's row already holds them: same values)
-        float4* park = reinterpret_cast<float4*>(gacc_park + (size_t)idx * ROW);
-        park[0] = make_float4(acc[0], acc[1], acc[2], acc[3]);
-        park[1] = make_float4(acc[4], acc[5], acc[6], acc[7]);
-        park[2] = make_float4(acc[8], acc[9], 0.f, 0.f);
-      }
-    } else if (vis && has_rows) {
+    if (vis && has_rows) {
       float* sh_row = dL_dsh ? dL_dsh + (size_t)idx * M * 3 : (brow ? brow + 3 : nullptr);
       pb_chain(idx, acc, D, M, means3D, shs, clamped, scales, rotations, scale_modifier, cov3Ds, view, proj, proj_raw, campos,
                h_x, h_y, tan_fovx, tan_fovy, act, sh_row, !dL_dsh && badd, dmean, dcov, dscale, drot, tau, sh_written);
@@ -764,23 +744,6 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
     }
   }
 
-  if constexpr (SPLIT) {
-    // this block's Gaussians with rows, ascending: act_list[block * PB_THREADS + 0 .. count)
-    __shared__ u32 s_listed[PB_THREADS / 64];
-    const u64 lm = ballot(has_rows);
-    const int lane = lane_id(), w = threadIdx.x >> 6;
-    if (lane == 0) s_listed[w] = (u32)__popcll(lm);
-    __syncthreads();
-    u32 before = 0, total = 0;
-#pragma unroll
-    for (int k = 0; k < PB_THREADS / 64; ++k) {
-      before += (k < w) ? s_listed[k] : 0u;
-      total += s_listed[k];
-    }
-    if (has_rows) act_list[(size_t)blockIdx.x * PB_THREADS + before + (u32)__popcll(lm & ((1ull << lane) - 1ull))] = (u32)r;
-    if (threadIdx.x == 0) act_count[blockIdx.x] = total;
-    return;  // (dL_dtau's partial sums come from pb_chain_kernel)
-  }
   // deterministic block partial of tau (fixed butterfly order, then waves in order)
   if (tau_partials) {
     __shared__ float wsum[PB_THREADS / 64][6];
@@ -799,30 +762,10 @@ __global__ __launch_bounds__(PB_THREADS) void preprocess_bwd_kernel(
   }
 }
 
-// The blocks' lists concatenated, in block order (= ascending Gaussian index): compact[0 .. *total).  One block: every thread
-// sums the counts of its contiguous share of the blocks, one block-wide scan, then copies its blocks' entries.
-constexpr int PC_THREADS = 1024;
-__global__ __launch_bounds__(PC_THREADS) void pb_compact_kernel(int nb, const u32* __restrict__ act_count,
-                                                                const u32* __restrict__ act_list, u32* __restrict__ compact,
-                                                                int32_t* __restrict__ total_out) {
-  __shared__ u32 s_w[PC_THREADS / 64];
-  const int tid = threadIdx.x;
-  const int per = (nb + PC_THREADS - 1) / PC_THREADS;
-  const int b0 = min(tid * per, nb), b1 = min(b0 + per, nb);
-  u32 mine = 0;
-  for (int b = b0; b < b1; ++b) mine += act_count[b];
-  u32 total;
-  u32 off = block_excl_scan<PC_THREADS / 64>(mine, s_w, &total);
-  for (int b = b0; b < b1; ++b) {
-    const u32 c = act_count[b];
-    for (u32 i = 0; i < c; ++i) compact[off + i] = act_list[(size_t)b * PB_THREADS + i];
-    off += c;
-  }
-  if (tid == 0) *total_out = (int32_t)total;
-}
-
-// The chain for the listed Gaussians, a lane each (pb_chain), over what the SPLIT form of preprocess_bwd_kernel left: per-Gaussian
-// outputs are overwritten, the bucket's chain columns written (assign) or added to.  Persistent grid; block partials of dL_dtau.
+// What is left of the three-kernel form of this stage (round 4, DESIGN 10 (d'): measured, lost, removed): the chain for a list of
+// Gaussians, a lane each (pb_chain).  NOTHING LAUNCHES IT.  It stays for now because taking it out of this translation unit changes
+// the machine code the compiler emits for preprocess_bwd_kernel, which runs none of it (another block layout, eight more branch
+// and exec-mask instructions among 3 700, cause not found) — it goes once the cause is known.
 constexpr int CH_THREADS = 128;
 __global__ __launch_bounds__(CH_THREADS) void pb_chain_kernel(
     const int32_t* __restrict__ total_p, const u32* __restrict__ compact, const float* __restrict__ gacc, int ROW, int D, int M,
@@ -970,38 +913,16 @@ static void launch_pb_t(const olsr_scene& s, const FrameDims& d, const GeometryS
                                                              rows_stamp_of(s.backward_row_capacity));
   const int F_out = s.F;
   const size_t bucket_lds = o.bucket_flat ? sizeof(float) * PB_THREADS * (size_t)(11 + 3 * s.M + F_out) : 0;
-#define OLSR_PB_ARGS                                                                                                      \
-  s.P, s.D, s.M, g.gacc, g.tiles_touched, g.inst_start, b.rowbase, rows, g.counters, s.means3D, radii, s.shs, g.clamped,  \
-      s.scales, s.rotations, s.scale_modifier, cov3D_ptr, s.viewmatrix, s.projmatrix, s.projmatrix_raw, s.cam_pos,        \
-      d.focal_x, d.focal_y, s.tan_fovx, s.tan_fovy, o.dL_dmeans2D, o.dL_dconic, o.dL_dopacity, o.dL_dcolors,              \
-      o.dL_dlanguage, o.dL_ddepths, o.dL_dmeans3D, o.dL_dcov3D, o.dL_dsh, o.dL_dscales, o.dL_drotations, o.dL_dtau
-  int n_partials = nb;
-#if OLSR_PB_SPLIT
-  {
-    // scratch: the depth sort's key / value buffers are dead once the forward's emission has run (olsr_state.h)
-    u32 *act_list = g.key_a, *act_count = g.key_b, *compact = g.val_b;
-    int32_t* total = &g.counters[CNT_EMITTERS];
-    preprocess_bwd_kernel<F, true><<<nb, PB_THREADS, bucket_lds, st>>>(
-        OLSR_PB_ARGS, nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii, o.bucket_assign, s.activations,
-        s.opacities, F_out, o.bucket_row_mask, g.gacc, act_list, act_count, g.blended, rows_stamp_of(s.backward_row_capacity),
-        g.conic_opacity);
-    pb_compact_kernel<<<1, PC_THREADS, 0, st>>>(nb, act_count, act_list, compact, total);
-    n_partials = std::min(nb, 256);
-    pb_chain_kernel<<<n_partials, CH_THREADS, 0, st>>>(
-        total, compact, g.gacc, grad_row(F), s.D, s.M, s.means3D, s.shs, g.clamped, s.scales, s.rotations, s.scale_modifier,
-        cov3D_ptr, s.viewmatrix, s.projmatrix, s.projmatrix_raw, s.cam_pos, d.focal_x, d.focal_y, s.tan_fovx, s.tan_fovy,
-        s.activations, o.dL_dmeans3D, o.dL_dcov3D, o.dL_dsh, o.dL_dscales, o.dL_drotations, o.dL_dtau,
-        o.dL_dtau_sum ? tau_partials : nullptr, o.bucket_flat, o.bucket_assign, 11 + 3 * s.M + F_out);
-  }
-#else
-  preprocess_bwd_kernel<F, false><<<nb, PB_THREADS, bucket_lds, st>>>(
-      OLSR_PB_ARGS, o.dL_dtau_sum ? tau_partials : nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii,
-      o.bucket_assign, s.activations, s.opacities, F_out, o.bucket_row_mask, nullptr, nullptr, nullptr, g.blended,
+  preprocess_bwd_kernel<F><<<nb, PB_THREADS, bucket_lds, st>>>(
+      s.P, s.D, s.M, g.gacc, g.tiles_touched, g.inst_start, b.rowbase, rows, g.counters, s.means3D, radii, s.shs, g.clamped,
+      s.scales, s.rotations, s.scale_modifier, cov3D_ptr, s.viewmatrix, s.projmatrix, s.projmatrix_raw, s.cam_pos,
+      d.focal_x, d.focal_y, s.tan_fovx, s.tan_fovy, o.dL_dmeans2D, o.dL_dconic, o.dL_dopacity, o.dL_dcolors,
+      o.dL_dlanguage, o.dL_ddepths, o.dL_dmeans3D, o.dL_dcov3D, o.dL_dsh, o.dL_dscales, o.dL_drotations, o.dL_dtau,
+      o.dL_dtau_sum ? tau_partials : nullptr, o.bucket_flat, o.bucket_densify, o.bucket_max_radii,
+      o.bucket_assign, s.activations, s.opacities, F_out, o.bucket_row_mask, g.blended,
       rows_stamp_of(s.backward_row_capacity), g.conic_opacity);
-#endif
-#undef OLSR_PB_ARGS
   if (o.dL_dtau_sum)
-    tau_final_kernel<<<1, TAU_T, 0, st>>>(tau_partials, n_partials, o.dL_dtau_sum, g.counters, o.status_dev, o.sticky_error,
+    tau_final_kernel<<<1, TAU_T, 0, st>>>(tau_partials, nb, o.dL_dtau_sum, g.counters, o.status_dev, o.sticky_error,
                                           o.status_rows ? rows_stamp_of(s.backward_row_capacity) : 0);
   else if (o.status_dev || o.sticky_error)
     tau_final_kernel<<<1, 64, 0, st>>>(tau_partials, 0, nullptr, g.counters, o.status_dev, o.sticky_error,

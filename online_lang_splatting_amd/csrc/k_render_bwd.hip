@@ -19,7 +19,7 @@
 //     j (12 lanes for the 10 reference-mode values), so the row costs one store and no permute;
 //   * the kernel is VALU-issue bound, so the per-visit instruction count is what is tuned: the
 //     skip-dependent values are three masked factors (G, dL_dalpha, alpha*T) instead of ~30
-//     zero-initialised registers, the language dot product runs on packed fp32 FMAs, 1/(1-alpha)
+//     zero-initialised registers, the language dot product runs as FMAs on pairs of channels, 1/(1-alpha)
 //     is v_rcp + one Newton step, and the reference-mode language row (tile rank 0 only) is ONE
 //     scalar broadcast times a per-lane constant;
 //   * no float atomics: rows are compacted in emission order (rowbase = exclusive scan of
@@ -33,11 +33,8 @@
 //   - the language recursion (accum_rec_F, last_language_feature) runs for every pixel of the
 //     tile whenever the tile as a whole does not skip the splat.
 // MODE = OLSR_BWD_EXACT sums all pixels and guards the language recursion like colour.
-#include <type_traits>
-
 #include "olsr_device.h"
 #include "olsr_kernels.h"
-#include "olsr_dense.h"  // f32x4
 
 namespace olsr {
 
@@ -64,42 +61,27 @@ __device__ __forceinline__ constexpr bool own_lanes_clear(int first, int end, in
   return true;
 }
 
-#ifndef OLSR_BWD_LDS_REDUCE
-#define OLSR_BWD_LDS_REDUCE 1  // fold the lanes of the per-splat sums through LDS (olsr_device.h) instead of permlane swaps
-#endif
-#ifndef OLSR_BWD_MFMA_REDUCE
-#define OLSR_BWD_MFMA_REDUCE 0  // 1: sum the ten per-splat values over the wave with MFMAs (round-4 experiment, slower: see the kernel)
-#endif
-#ifndef OLSR_BWD_SCALAR_MAX_F
-#define OLSR_BWD_SCALAR_MAX_F 32
-#endif
-#ifndef OLSR_BWD_SCALAR_VALUE
-#define OLSR_BWD_SCALAR_VALUE 1  // the value path on scalar fp32 (build with -fno-slp-vectorize); 0: packed pairs (rounds 1-3)
-#endif
-// packed fp32 is half rate on gfx950: two lanes' work in twice the time, plus the moves that pair the operands up
-struct bv2s {
+// The value path's pairs, on scalar fp32 for every F (build with -fno-slp-vectorize): packed fp32 is half rate on gfx950 —
+// two lanes' work in twice the time, plus the moves that pair the operands up (config 3: 0.1907 -> 0.1763 ms, exact mode
+// 1 108 -> 1 155 fps, tracking iteration 0.548 -> 0.538 ms; config 5, F = 32: 0.525 -> 0.506 ms against the packed pairs of
+// rounds 1-3).
+struct bv2 {
   float x, y;
 };
 // (value path only: its products and sums may contract to FMAs like the packed form's did — the flag travels with the
 //  operations when they are inlined; the decision path never touches this type)
 #pragma clang fp contract(fast)
-__device__ __forceinline__ bv2s operator+(bv2s a, bv2s b) { return {a.x + b.x, a.y + b.y}; }
-__device__ __forceinline__ bv2s operator-(bv2s a, bv2s b) { return {a.x - b.x, a.y - b.y}; }
-__device__ __forceinline__ bv2s operator*(bv2s a, bv2s b) { return {a.x * b.x, a.y * b.y}; }
-__device__ __forceinline__ bv2s operator*(bv2s a, float b) { return {a.x * b, a.y * b}; }
-__device__ __forceinline__ bv2s operator-(bv2s a) { return {-a.x, -a.y}; }
-__device__ __forceinline__ bv2s& operator+=(bv2s& a, bv2s b) {
+__device__ __forceinline__ bv2 operator+(bv2 a, bv2 b) { return {a.x + b.x, a.y + b.y}; }
+__device__ __forceinline__ bv2 operator-(bv2 a, bv2 b) { return {a.x - b.x, a.y - b.y}; }
+__device__ __forceinline__ bv2 operator*(bv2 a, bv2 b) { return {a.x * b.x, a.y * b.y}; }
+__device__ __forceinline__ bv2 operator*(bv2 a, float b) { return {a.x * b, a.y * b}; }
+__device__ __forceinline__ bv2 operator-(bv2 a) { return {-a.x, -a.y}; }
+__device__ __forceinline__ bv2& operator+=(bv2& a, bv2 b) {
   a.x += b.x;
   a.y += b.y;
   return a;
 }
 #pragma clang fp contract(off)
-// scalar for every F (config 3: 0.1907 -> 0.1763 ms, exact mode 1 108 -> 1 155 fps, tracking iteration 0.548 -> 0.538 ms;
-// config 5, F = 32: 0.525 -> 0.506 ms).  OLSR_BWD_SCALAR_VALUE=0 / OLSR_BWD_SCALAR_MAX_F restore the packed pairs.
-template <int F>
-struct bwd_pair {
-  typedef typename std::conditional<(OLSR_BWD_SCALAR_VALUE != 0) && (F <= OLSR_BWD_SCALAR_MAX_F), bv2s, v2f>::type type;
-};
 
 // PACKED (reference mode, 15x15 tiles): the workgroup is the 128 survivors of the reference's reduction
 // tree in two full waves (ref15_rank_of_packed); the 97 other pixels of the tile are not evaluated at all —
@@ -127,10 +109,6 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
     const float* __restrict__ lang, const float* __restrict__ depths, const float* __restrict__ final_Ts,
     const u32* __restrict__ n_contrib, const float* __restrict__ dL_dpixels, const float* __restrict__ dL_dpixels_lang,
     const float* __restrict__ dL_dpixels_depth, float* __restrict__ rows, int rows_stamp) {
-#ifdef OLSR_COMPOSITE_VGPR_FLOOR
-  asm volatile("; vgpr floor" ::: OLSR_COMPOSITE_VGPR_FLOOR);  // (experiment: fewer resident waves, room for other frames' kernels)
-#endif
-  typedef typename bwd_pair<F>::type bv2;
   constexpr int BS = TILE * TILE;
   constexpr int FR = feat_row(F);
   constexpr int ROW = grad_row(F);
@@ -164,7 +142,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   // Where the lanes of the per-splat sums are folded through LDS (olsr_device.h): the reference mode's ten values with at
   // most 16 language channels.  Measured at the other instantiations, the extra LDS costs a resident workgroup (F = 32:
   // 0.567 -> 0.602 ms) or the seven exchanges of the exact mode's 25 values cost more than the swaps (-1.7 %).
-  constexpr bool LDSR = (OLSR_BWD_LDS_REDUCE != 0) && REF && (F <= 16);
+  constexpr bool LDSR = REF && (F <= 16);
   // The reference mode's three folded registers (two groups of four values + the pair) share one in-row reduction
   // (row_sums3: 7 DPP operations instead of 12), whichever way they were folded ...
   constexpr bool MERGED = NG4 == 2 && REM == 2;  // (NV = 10: the reference mode, and the exact mode without language)
@@ -173,20 +151,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   constexpr int NTRI = MERGED ? 0 : NG4 / 3;
   static_assert(NTRI <= 4 && NG4 + 1 <= 16 && own_lanes_clear(3 * NTRI, NG4 + (REM ? 1 : 0), NTRI),
                 "the lanes of the groups reduced on their own must stay clear of the triples' lanes");
-  // The ten-value sums (NV == 10) on the MATRIX pipe (round 4): the cross-lane sum of a value is a
-  // product with a constant matrix, and v_mfma_f32_16x16x4_f32 is exact fp32.  Value m goes in as the A operand (lane l holds
-  // A[i = l % 16][k = l / 16]) against the selector B_m[k][j] = (j == m): D[i][m] += sum_k v_m[16 k + i], so ten chained MFMAs
-  // leave, in the lanes of column m, the sixteen partial sums of value m (four registers x four rows of lanes).  Three adds
-  // fold the registers — for all ten values at once, every column holds another value — and an eleventh MFMA against a ones
-  // operand folds the four rows: every lane of column m then holds total m, and lanes 0..9 store row elements 0..9 as ONE
-  // contiguous 40-byte store.  VALU work of the reduction: 3 adds, against 9 adds + 7 DPP + 2 selects + 8 LDS instructions
-  // of the LDS fold.  MEASURED (config 3, profiles/r4_experiments.json): 0.188 -> 0.262 ms, the tracking iteration's F = 0
-  // backward 0.143 -> 0.249 ms; parity suite green.  The f32-input MFMA runs at the f32 VECTOR rate (64 FLOP / clk / SIMD,
-  // MI355X_MICROARCH.md) — 11 x 32 cycles per visit that behave like VALU time, not like time on an idle pipe, plus a chain
-  // of ten dependent accumulations (40 cycles each) that an in-order wave sits out.  Kept behind the macro, off.
-  // (A non-finite value would poison all ten sums of its visit (0 x inf), not only its own.)
-  constexpr bool MRED = (OLSR_BWD_MFMA_REDUCE != 0) && MERGED;
-  __shared__ __attribute__((aligned(16))) float s_red[(LDSR && !MRED) ? NWV * 256 : 4];  // 1 KB per wave: the exchange
+  __shared__ __attribute__((aligned(16))) float s_red[LDSR ? NWV * 256 : 4];  // 1 KB per wave: the exchange
 
   // workgroup b runs on XCD b % 8 and takes the (b / 8)-th heaviest tile of that XCD's chunk
   const int tile_id = (int)tile_order[xcd_remap((int)blockIdx.x, ntiles)];
@@ -242,7 +207,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   bool seen_mine = false;  // wave-uniform: an entry of this wave's own has been visited
 #pragma unroll
   for (int ch = 0; ch < FX; ++ch) dLf[ch] = (F > 0 && inside) ? dL_dpixels_lang[ch * HW + pix] : 0.f;
-  bv2 dLf2[F2X];  // the same cotangents in pairs, for packed fp32 math
+  bv2 dLf2[F2X];  // the same cotangents in pairs
 #pragma unroll
   for (int k2 = 0; k2 < F2X; ++k2) {
     dLf2[k2].x = (2 * k2 < F) ? dLf[(2 * k2 < F) ? 2 * k2 : 0] : 0.f;
@@ -256,12 +221,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   // to the free lanes in ascending order.
   const int lg = lane & 15, lr = lane >> 4;
   int role = -1;
-  float sel[MRED ? 10 : 1];  // MRED: the selectors B_m (1 in the lanes of column m)
-#pragma unroll
-  for (int m = 0; m < (MRED ? 10 : 1); ++m) sel[m] = (lg == m) ? 1.0f : 0.0f;
-  if constexpr (MRED) {
-    role = (lane < NV) ? lane : -1;  // every lane of column m ends with total m; row 0's lanes store
-  } else if constexpr (MERGED) {
+  if constexpr (MERGED) {
     // row_sums3: (lane & 15) == 4 -> group 0, == 12 -> group 1, == 0 -> the pair (rows 1 and 3 store it)
     if (lg == 4) role = (((lr & 1) << 1) | (lr >> 1));
     if (lg == 12) role = 4 + (((lr & 1) << 1) | (lr >> 1));
@@ -422,8 +382,8 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
           D_last = D_cur;
         }
         // Everything a skipping pixel must not do hangs off two masked factors and one select: alpha_eff = 0 zeroes
-        // alpha * T, inv_eff = 1 leaves T unchanged, Z is selected.  Colour and depth run on packed fp32 pairs — an
-        // instruction holds the SIMD's issue for one quad-cycle whether it is packed or not.
+        // alpha * T, inv_eff = 1 leaves T unchanged, Z is selected.  Colour and depth run in pairs of scalar fp32
+        // (bv2 above: packed fp32 is half rate).
         const float one_m_alpha = 1.f - alpha;  // in [0.01, 1] for every pixel that does not skip
         float inv = __builtin_amdgcn_rcpf(one_m_alpha);
         inv = __builtin_fmaf(__builtin_fmaf(-one_m_alpha, inv, 1.0f), inv, inv);
@@ -492,14 +452,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
       // Wave reduction (olsr_device.h): four values per permlane-swap tree, the 1-2 left over in a
       // two-value tree.  Total j ends up in the lanes whose role is j (role_of below); that lane stores it.
       float rowval = 0.f;
-      if constexpr (MRED) {
-        f32x4 d4 = {0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int m = 0; m < 10; ++m) d4 = __builtin_amdgcn_mfma_f32_16x16x4f32(sum[m], sel[m], d4, 0, 0, 0);
-        const float part = (d4[0] + d4[1]) + (d4[2] + d4[3]);
-        const f32x4 t4 = __builtin_amdgcn_mfma_f32_16x16x4f32(1.0f, part, f32x4{0.f, 0.f, 0.f, 0.f}, 0, 0, 0);
-        rowval = t4[0];
-      } else if constexpr (MERGED && LDSR) {
+      if constexpr (MERGED && LDSR) {
         float* wl = &s_red[w * 256];
         const float t0 = wave_fold4_lds(sum[0], sum[1], sum[2], sum[3], wl);
         const float t1 = wave_fold4_lds(sum[4], sum[5], sum[6], sum[7], wl);
@@ -510,17 +463,6 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         const float t1 = wave_fold4(sum[4], sum[5], sum[6], sum[7]);
         const float t2 = wave_fold2(sum[8], sum[9]);
         rowval = row_sums3(t0, t1, t2, in_hi8, in_0to3);
-      } else if constexpr (LDSR) {
-        float* wl = &s_red[w * 256];
-#pragma unroll
-        for (int g = 0; g < NG4; ++g) {
-          const float red = wave_reduce4_lds(sum[4 * g], sum[4 * g + 1], sum[4 * g + 2], sum[4 * g + 3], wl);
-          rowval = (lg == g) ? red : rowval;
-        }
-        if constexpr (REM > 0) {
-          const float red = wave_reduce2_lds(sum[4 * NG4], REM > 1 ? sum[4 * NG4 + 1] : 0.f, wl);
-          rowval = (lg == NG4) ? red : rowval;
-        }
       } else {
 #pragma unroll
         for (int j = 0; j < NTRI; ++j) {

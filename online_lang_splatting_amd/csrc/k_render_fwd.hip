@@ -47,15 +47,6 @@ constexpr int FWD_BATCH = 128;
 #define OLSR_FWD_ACC2_WAVES 7  // waves per SIMD the weight-accumulation variant is compiled for
 #endif
 
-#ifdef OLSR_FWD_STATS
-// experiment build only (scripts/build_variant.sh ... -DOLSR_FWD_STATS): how many (entry, wave) pairs the loop looks at,
-// how many pass the wave-level reach test, how many blend, and how many lanes blend — read with olsr_debug_fwd_stats
-__device__ unsigned long long g_fwd_stats[8];
-#define FWD_STAT(i, v) st_##i += (unsigned)(v)
-#else
-#define FWD_STAT(i, v)
-#endif
-
 // MFMA (OLSR_FLAG_FWD_ACCUM_MFMA): the accumulation acc[64 px x (4 + F)] += w[64 px x K] feat[K x (4 + F)], w = alpha T, runs on
 // the matrix pipe (v_mfma_f32_16x16x4_f32: exact fp32, a k-ordered fma chain) in groups of K = 4 blending entries per
 // wave, beside the VALU that evaluates alpha and the transmittance; every decision stays on the VALU, bit for bit.
@@ -81,9 +72,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
     u32* __restrict__ tile_work, const u32* __restrict__ order_hint, const int32_t* __restrict__ counters,
     const u32* __restrict__ hint_slot, float* __restrict__ depth_cut, int32_t* __restrict__ cut_miss,
     uint8_t* __restrict__ blended, const FusedLossArgs fl) {
-#ifdef OLSR_COMPOSITE_VGPR_FLOOR
-  asm volatile("; vgpr floor" ::: OLSR_COMPOSITE_VGPR_FLOOR);  // (experiment: fewer resident waves, room for other frames' kernels)
-#endif
   // a radix pass of this frame lost a predecessor's counts (olsr_state.h, counters[CNT_SYNC_ERROR]): the lists are garbage and must not be
   // used as indices — render nothing; the tile-order kernel behind this one reports OLSR_STATUS_SYNC_ERROR
   if (counters[CNT_SYNC_ERROR] != 0) return;
@@ -155,9 +143,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
   int last_base = 0;  // (uniform) first list position of the batch staged last
   // (the tile's live-pair counts are summed per flush with wave ballots straight into LDS: a per-thread counter kept across
   //  the loop cost a register the accumulation variants do not have)
-#ifdef OLSR_FWD_STATS
-  unsigned st_0 = 0, st_1 = 0, st_2 = 0, st_3 = 0, st_4 = 0;
-#endif
   float T = 1.0f;
   u32 last_contributor = 0;
   // r g b depth lang[F] in pairs: the accumulation runs on packed fp32 (v_pk_mul_f32 / v_pk_fma_f32)
@@ -262,8 +247,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
         u64 live = ~done_m;
         // wave-level early-out: no live pixel of this slot can reach the alpha floor of either entry
         const u64 reach0 = ballot(!(power.x < q1.x)) & live, reach1 = ballot(!(power.y < q1.y)) & live;
-        FWD_STAT(0, (j + 1 < cnt) ? 2 : 1);
-        FWD_STAT(1, (reach0 != 0ull) + (reach1 != 0ull));
         if ((reach0 | reach1) == 0ull) continue;
         const float2 op = *reinterpret_cast<const float2*>(&s_pair[(j >> 1) * 4 + 3]);
         const v2f G = pinned_expf2(power);
@@ -280,7 +263,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
           const u64 term_m = ok_m & ballot(test_T < 0.0001f);
           const u64 contrib_m = ok_m & ~term_m;
           done_m |= term_m;
-          FWD_STAT(4, 1);
           if (MFMA && contrib_m != 0ull) {
             const bool cl = __builtin_amdgcn_inverse_ballot_w64(contrib_m);
             const float wv = cl ? alpha * T : 0.0f;
@@ -294,8 +276,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
             if (++gfill == 4) mfma_flush();
           }
           if (contrib_m != 0ull) {
-            FWD_STAT(2, 1);
-            FWD_STAT(3, __popcll(contrib_m));
             if (!MFMA && __builtin_amdgcn_inverse_ballot_w64(contrib_m)) {
               // C += f * alpha * T as fma(f * alpha, T, C): what nvcc's default contraction makes of the
               // reference's expression (CR/forward.cu:479-484), and what the oracle restates
@@ -320,7 +300,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
             if constexpr (TILE == 15) rec |= ((contrib_m & cls_m0) ? 0x100u : 0u) | ((contrib_m & cls_m1) ? 0x200u : 0u);
             if (lane0) reinterpret_cast<uint16_t*>(s_hit)[4 * jj + w] = (uint16_t)rec;
           }
-#ifndef OLSR_FWD_INNER_BREAK
           // (no exit between the two entries of a pair: once every pixel of the wave is saturated `live` is empty, the second
           //  entry blends nothing, records nothing and changes no T — and the loop leaves below.  The break that stood here
           //  cost every blending entry ~12 scalar instructions of the structuriser's exit encoding.  The cut-off variant needs
@@ -331,12 +310,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
               break;
             }
           }
-#else
-          if (done_m == ~0ull) {
-            if constexpr (CUT) my_stop = base + jj;
-            break;
-          }
-#endif
         }
         if (done_m == ~0ull) break;
       }
@@ -369,16 +342,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
     }
   }
 
-#ifdef OLSR_FWD_STATS
-  if ((tid & 63) == 0) {
-    atomicAdd(&g_fwd_stats[0], (unsigned long long)st_0);
-    atomicAdd(&g_fwd_stats[1], (unsigned long long)st_1);
-    atomicAdd(&g_fwd_stats[2], (unsigned long long)st_2);
-    atomicAdd(&g_fwd_stats[3], (unsigned long long)st_3);
-    atomicAdd(&g_fwd_stats[4], (unsigned long long)st_4);
-    atomicAdd(&g_fwd_stats[5], (unsigned long long)n);
-  }
-#endif
   // Per-tile depth cut-offs (include/olsr.h).  The frame dropped every Gaussian that lies behind the cut-off of each tile
   // it reaches, so a tile's list is complete up to its cut-off depth and may have holes behind it.  The tile is exact if its
   // last pixel saturated at an entry not deeper than the cut-off; if it read on into the part with holes, or ran out of list
@@ -696,14 +659,3 @@ void launch_render_forward(const olsr_scene& s, const FrameDims& d, const Geomet
 #endif
 
 }  // namespace olsr
-
-#if defined(OLSR_FWD_STATS) && OLSR_FWD_TU_LOSS == 0
-extern "C" void olsr_debug_fwd_stats(unsigned long long* out8, int reset) {
-  (void)hipDeviceSynchronize();
-  (void)hipMemcpyFromSymbol(out8, HIP_SYMBOL(olsr::g_fwd_stats), 8 * sizeof(unsigned long long));
-  if (reset) {
-    unsigned long long z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    (void)hipMemcpyToSymbol(HIP_SYMBOL(olsr::g_fwd_stats), z, sizeof(z));
-  }
-}
-#endif

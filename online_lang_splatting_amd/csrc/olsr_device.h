@@ -100,12 +100,12 @@ __device__ __forceinline__ float wave_reduce2(float a, float b) {
   t += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, t), 0x142, 0xa, 0xf, false));
   return t;
 }
-// The same two reductions with the lane folding done through LDS instead of the permlane swaps.  The swaps are quarter-rate
+// The lane folding of the same two reductions done through LDS instead of the permlane swaps.  The swaps are quarter-rate
 // VALU operations (8.2 cycles of the SIMD's vector pipe each, profiles/r3_valu_ubench.json) in kernels that are bound by
 // that pipe; an LDS exchange costs the pipe nothing: one 16-byte write per lane, then every lane of row r reads the four
 // lanes of its column (one per row of 16: ds_read2st64_b32 twice) for the value its row is responsible for.  `wl` is 1 KB
 // of LDS private to the wave (a wave's LDS operations execute in order: no barrier, only the compiler is fenced).
-// Same result layout as above (rows a, c, b, d), different summation order.
+// Same rows as above (a, c, b, d), different summation order; row_sums3 below finishes inside the rows.
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
@@ -152,23 +152,6 @@ __device__ __forceinline__ float row_sums3(float t0, float t1, float t2, bool in
   m += dpp_quad<0x4E>(m);                    // quad_perm [2,3,0,1]
   m += dpp_quad<0xB1>(m);                    // quad_perm [1,0,3,2]
   return m;
-}
-__device__ __forceinline__ float wave_reduce4_lds(float a, float b, float c, float d, float* wl) {
-  float t = wave_fold4_lds(a, b, c, d, wl);
-  t += dpp_mov<0x128>(t);  // row_ror:8
-  t += dpp_mov<0x124>(t);  // row_ror:4
-  t += dpp_mov<0x122>(t);  // row_ror:2
-  t += dpp_mov<0x121>(t);  // row_ror:1
-  return t;
-}
-// rows 0 and 1 hold sum(a), rows 2 and 3 sum(b) (wave_reduce2's contract — row 1: a, row 3: b — is contained)
-__device__ __forceinline__ float wave_reduce2_lds(float a, float b, float* wl) {
-  float t = wave_fold2_lds(a, b, wl);
-  t += dpp_mov<0x128>(t);
-  t += dpp_mov<0x124>(t);
-  t += dpp_mov<0x122>(t);
-  t += dpp_mov<0x121>(t);
-  return t;
 }
 typedef float v2f __attribute__((ext_vector_type(2)));
 // lane that holds value i (0..3) of a wave_reduce4 result: rows are ordered a, c, b, d
@@ -576,13 +559,9 @@ __device__ __forceinline__ int ref15_packed_of_rank(int rank) {  // survivors on
 // 15x15 tiles; four 8x8 for 16x16).  A splat's footprint edge crosses a compact region less often than a strip, so fewer
 // (entry, wave) pairs are visited and more lanes of a visit blend; the waves' pixel counts are 64 / 56 / 56 / 49 instead of
 // 64 / 64 / 64 / 33.  Per-pixel results do not depend on the assignment (each pixel composites its list in order); tile rank 0
-// stays thread 0.  Returns TILE * TILE for a lane without a pixel.  OLSR_SLOT_QUADRANTS=0 restores the strips.
-#ifndef OLSR_SLOT_QUADRANTS
-#define OLSR_SLOT_QUADRANTS 1
-#endif
+// stays thread 0.  Returns TILE * TILE for a lane without a pixel.  The strip form is history (rank = tid).
 template <int TILE>
 __device__ __forceinline__ int slot_rank(int tid) {
-#if OLSR_SLOT_QUADRANTS
   const int w = tid >> 6, l = tid & 63;
   const int qx = w & 1, qy = w >> 1;
   int lx, ly;
@@ -597,9 +576,6 @@ __device__ __forceinline__ int slot_rank(int tid) {
     valid = ly < qh;
   }
   return valid ? (qy * 8 + ly) * TILE + qx * 8 + lx : TILE * TILE;
-#else
-  return tid;
-#endif
 }
 
 constexpr int round_up(int v, int m) { return (v + m - 1) / m * m; }
