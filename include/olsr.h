@@ -875,7 +875,9 @@ int olsr_lang_ae_decode(int32_t N, const float *codes, const float *params, int3
  * and without atomics: both are bit-reproducible.  Arithmetic is float32 (v_mfma_f32_16x16x4_f32 is a k-ordered fmaf chain),
  * norms and window sums are accumulated in double.
  *   widths        the layer widths of the general decoder, input first.  This build has kernels for the two-stage chain
- *                 {32, 192, 256, 384, 512, 768} behind the online decoder; any other list is OLSR_ERR_ARG
+ *                 {32, 192, 256, 384, 512, 768} behind the online decoder; any other list is OLSR_ERR_ARG (the single-stage
+ *                 decoder {15, 24, 48, 96, 192, 384, 384, 768} has an entry of its own in olsr_single_stage.h, whose
+ *                 similarities olsr_lang_query_relevancy takes as they are)
  *   phrases       device float[K,768], unit rows, 16-byte aligned: [n_pos positives | n_labels labels | negatives], 1 <= K <= 64
  *   codes         device float[15,in_height,in_width], channel-major: what the rasteriser returns.  When (dec_width,
  *                 dec_height) differs they are resampled first, as F.interpolate(mode="bilinear", align_corners=False) (:270)
@@ -934,7 +936,8 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params *params, const float 
  * whose h5 is exactly zero gives NaN, as in the reference.  No atomics: a call is bit-reproducible, a pixel's result does not
  * depend on the other pixels, and both input layouts give the same bits.
  *   widths          the layer widths, input first.  This build has a kernel for the two-stage chain {768, 512, 256, 128, 64, 32};
- *                   any other list (the single-stage {768, 384, 192, 96, 48, 24, 15} included) is OLSR_ERR_ARG
+ *                   any other list (the single-stage {768, 384, 192, 96, 48, 24, 15} included) is OLSR_ERR_ARG: that chain's
+ *                   encoder is a separate entry, declared in olsr_single_stage.h
  *   features768     device float, N >= 1 pixels.  OLSR_LANG_ENCODER_IN_CHANNELS: [768] planes of N pixels, plane_stride >= N
  *                   elements apart — a [1,768,h,w] tensor, or one item of a batch, read in place; no alignment is assumed and
  *                   nothing beyond pixel N - 1 of a plane is read.  OLSR_LANG_ENCODER_IN_ROWS: [N,768] (plane_stride unused)

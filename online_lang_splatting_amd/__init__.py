@@ -14,6 +14,8 @@ from .rasterizer import (GaussianRasterizationSettings, GaussianRasterizer,  # n
 from .renderer import render  # noqa: F401,E402  (the caller-side façade: gaussian_renderer.render)
 from .lang_query import LanguageDecoder, LanguageQuery  # noqa: F401,E402  (text queries on a rendered language map)
 from .lang_encoder import LanguageEncoder  # noqa: F401,E402  (the general encoder 768 -> 32 ahead of the online autoencoder)
+from .lang_single_stage import (SingleStageDecoder, SingleStageEncoder,  # noqa: F401,E402  (single_stage_ae: True: one
+                                SingleStageQuery, SingleStageTargets)     # autoencoder 768 -> 15 -> 768, nothing online)
 from .hr_net import HighResLanguageNet  # noqa: F401,E402  (the high-resolution feature net ahead of that encoder)
 from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and language maps into a 3-D map)
 from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_distance,  # noqa: F401,E402  (the 3-D evaluation's
@@ -25,7 +27,7 @@ from .frontend import KeyframeSelector, median_depth, tracking_mask  # noqa: F40
 from .slam_iterations import KeyframeWindow  # noqa: F401,E402  (mapping's bundle adjustment: window poses and exposures)
 from .losses import isotropic_loss  # noqa: F401,E402  (the mapping loss's isotropic regulariser)
 
-__all__ = ["render", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "SingleStageEncoder", "SingleStageDecoder", "SingleStageQuery", "SingleStageTargets", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "query_eval", "QueryEvaluator", "smooth_masks", "frame_metrics", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

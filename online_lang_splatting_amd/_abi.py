@@ -216,6 +216,33 @@ class OlsrLangEncoderParams(C.Structure):
                 ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
 
 
+# the single-stage chain 768 -> 15 -> 768 (include/olsr_single_stage.h): one AutoencoderMLP, no online autoencoder
+SS_ENCODER_PARAMS, SS_DECODER_PARAMS = 396927, 542544
+SS_ENCODER_WIDTHS = (768, 384, 192, 96, 48, 24, 15)
+SS_DECODER_WIDTHS = (15, 24, 48, 96, 192, 384, 384, 768)
+
+
+def _ss_encoder_state():
+    out = []
+    for k, (i, o) in enumerate(zip(SS_ENCODER_WIDTHS, SS_ENCODER_WIDTHS[1:])):
+        out += [(f"encoder.{3 * k}.weight", (o, i)), (f"encoder.{3 * k}.bias", (o,))]
+        if k < len(SS_ENCODER_WIDTHS) - 2:   # BatchNorm1d on the layer's output, ahead of the ReLU
+            out += [(f"encoder.{3 * k + 1}.{n}", (o,)) for n in ("weight", "bias", "running_mean", "running_var")]
+    return tuple(out)
+
+
+SS_ENCODER_STATE = _ss_encoder_state()
+SS_DECODER_STATE = tuple(e for k, (i, o) in enumerate(zip(SS_DECODER_WIDTHS, SS_DECODER_WIDTHS[1:]))
+                         for e in ((f"decoder.{2 * k}.weight", (o, i)), (f"decoder.{2 * k}.bias", (o,))))
+
+
+class OlsrSsEncoderParams(C.Structure):
+    """struct olsr_ss_encoder_params, include/olsr_single_stage.h."""
+
+    _fields_ = [("n_widths", C.c_int32), ("widths", C.c_int32 * 8), ("in_layout", C.c_int32), ("code_layout", C.c_int32),
+                ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
+
+
 # the high-resolution language feature net (OLSR_HR_NET_*): HighResLanguageFeatureNet's layers in forward order as
 # (module path, kind, out, in, BatchNorm path or None); kind "conv1" / "conv3" is nn.Conv2d [out,in,k,k], "convT" is
 # nn.ConvTranspose2d(4, 2, 1) [in,out,4,4].  The packed array holds, per layer, taps x [out][in] | bias | BatchNorm [4][out].

@@ -1,4 +1,4 @@
-"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h) and declares its prototypes.
+"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h and include/olsr_single_stage.h) and declares its prototypes.
 
 There is no fallback: if the library is missing or a symbol is absent this raises, loudly.
 """
@@ -18,6 +18,9 @@ EXPORTS = (
     "olsr_set_profiling", "olsr_get_stage_times", "olsr_debug_sort_timing", "olsr_debug_sort_plan", "olsr_debug_sort_knobs", "olsr_debug_sort_small", "olsr_debug_sort_compact", "olsr_debug_sort_threads", "olsr_debug_composite_stamps", "olsr_debug_sync_fault", "olsr_debug_rows_ratio", "olsr_debug_backward_ordered", "olsr_debug_backward_ordered_scratch_bytes", "olsr_debug_exp_sweep", "olsr_debug_activate", "olsr_debug_carve_log", "olsr_debug_carve_log_read", "olsr_debug_sort_status_room", "olsr_live_rows_wait", "olsr_live_rows_overwritten", "olsr_backward_rows", "olsr_last_error", "olsr_version",
 )
 
+# every symbol include/olsr_single_stage.h declares (the same library)
+EXPORTS_SINGLE_STAGE = ("olsr_ss_encoder_encode", "olsr_ss_query_sims")
+
 _lib = None
 
 
@@ -36,7 +39,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m online_lang_splatting_amd.build` "
             "(hipcc, gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS if not hasattr(L, s)]
+    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE if not hasattr(L, s)]
     if missing:
         raise ImportError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
@@ -86,6 +89,9 @@ def lib():
     L.olsr_lang_query_relevancy.argtypes, L.olsr_lang_query_relevancy.restype = [qp] + [vp] * 11, C.c_int
     L.olsr_lang_encoder_encode.argtypes = [C.POINTER(_abi.OlsrLangEncoderParams), i32] + [vp] * 6
     L.olsr_lang_encoder_encode.restype = C.c_int
+    L.olsr_ss_encoder_encode.argtypes = [C.POINTER(_abi.OlsrSsEncoderParams), i32] + [vp] * 4
+    L.olsr_ss_encoder_encode.restype = C.c_int
+    L.olsr_ss_query_sims.argtypes, L.olsr_ss_query_sims.restype = [qp] + [vp] * 5, C.c_int
     L.olsr_hr_net_workspace_bytes.argtypes, L.olsr_hr_net_workspace_bytes.restype = [i32] * 6, sz
     L.olsr_hr_net_forward.argtypes, L.olsr_hr_net_forward.restype = [C.POINTER(_abi.OlsrHrNetParams)] + [vp] * 7, C.c_int
     tv = C.POINTER(_abi.OlsrTsdfVolume)

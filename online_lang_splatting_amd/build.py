@@ -41,6 +41,7 @@ UNITS = [
     ("k_lang_ae.hip", "k_lang_ae.o", []),
     ("k_lang_query.hip", "k_lang_query.o", []),
     ("k_lang_encoder.hip", "k_lang_encoder.o", []),
+    ("k_lang_single_stage.hip", "k_lang_single_stage.o", []),
     ("k_hr_net.hip", "k_hr_net.o", []),
     ("k_knn.hip", "k_knn.o", []),
     ("k_adam.hip", "k_adam.o", []),
@@ -52,7 +53,8 @@ UNITS = [
     ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),
     ("k_query_eval.hip", "k_query_eval.o", []),
 ]
-HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h")]
+HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h"),
+           os.path.join("..", "..", "include", "olsr_single_stage.h")]
 
 
 def hipcc():

@@ -1,5 +1,5 @@
 // olsr_dense.h — the dense layer Y^T = W X^T on v_mfma_f32_16x16x4_f32 that the language nets share (k_lang_query.hip,
-// k_lang_encoder.hip, k_hr_net.hip), and the 4-float vector every MFMA user names (k_render_fwd.hip, k_render_bwd.hip).
+// k_lang_encoder.hip, k_lang_single_stage.hip, k_hr_net.hip), and the 4-float vector every MFMA user names (k_render_fwd.hip, k_render_bwd.hip).
 //
 // Device only; included after olsr_device.h by the units that use it.
 //
@@ -83,8 +83,9 @@ __device__ __forceinline__ void bn_fold(const float* __restrict__ bn, int C, int
 // What a layer does to its accumulators on their way into the image.  The two ReLUs differ: DENSE_EPI_RELU is the text
 // query's plain fmaxf, which turns a NaN activation into 0; DENSE_EPI_BN_RELU keeps it, as torch does.  Each is what its net
 // computed before the layers were shared, and which of the two the query should have is a question of behaviour, not of
-// sharing: neither was touched.
-enum { DENSE_EPI_NONE = 0, DENSE_EPI_RELU = 1, DENSE_EPI_BN_RELU = 2 };
+// sharing: neither was touched.  DENSE_EPI_RELU_NAN is the ReLU alone with the NaN kept: the single-stage query's
+// (k_lang_single_stage.hip), where a NaN code pixel has to come out as NaN similarities.
+enum { DENSE_EPI_NONE = 0, DENSE_EPI_RELU = 1, DENSE_EPI_BN_RELU = 2, DENSE_EPI_RELU_NAN = 3 };
 
 // the accumulators into the image X[64][S]; alpha, beta: the layer's folded BatchNorm per neuron (DENSE_EPI_BN_RELU)
 template <int NT, int S, int EPI>
@@ -105,6 +106,7 @@ __device__ __forceinline__ void dense_store(float* __restrict__ X, const float* 
       for (int r = 0; r < 4; ++r) {
         if (EPI == DENSE_EPI_RELU) v[r] = fmaxf(v[r], 0.f);
         if (EPI == DENSE_EPI_BN_RELU) v[r] = relu_keep_nan(fmaf(al[r], v[r], be[r]));
+        if (EPI == DENSE_EPI_RELU_NAN) v[r] = relu_keep_nan(v[r]);
       }
       *reinterpret_cast<f32x4*>(X + (pt * 16 + li) * S + n) = v;
     }

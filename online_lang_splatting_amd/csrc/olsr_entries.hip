@@ -341,16 +341,13 @@ int olsr_lang_ae_decode(int32_t N, const float* codes, const float* params, int3
   return launch_check("lang_ae_decode");
 }
 
-// the six layer widths a caller names against the ones compiled in
-static bool widths_built(int32_t n_widths, const int32_t* widths, const int32_t (&built)[6]) {
-  return n_widths == 6 && std::equal(built, built + 6, widths);
+// the layer widths a caller names against the ones compiled in
+static bool widths_built(int32_t n_widths, const int32_t* widths, std::initializer_list<int32_t> built) {
+  return n_widths == (int32_t)built.size() && std::equal(built.begin(), built.end(), widths);
 }
 
-// what is wrong with the sizes of a language query, or nullptr
-static const char* lang_query_params_error(const olsr_lang_query_params* p) {
-  if (!p) return "the parameter struct is NULL";
-  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_AE_IN, 192, 256, 384, 512, OLSR_LANG_QUERY_FEATURE_DIM}))
-    return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
+// what is wrong with the sizes of a language query apart from its width list, or nullptr
+static const char* lang_query_sizes_error(const olsr_lang_query_params* p) {
   if (p->K < 1 || p->K > OLSR_LANG_QUERY_MAX_PHRASES) return "K must be between 1 and 64";
   if (p->n_pos < 0 || p->n_labels < 0 || p->n_pos + p->n_labels > p->K) return "n_pos and n_labels must be >= 0 and sum to at most K";
   if (p->in_width < 1 || p->in_height < 1 || p->dec_width < 1 || p->dec_height < 1 || p->out_width < 1 || p->out_height < 1)
@@ -360,6 +357,14 @@ static const char* lang_query_params_error(const olsr_lang_query_params* p) {
     return "a map has at most 2^28 pixels";
   if (p->flags & ~(OLSR_LANG_QUERY_WANT_MASK | OLSR_LANG_QUERY_WANT_LABELS)) return "flags holds unknown OLSR_LANG_QUERY_* bits";
   return nullptr;
+}
+
+// what is wrong with the sizes of a language query, or nullptr
+static const char* lang_query_params_error(const olsr_lang_query_params* p) {
+  if (!p) return "the parameter struct is NULL";
+  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_AE_IN, 192, 256, 384, 512, OLSR_LANG_QUERY_FEATURE_DIM}))
+    return "this build decodes the layer widths {32, 192, 256, 384, 512, 768} only";
+  return lang_query_sizes_error(p);
 }
 
 size_t olsr_lang_query_scratch_bytes(const olsr_lang_query_params* p) {
@@ -414,6 +419,38 @@ int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const
   if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "lang_encoder_encode: encoder_params must be 16-byte aligned");
   return launch_check("lang_encoder_encode", launch_lang_encoder(*p, N, features768, encoder_params, online_params,
                                                                  features32, codes, (hipStream_t)hip_stream));
+}
+
+// ---- the single-stage chain (include/olsr_single_stage.h)
+int olsr_ss_encoder_encode(const olsr_ss_encoder_params* p, int32_t N, const float* features768, const float* encoder_params,
+                           float* codes, void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "ss_encoder_encode: the parameter struct is NULL");
+  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_QUERY_FEATURE_DIM, 384, 192, 96, 48, 24, OLSR_LANG_AE_CODE}))
+    return fail(OLSR_ERR_ARG, "ss_encoder_encode: this entry encodes the layer widths {768, 384, 192, 96, 48, 24, 15} only");
+  if (N < 1) return fail(OLSR_ERR_ARG, "ss_encoder_encode: N must be positive");
+  if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS)
+    return fail(OLSR_ERR_ARG, "ss_encoder_encode: unknown input layout");
+  if (!lang_ae_layout_ok(p->code_layout)) return fail(OLSR_ERR_ARG, "ss_encoder_encode: unknown code layout");
+  if (p->in_layout == OLSR_LANG_ENCODER_IN_CHANNELS && p->plane_stride < (int64_t)N)
+    return fail(OLSR_ERR_ARG, "ss_encoder_encode: plane_stride must be at least N in the channel layout");
+  if (!(p->bn_eps > 0.0)) return fail(OLSR_ERR_ARG, "ss_encoder_encode: bn_eps must be positive");
+  if (!features768 || !encoder_params || !codes)
+    return fail(OLSR_ERR_ARG, "ss_encoder_encode: features768, encoder_params and codes are required");
+  if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "ss_encoder_encode: encoder_params must be 16-byte aligned");
+  return launch_check("ss_encoder_encode", launch_ss_encoder(*p, N, features768, encoder_params, codes, (hipStream_t)hip_stream));
+}
+
+int olsr_ss_query_sims(const olsr_lang_query_params* p, const float* codes, const float* decoder_params, const float* phrases,
+                       float* sims, void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "ss_query_sims: the parameter struct is NULL");
+  if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_AE_CODE, 24, 48, 96, 192, 384, 384, OLSR_LANG_QUERY_FEATURE_DIM}))
+    return fail(OLSR_ERR_ARG, "ss_query_sims: this entry decodes the layer widths {15, 24, 48, 96, 192, 384, 384, 768} only");
+  if (const char* e = lang_query_sizes_error(p)) return fail(OLSR_ERR_ARG, std::string("ss_query_sims: ") + e);
+  if (!codes || !decoder_params || !phrases || !sims)
+    return fail(OLSR_ERR_ARG, "ss_query_sims: codes, decoder_params, phrases and sims are required");
+  if (((uintptr_t)decoder_params & 15u) || ((uintptr_t)phrases & 15u))
+    return fail(OLSR_ERR_ARG, "ss_query_sims: decoder_params and phrases must be 16-byte aligned");
+  return launch_check("ss_query_sims", launch_ss_query_sims(*p, codes, decoder_params, phrases, sims, (hipStream_t)hip_stream));
 }
 
 size_t olsr_hr_net_workspace_bytes(int32_t h, int32_t w, int32_t h3, int32_t w3, int32_t h2, int32_t w2) {

@@ -4,6 +4,7 @@
 #include <stdint.h>
 
 #include "../../include/olsr.h"
+#include "../../include/olsr_single_stage.h"
 #include "olsr_state.h"
 
 namespace olsr {
@@ -303,6 +304,12 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
 // k_lang_encoder.hip: the general language encoder 768 -> 32 (include/olsr.h)
 hipError_t launch_lang_encoder(const olsr_lang_encoder_params& p, int N, const float* features, const float* params,
                                const float* online, float* features32, float* codes, hipStream_t st);
+
+// k_lang_single_stage.hip: the single-stage chain's encoder 768 -> 15 and stage A of its text query (include/olsr_single_stage.h)
+hipError_t launch_ss_encoder(const olsr_ss_encoder_params& p, int N, const float* features, const float* params, float* codes,
+                             hipStream_t st);
+hipError_t launch_ss_query_sims(const olsr_lang_query_params& p, const float* codes, const float* dec, const float* phrases,
+                                float* sims, hipStream_t st);
 
 // k_hr_net.hip: the high-resolution language feature net ahead of the encoder (include/olsr.h)
 size_t hr_net_workspace_bytes(long long h, long long w);

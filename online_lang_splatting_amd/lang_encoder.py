@@ -39,6 +39,32 @@ def load_encoder_state(flat, state):
                      f"the widths {_abi.LANG_ENCODER_WIDTHS} are compiled into the kernel", CHECKPOINT_PREFIX, "encoder.")
 
 
+def feature_items(device, who, t):
+    """A feature tensor on `device` -> (layout, N, plane_stride, [data pointer per item]).  No conversion and no copy: what
+    cannot be read in place is an error.  (Shared with lang_single_stage.SingleStageEncoder: the input forms are the same.)"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
+        raise RuntimeError(f"{who}: features must be a float32 tensor on the GPU")
+    if t.device != device:
+        raise RuntimeError(f"{who}: features is on {t.device}, expected {device}")
+    t = t.detach()
+    if t.dim() == 2:
+        if t.shape[1] != FEATURE_DIM or t.shape[0] < 1:
+            raise RuntimeError(f"{who}: features has shape {tuple(t.shape)}, expected [N,{FEATURE_DIM}] with N >= 1")
+        if not t.is_contiguous():
+            raise RuntimeError(f"{who}: [N,{FEATURE_DIM}] rows must be contiguous")
+        return _abi.LANG_ENCODER_IN_ROWS, int(t.shape[0]), 0, [t.data_ptr()]
+    if t.dim() == 3:
+        t = t.unsqueeze(0)
+    if t.dim() != 4 or t.shape[1] != FEATURE_DIM or min(t.shape[0], t.shape[2], t.shape[3]) < 1:
+        raise RuntimeError(f"{who}: features has shape {tuple(t.shape)}, expected [N,{FEATURE_DIM}], [{FEATURE_DIM},h,w] or "
+                           f"[B,{FEATURE_DIM},h,w]")
+    B, _, h, w = t.shape
+    if (w > 1 and t.stride(3) != 1) or (h > 1 and t.stride(2) != w) or t.stride(1) < h * w:
+        raise RuntimeError(f"{who}: every channel plane must be contiguous and the planes must not overlap "
+                           f"(strides {tuple(t.stride())} for shape {tuple(t.shape)})")
+    return _abi.LANG_ENCODER_IN_CHANNELS, int(h * w), int(t.stride(1)), [t[b].data_ptr() for b in range(B)]
+
+
 class LanguageEncoder:
     """The general encoder (AutoencoderMLP.encoder with its BatchNorm running statistics) as a flat float32 array on `device`."""
 
@@ -71,29 +97,7 @@ class LanguageEncoder:
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def _items(self, who, t):
-        """-> (layout, N, plane_stride, [data pointer per item]).  No conversion and no copy: what cannot be read in place is an
-        error."""
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"{who}: features must be a float32 tensor on the GPU")
-        if t.device != self.device:
-            raise RuntimeError(f"{who}: features is on {t.device}, expected {self.device}")
-        t = t.detach()
-        if t.dim() == 2:
-            if t.shape[1] != FEATURE_DIM or t.shape[0] < 1:
-                raise RuntimeError(f"{who}: features has shape {tuple(t.shape)}, expected [N,{FEATURE_DIM}] with N >= 1")
-            if not t.is_contiguous():
-                raise RuntimeError(f"{who}: [N,{FEATURE_DIM}] rows must be contiguous")
-            return _abi.LANG_ENCODER_IN_ROWS, int(t.shape[0]), 0, [t.data_ptr()]
-        if t.dim() == 3:
-            t = t.unsqueeze(0)
-        if t.dim() != 4 or t.shape[1] != FEATURE_DIM or min(t.shape[0], t.shape[2], t.shape[3]) < 1:
-            raise RuntimeError(f"{who}: features has shape {tuple(t.shape)}, expected [N,{FEATURE_DIM}], [{FEATURE_DIM},h,w] or "
-                               f"[B,{FEATURE_DIM},h,w]")
-        B, _, h, w = t.shape
-        if (w > 1 and t.stride(3) != 1) or (h > 1 and t.stride(2) != w) or t.stride(1) < h * w:
-            raise RuntimeError(f"{who}: every channel plane must be contiguous and the planes must not overlap "
-                               f"(strides {tuple(t.stride())} for shape {tuple(t.shape)})")
-        return _abi.LANG_ENCODER_IN_CHANNELS, int(h * w), int(t.stride(1)), [t[b].data_ptr() for b in range(B)]
+        return feature_items(self.device, who, t)
 
     def _launch(self, lay, N, plane_stride, ptr, online, feat_ptr, codes_ptr, code_layout):
         p = _abi.OlsrLangEncoderParams(n_widths=len(_abi.LANG_ENCODER_WIDTHS), in_layout=lay, code_layout=code_layout,
