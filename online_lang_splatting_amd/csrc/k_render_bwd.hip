@@ -87,7 +87,7 @@ __device__ __forceinline__ bv2& operator+=(bv2& a, bv2 b) {
 // tree in two full waves (ref15_rank_of_packed); the 97 other pixels of the tile are not evaluated at all —
 // nothing they compute reaches an output of the reference's backward.
 //
-// B: the staging batch, list entries per fill of the LDS tables; WAVES: the waves per SIMD the instantiation is compiled for.
+// B: the staging batch, list entries per fill of the LDS tables; WAVES .. WAVES_MAX: the waves per SIMD the instantiation is compiled for.
 // Both are chosen per instantiation (bwd_shape).  The LDS of a workgroup is almost all staging (80 B of features per entry at
 // F = 15), so B decides how many workgroups a CU holds; the per-pixel state lives in registers across batches, a smaller batch
 // only meets the other waves of its tile more often.
@@ -99,16 +99,20 @@ struct bwd_shape {
   static constexpr bool SMALL = (MODE == OLSR_BWD_REFERENCE) && (F <= 16);
   static constexpr int B = SMALL ? 64 : 128;
   static constexpr int WAVES = SMALL ? 7 : 1;
+  // ... and NOT eight, which the 62 - 66 registers of the F = 15 / 16 instantiations would otherwise give them: the visit
+  // waits on LDS, and an eighth wave per SIMD only lengthens that queue (backward stage 0.160 ms at eight waves against
+  // 0.153 at seven).  The compiler rounds their register count up to seven waves' worth.
+  static constexpr int WAVES_MAX = (SMALL && F > 3) ? 7 : 8;
 };
 template <int TILE, int F, int MODE, bool PACKED, int B, int WAVES>
-__global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
+__global__ __launch_bounds__(PACKED ? 128 : 256) __attribute__((amdgpu_waves_per_eu(WAVES, bwd_shape<F, MODE>::WAVES_MAX))) void render_bwd_kernel(
     const u32* __restrict__ ranges, const u32* __restrict__ inst_gid, const u32* __restrict__ src,
     const uint8_t* __restrict__ flags, const u32* __restrict__ rowbase, const int32_t* __restrict__ counters,
     const u32* __restrict__ tile_order, int W, int H, int gx, int ntiles, const float* __restrict__ bg,
     const float* __restrict__ means2D, const float* __restrict__ conic_opacity, const float* __restrict__ colors,
     const float* __restrict__ lang, const float* __restrict__ depths, const float* __restrict__ final_Ts,
     const u32* __restrict__ n_contrib, const float* __restrict__ dL_dpixels, const float* __restrict__ dL_dpixels_lang,
-    const float* __restrict__ dL_dpixels_depth, float* __restrict__ rows, int rows_stamp) {
+    const float* __restrict__ dL_dpixels_depth, float* __restrict__ rows, int rows_stamp, float half_W, float half_H) {
   constexpr int BS = TILE * TILE;
   constexpr int FR = feat_row(F);
   constexpr int ROW = grad_row(F);
@@ -133,10 +137,13 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   static_assert(ROW <= 64, "one lane per row element");
   static_assert(!PACKED || (REF && TILE == 15), "survivor packing is the reference mode of 15x15 tiles");
 
-  __shared__ float2 s_xy[B];
-  __shared__ float4 s_co[B];
-  __shared__ __attribute__((aligned(16))) float s_feat[B * FR];
-  __shared__ u32 s_row[B];   // first compact row of the instance
+  // One LDS record per staged entry: [feature row (FR floats) | conic, opacity | x, y, first compact row, -].  A visit forms
+  // ONE wave-uniform address (i * REC) and reads everything through immediate offsets.  REC = FR + 8 floats keeps every
+  // part 16-byte aligned; at F = 15 / 16 that is 7 x 16 bytes, an odd number of 16-byte units, so the staging threads'
+  // 16-byte stores of consecutive entries fall on distinct bank groups.  The flags stay a byte array of their own: the
+  // batch's ballots read them one entry per lane, consecutive bytes.
+  constexpr int REC = FR + 8;
+  __shared__ __attribute__((aligned(16))) float s_rec[B * REC];
   __shared__ uint8_t s_flag[B];
   __shared__ int s_kmax[NWV];
   // Where the lanes of the per-splat sums are folded through LDS (olsr_device.h): the reference mode's ten values with at
@@ -165,8 +172,10 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
 
   const float bg0 = bg[0], bg1 = bg[1], bg2 = bg[2];
   const bool has_bg = (bg0 != 0.0f) || (bg1 != 0.0f) || (bg2 != 0.0f);
-  const float ddelx_dx = 0.5f * W;
-  const float ddely_dy = 0.5f * H;
+  // (0.5 W and 0.5 H arrive as kernel arguments — exact in fp32, the same bits as 0.5f * W computed here — so that the
+  //  visit's two multiplies take them as scalar operands instead of two vector registers)
+  const float ddelx_dx = half_W;
+  const float ddely_dy = half_H;
 
   // ---- per-pixel state (one pixel per lane; thread rank = ty*TILE + tx as in the reference) ----
   // Language channels are carried in "dot form": the reference keeps accum_rec_F[F] and
@@ -222,11 +231,11 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
   const int lg = lane & 15, lr = lane >> 4;
   int role = -1;
   if constexpr (MERGED) {
-    // row_sums3: (lane & 15) == 4 -> group 0, == 12 -> group 1, == 0 -> the pair (rows 1 and 3 store it)
+    // row_sums3: (lane & 15) == 4 -> group 0, == 12 -> group 1, == 0 -> the pair (rows 0 and 2 store it)
     if (lg == 4) role = (((lr & 1) << 1) | (lr >> 1));
     if (lg == 12) role = 4 + (((lr & 1) << 1) | (lr >> 1));
-    // (the pair: the LDS fold leaves a in rows 0-1 and b in rows 2-3, the swap fold a in row 0 and b in row 2)
-    if (lg == 0 && (lr & 1) == (LDSR ? 1 : 0)) role = 8 + (lr >> 1);
+    // (the pair: both folds leave a in row 0 and b in row 2)
+    if (lg == 0 && (lr & 1) == 0) role = 8 + (lr >> 1);
   } else {
     const int perm = ((lr & 1) << 1) | (lr >> 1);
 #pragma unroll
@@ -257,6 +266,7 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
     }
     if (w != 0) dLf0_lane = 0.f;
   }
+  u32 role_off = (role >= 0) ? 4u * (u32)role : 0u;  // the lane's byte offset inside a row (unsigned: a scalar base takes it)
 
   // entries at list positions >= max(last_contributor) are skipped by every pixel of the tile
   int kmax = last_contributor;
@@ -278,14 +288,15 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         const u32 u = src[sp];        // emission index of the instance
         const u32 gid = inst_gid[u];  // its Gaussian
         const int part = tid / B;  // (wave-uniform: B is a multiple of 64)
+        float* rec = &s_rec[e * REC];
         if (TPS == 1 || part == 0) {
-          s_row[e] = rowbase[u];
           s_flag[e] = flags[u];
-          s_xy[e] = reinterpret_cast<const float2*>(means2D)[gid];
-          s_co[e] = reinterpret_cast<const float4*>(conic_opacity)[gid];
+          const float2 xy = reinterpret_cast<const float2*>(means2D)[gid];
+          reinterpret_cast<float4*>(rec + FR)[0] = reinterpret_cast<const float4*>(conic_opacity)[gid];
+          reinterpret_cast<float4*>(rec + FR)[1] = make_float4(xy.x, xy.y, bits2f(rowbase[u]), 0.f);  // (the row: its bits)
         }
         if (TPS == 1 || part > 0) {
-          float* fr = &s_feat[e * FR];
+          float* fr = rec;
           const int run = (TPS == 1) ? 0 : part - 1;  // this thread's run of the row
 #pragma unroll
           for (int ch = 0; ch < FR; ++ch) {
@@ -333,8 +344,15 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
       // this wave's last contributors) are skipped outright, bit for bit the same result.
       if (REF && !mine && !seen_mine) continue;
       seen_mine = true;
-      const float* fr = &s_feat[i * FR];
+      const float* fr = &s_rec[i * REC];  // the entry's record: everything below reads it at constant offsets
       float D_cur = 0.f;
+      // reference mode: the language recursion is unguarded (CR/backward.cu:1127-1139) — it advances on every visit, own
+      // or not, and uses only the state of the visit before.  So it goes first, and the dot product below lands in D_last
+      // itself: no copy of it is carried round the loop.
+      if constexpr (REF && F > 0) {
+#pragma clang fp contract(fast)
+        A_f = last_alpha * D_last + (1.f - last_alpha) * A_f;
+      }
       if constexpr (F > 0) {
 #pragma clang fp contract(fast)
         const bv2* fr2 = reinterpret_cast<const bv2*>(fr + 4);
@@ -342,20 +360,17 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
 #pragma unroll
         for (int k = 0; k < F2; ++k) acc2 += fr2[k] * dLf2[k];
         D_cur = acc2.x + acc2.y;
+        if constexpr (REF) D_last = D_cur;
       }
       if (REF && !mine) {
         // every pixel of this slot skips, but the tile does not: only the unguarded language
-        // recursion advances (CR/backward.cu:1127-1139)
-        if constexpr (F > 0) {
-#pragma clang fp contract(fast)
-          A_f = last_alpha * D_last + (1.f - last_alpha) * A_f;
-          D_last = D_cur;
-        }
+        // recursion advances (done above)
         continue;
       }
       const int k = kstart - i;  // == `contributor` after its decrement (CR/backward.cu:999,1073)
-      const float2 xy = s_xy[i];
-      const float4 co = s_co[i];
+      const float4 co = *reinterpret_cast<const float4*>(fr + FR);
+      const float4 xy = *reinterpret_cast<const float4*>(fr + FR + 4);  // x, y, the first compact row's bits
+      asm("" ::"v"(xy.w));  // (all sixteen bytes: the 12-byte LDS read takes twice the LDS cycles of the 16-byte one)
 
       // -- decision path: bit-for-bit the forward's arithmetic (no contraction)
       bool skip = !inside;
@@ -370,19 +385,16 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
       // -- value path: FMA contraction allowed (rounding differs from the oracle by ~1 ulp per
       //    operation; no decision depends on these values).  Everything a skipping pixel must not
       //    contribute hangs off three factors that are zero for it.
-      // The state update is branch-free: every lane evaluates it, a skipping lane keeps its old state through a
-      // select.  (An `if (!skip)` block cost ~28 register copies per visit around the exec-masked region, in a kernel
-      // that is bound by VALU issue.)
+      // The sums are branch-free: every lane evaluates them.  (An `if (!skip)` block around them cost ~28 register copies
+      // per visit around the exec-masked region.)  Only the state a skipping lane must keep — Z and last_alpha — is written
+      // under `!skip`, in five instructions at the very end of the visit.
+      bv2 d01_ = {0.f, 0.f}, d23_ = {0.f, 0.f};  // colour - Z of the visit, for that update
       float f_dcd, f_dLa;  // alpha * T (dchannel_dcolor) and dL_dalpha; zero for a skipping pixel
       float sum[NVP];
       {
 #pragma clang fp contract(fast)
-        if constexpr (REF && F > 0) {  // unguarded (CR/backward.cu:1132-1133)
-          A_f = last_alpha * D_last + (1.f - last_alpha) * A_f;
-          D_last = D_cur;
-        }
-        // Everything a skipping pixel must not do hangs off two masked factors and one select: alpha_eff = 0 zeroes
-        // alpha * T, inv_eff = 1 leaves T unchanged, Z is selected.  Colour and depth run in pairs of scalar fp32
+        // Everything a skipping pixel must not do hangs off two masked factors and one masked write: alpha_eff = 0 zeroes
+        // alpha * T, inv_eff = 1 leaves T unchanged, Z is written at the end of the visit.  Colour and depth run in pairs of scalar fp32
         // (bv2 above: packed fp32 is half rate).
         const float one_m_alpha = 1.f - alpha;  // in [0.01, 1] for every pixel that does not skip
         float inv = __builtin_amdgcn_rcpf(one_m_alpha);
@@ -393,13 +405,10 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         const float4 f4 = *reinterpret_cast<const float4*>(fr);  // r g b depth of the splat (wave-uniform LDS read)
         const bv2 d01 = bv2{f4.x, f4.y} - Z01, d23 = bv2{f4.z, f4.w} - Z23;
         const bv2 dd = d01 * dL01 + d23 * dL23;
+        d01_ = d01;
+        d23_ = d23;
         float dL_dalpha = dd.x + dd.y;
-        // (a select, not alpha_eff * d: a skipping pixel must keep Z also when the splat's colour is infinite or NaN —
-        //  0 * inf would hand a NaN to every Gaussian in front of it in this pixel, which the reference's guarded update does not)
-        const bv2 a2 = {alpha, alpha};
-        const bv2 Zn01 = Z01 + a2 * d01, Zn23 = Z23 + a2 * d23;
-        Z01 = bv2{skip ? Z01.x : Zn01.x, skip ? Z01.y : Zn01.y};
-        Z23 = bv2{skip ? Z23.x : Zn23.x, skip ? Z23.y : Zn23.y};
+        // (Z and last_alpha advance at the end of the visit, under `!skip`)
         if constexpr (F > 0) {
           if constexpr (!REF) {  // guarded like colour
             const float A_new = last_alpha * D_last + (1.f - last_alpha) * A_f;
@@ -412,7 +421,6 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         }
         dL_dalpha *= T;
         dL_dalpha += bg_term * inv;  // (-T_final / (1 - alpha)) <bg, dL_dpixel>, CR/backward.cu:1119-1125; one fma, 0 without a background
-        last_alpha = skip ? last_alpha : alpha;
         f_dcd = alpha_eff * T;
         f_dLa = skip ? 0.f : dL_dalpha;
         // reference mode: only the ranks that survive its 225-lane tree contribute to these ten sums
@@ -497,8 +505,24 @@ __global__ __launch_bounds__(PACKED ? 128 : 256, WAVES) void render_bwd_kernel(
         const u32 fl = (u32)__builtin_amdgcn_readfirstlane((int)s_flag[i]);
         before = (u32)__popc(fl & ((1u << w) - 1u));
       }
-      float* rowp = rows + ((size_t)(u32)__builtin_amdgcn_readfirstlane((int)s_row[i]) + before) * ROW;  // scalar
-      if (role >= 0) rowp[role] = rowval;
+      // The row's byte address is wave-uniform and formed on the scalar unit with the full 64-bit product (the scratch can
+      // exceed 4 GiB); the lane adds only its constant, unsigned 32-bit offset role * 4.
+      const size_t row = (size_t)(u32)__builtin_amdgcn_readfirstlane((int)f2bits(xy.z)) + before;
+      size_t rowp = reinterpret_cast<size_t>(rows) + row * (size_t)(ROW * sizeof(float));
+      asm("" : "+s"(rowp));  // (stays a scalar pair: otherwise the lane offset is folded in first and the sum becomes a 64-bit vector multiply-add)
+      typedef __attribute__((address_space(1))) float global_float;  // (an address made of integers: say that it is global memory)
+      asm("" : "+v"(role_off));  // (its zero extension belongs to THIS store — scalar base + 32-bit lane offset — not into a 64-bit register pair ahead of the loop)
+      if (role >= 0) *(global_float*)(rowp + role_off) = rowval;
+      // Z <- Z + alpha (c - Z) and last_alpha, for the lanes that blend: four FMAs and a move under the lane mask.  A masked
+      // write, not alpha_eff * d: a skipping pixel must keep Z also when the splat's colour is infinite or NaN — 0 * inf
+      // would hand a NaN to every Gaussian in front of it in this pixel, which the reference's guarded update does not.
+      // Nothing else may move in here (see above).
+      if (!skip) {
+#pragma clang fp contract(fast)
+        Z01 = Z01 + bv2{alpha, alpha} * d01_;
+        Z23 = Z23 + bv2{alpha, alpha} * d23_;
+        last_alpha = alpha;
+      }
     }
     }
   }
@@ -515,7 +539,7 @@ static void launch_bwd_t(const olsr_scene& s, const FrameDims& d, const Geometry
       im.ranges, b.inst_gid, b.src, b.flags, b.rowbase, g.counters, im.tile_order, d.W, d.H, d.gx, d.ntiles,
       s.background,
       g.means2D, g.conic_opacity, colors, s.language_precomp, g.depths, im.final_T, im.n_contrib, dc, dl, dd, rows,
-      rows_stamp_of(s.backward_row_capacity));
+      rows_stamp_of(s.backward_row_capacity), 0.5f * d.W, 0.5f * d.H);
 }
 
 // F_rows: the language channels the rows carry — s.F, or 0 when the caller handed no language cotangent (the

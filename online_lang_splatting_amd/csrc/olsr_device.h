@@ -102,33 +102,49 @@ __device__ __forceinline__ float wave_reduce2(float a, float b) {
 }
 // The lane folding of the same two reductions done through LDS instead of the permlane swaps.  The swaps are quarter-rate
 // VALU operations (8.2 cycles of the SIMD's vector pipe each, profiles/r3_valu_ubench.json) in kernels that are bound by
-// that pipe; an LDS exchange costs the pipe nothing: one 16-byte write per lane, then every lane of row r reads the four
-// lanes of its column (one per row of 16: ds_read2st64_b32 twice) for the value its row is responsible for.  `wl` is 1 KB
-// of LDS private to the wave (a wave's LDS operations execute in order: no barrier, only the compiler is fenced).
+// that pipe; an LDS exchange costs the pipe nothing.  `wl` is 1 KB of LDS private to the wave (a wave's LDS operations
+// execute in order: no barrier, only the compiler is fenced), laid out TRANSPOSED: value v of lane (row rk, column col)
+// goes to word 64 v + 4 col + rk, so the four lanes of a column lie side by side and a lane of row r reads the four
+// partial values its row is responsible for — lanes col, col + 16, col + 32, col + 48 — with ONE 16-byte read (4 LDS
+// cycles, conflict-free: the sixteen lanes of a read group hold sixteen different columns) instead of two
+// ds_read2st64_b32 (8), and the writes are ds_write2st64_b32 (two lanes per bank, which a 4-byte store does not pay
+// for) that need no four consecutive registers.  The kernels that fold this way wait on LDS, so its cycles count
+// (DESIGN.md 12.9).
 // Same rows as above (a, c, b, d), different summation order; row_sums3 below finishes inside the rows.
 __device__ __forceinline__ void wave_lds_fence() {
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
 }
-// (the fold alone: on return lane (row r, column c) holds the sum over the four rows of column c, of the value row r is
-//  responsible for — sixteen partial sums per value are left to add up inside the row)
+// (on return lane (row r, column c) holds the sum over the four rows of column c, of the value row r is responsible for —
+//  sixteen partial sums per value are left to add up inside the row)
+__device__ __forceinline__ float wave_fold_lds_read(const float* wl, int l) {
+  const int r = l >> 4, col = l & 15;
+  const float4 x = *reinterpret_cast<const float4*>(wl + 64 * (((r & 1) << 1) | (r >> 1)) + 4 * col);  // row 0 -> a, 1 -> c, 2 -> b, 3 -> d
+  return (x.x + x.y) + (x.z + x.w);                                                                    // lanes col, col + 16, col + 32, col + 48
+}
 __device__ __forceinline__ float wave_fold4_lds(float a, float b, float c, float d, float* wl) {
   const int l = lane_id();
-  reinterpret_cast<float4*>(wl)[l] = make_float4(a, b, c, d);
+  float* w = wl + 4 * (l & 15) + (l >> 4);
+  w[0] = a;
+  w[64] = b;
+  w[128] = c;
+  w[192] = d;
   wave_lds_fence();
-  const int r = l >> 4, col = l & 15;
-  const float* p = wl + 4 * col + (((r & 1) << 1) | (r >> 1));  // row 0 -> a, 1 -> c, 2 -> b, 3 -> d
-  const float t = (p[0] + p[64]) + (p[128] + p[192]);            // lanes col, col + 16, col + 32, col + 48
+  const float t = wave_fold_lds_read(wl, l);
   wave_lds_fence();
   return t;
 }
-__device__ __forceinline__ float wave_fold2_lds(float a, float b, float* wl) {  // rows 0, 1 -> a; rows 2, 3 -> b
+// Two values, on the four-value fold's own two addresses (a kernel that calls both keeps two address registers): only a and
+// b are written, so row 0 comes out with the sum of a and row 2 with that of b, like wave_fold2.  Rows 1 and 3 read the
+// words of c and d, which this call does not write: their result is unspecified and must not be used (the in-row sums
+// never cross rows).
+__device__ __forceinline__ float wave_fold2_lds(float a, float b, float* wl) {  // row 0 -> a; row 2 -> b
   const int l = lane_id();
-  reinterpret_cast<float2*>(wl)[l] = make_float2(a, b);
+  float* w = wl + 4 * (l & 15) + (l >> 4);
+  w[0] = a;
+  w[64] = b;
   wave_lds_fence();
-  const int r = l >> 4, col = l & 15;
-  const float* p = wl + 2 * col + (r >> 1);
-  const float t = (p[0] + p[32]) + (p[64] + p[96]);
+  const float t = wave_fold_lds_read(wl, l);
   wave_lds_fence();
   return t;
 }
