@@ -36,10 +36,8 @@ def fwd_args(sc, dev=None, colors_precomp=None, cov3D_precomp=None, scale_modifi
     return a
 
 
-def run_backend(C, sc, dev=None, seed=0, tile=15, mode=0, binning=1, **kw):
-    """Forward + backward through backend module C (oracle_C or the product _C).  Returns (fwd dict, grads dict).
-    `binning` (product only; the oracle always bins like the reference): 1 = exact ellipse lists (the
-    product's default), 0 = the reference's bounding-square lists."""
+def run_forward(C, sc, dev=None, tile=15, mode=0, binning=1, **kw):
+    """The forward half of run_backend: (fwd dict, the positional args it was called with)."""
     C.TILE = tile
     C.BWD_MODE = mode
     C.BINNING = binning
@@ -52,6 +50,16 @@ def run_backend(C, sc, dev=None, seed=0, tile=15, mode=0, binning=1, **kw):
         lang = None
     fwd = dict(R=R, color=color, language=lang, radii=radii, depth=depth, opacity=opac, n_touched=nt, geom=geom,
                binning=binb, img=img)
+    return fwd, a
+
+
+def run_backend(C, sc, dev=None, seed=0, tile=15, mode=0, binning=1, **kw):
+    """Forward + backward through backend module C (oracle_C or the product _C).  Returns (fwd dict, grads dict).
+    `binning` (product only; the oracle always bins like the reference): 1 = exact ellipse lists (the
+    product's default), 0 = the reference's bounding-square lists."""
+    F = sc.F
+    fwd, a = run_forward(C, sc, dev, tile, mode, binning, **kw)
+    radii, geom, R, binb, img = fwd["radii"], fwd["geom"], fwd["R"], fwd["binning"], fwd["img"]
     dc, dl, dd = sc.cotangents(seed)
     mv = (lambda t: None if t is None else t.to(dev)) if dev is not None else (lambda t: t)
     off = 1 if F > 0 else 0
@@ -174,6 +182,40 @@ def ordered_backward(hip, sc, fwd, seed, tile, mode, dev=None, cotangents=None, 
 def same_bits(a, b):
     a, b = a.detach().cpu().float().reshape(-1), b.detach().cpu().float().reshape(-1)
     return bool(((a == b) | (a.isnan() & b.isnan())).all())
+
+
+def tile_pairs(hip, f, sc, tile):
+    """(tile * P + Gaussian) per sorted list position, the per-position blend flags, and the positions."""
+    W, H, F, R = sc.camera.width, sc.camera.height, sc.F, f["R"]
+    hip.TILE = tile
+    pl = hip.state_field("binning", f["binning"], "point_list", R=R, F=F, dtype=torch.int32, count=R).long()
+    src = hip.state_field("binning", f["binning"], "src", R=R, F=F, dtype=torch.int32, count=R).long()
+    fl = hip.state_field("binning", f["binning"], "flags", R=R, F=F, dtype=torch.uint8, count=R)
+    nt = ((W + tile - 1) // tile) * ((H + tile - 1) // tile)
+    rg = hip.state_field("image", f["img"], "ranges", W=W, H=H, dtype=torch.int32, count=2 * nt).view(-1, 2).long()
+    lens = rg[:, 1] - rg[:, 0]
+    assert int(lens.sum()) == R
+    tile_of = torch.repeat_interleave(torch.arange(nt, device=pl.device), lens)
+    # list positions of tile t are ranges[t]; walk them tile by tile
+    starts = torch.repeat_interleave(rg[:, 0], lens)
+    pos = starts + (torch.arange(R, device=pl.device) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens))
+    return tile_of * max(sc.P, 1) + pl[pos], fl[src[pos]], pos
+
+
+def assert_backward_criteria(hip, sc, fg, gg, go, seed, tile, mode, where, rtol=1e-4):
+    """The backward's criteria on one scene (tests/test_gpu_bwd_batches.py, tests/test_gpu_fwd_batches.py): every gradient
+    within `rtol` of its tensor's largest magnitude of the oracle's, the composite-level tensors per element (worst element
+    within 2e-4), the ordered kernel equal to the oracle, and the fast kernel within 64 x 2^-24 x condition of it."""
+    for k in go:
+        if go[k].numel():
+            r, e = rel_err(gg[k], go[k])
+            assert r <= rtol, f"{where}: {k}: rel {r:.2e} abs {e:.2e}"
+            if k in COMPOSITE_KEYS:
+                assert_elementwise(gg[k], go[k], f"{where}:{k}", 2e-4)
+    gord = ordered_backward(hip, sc, fg, seed, tile, mode)
+    assert_ordered_equals_oracle(go, gord, where=f"{where}:ordered:")
+    gcond = ordered_backward(hip, sc, fg, seed, tile, mode, condition=True)
+    assert_rounding_only(gg, gord, gcond, k_bound=64.0, name=f"{where}:")
 
 
 def assert_ordered_equals_oracle(go, gord, where=""):

@@ -12,32 +12,18 @@ import os
 import pytest
 import torch
 
+import fwd_batch_scenes as fs
 from online_lang_splatting_amd import _abi
 from online_lang_splatting_amd.scene import default_camera, make_scene
 from parity_common import (ELEM_MIN_FRACTION, assert_elementwise, assert_ordered_equals_oracle, assert_rounding_only,
-                           fwd_args, ordered_backward, rel_err, run_backend)
+                           fwd_args, ordered_backward, rel_err, run_backend, tile_pairs)
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
 DEV = "cuda:0"
 
 
-def _tile_pairs(hip, f, sc, tile):
-    """(tile * P + Gaussian) per sorted list position, and the per-position blend flags."""
-    W, H, F, R = sc.camera.width, sc.camera.height, sc.F, f["R"]
-    hip.TILE = tile
-    pl = hip.state_field("binning", f["binning"], "point_list", R=R, F=F, dtype=torch.int32, count=R).long()
-    src = hip.state_field("binning", f["binning"], "src", R=R, F=F, dtype=torch.int32, count=R).long()
-    fl = hip.state_field("binning", f["binning"], "flags", R=R, F=F, dtype=torch.uint8, count=R)
-    nt = ((W + tile - 1) // tile) * ((H + tile - 1) // tile)
-    rg = hip.state_field("image", f["img"], "ranges", W=W, H=H, dtype=torch.int32, count=2 * nt).view(-1, 2).long()
-    lens = rg[:, 1] - rg[:, 0]
-    assert int(lens.sum()) == R
-    tile_of = torch.repeat_interleave(torch.arange(nt, device=pl.device), lens)
-    # list positions of tile t are ranges[t]; walk them tile by tile
-    starts = torch.repeat_interleave(rg[:, 0], lens)
-    pos = starts + (torch.arange(R, device=pl.device) - torch.repeat_interleave(torch.cumsum(lens, 0) - lens, lens))
-    return tile_of * max(sc.P, 1) + pl[pos], fl[src[pos]], pos
+_tile_pairs = tile_pairs
 
 
 COMPOSITE_GRADS = ("dL_dmeans2D", "dL_dconic", "dL_dopacity", "dL_dcolors", "dL_dlanguage", "dL_ddepths")
@@ -48,7 +34,7 @@ COMPOSITE_KEYS = COMPOSITE_GRADS
 
 def _check(hip, oracle, sc, seed=0, tile=15, mode=0, grad_keys=None, elementwise=False, worst_bound=1e-2, log=None,
            chain=True, chain_worst_bound=1e-3, chain_min_fraction=ELEM_MIN_FRACTION, composite_worst_bound=2e-4,
-           chain_exact=True, ordered=True, rounding_k_bound=64.0, **kw):
+           chain_exact=True, ordered=True, rounding_k_bound=64.0, check_flags=False, **kw):
     """Oracle vs the HIP library in both binning modes.
     RECT: images, counters AND the instance lists equal the reference's bit for bit.
     ELLIPSE (the product's default): identical images / radii / n_touched / final_T, gradients to RTOL,
@@ -72,8 +58,17 @@ def _check(hip, oracle, sc, seed=0, tile=15, mode=0, grad_keys=None, elementwise
     and the product's fast kernel must differ from it BY ROUNDING ONLY: every element within rounding_k_bound x 2^-24 x the
     element's condition (the same sums over magnitudes; measured K <= 13 on the suite's scenes, <= 30 at the full configs).
     With the chain exact on identical inputs, this closes the backward: what is not an equality is bounded per element by
-    the arithmetic's own rounding."""
-    fo, go = run_backend(oracle, sc, None, seed, tile, mode, **kw)
+    the arithmetic's own rounding.
+    check_flags: the oracle records which pixels blended every list entry (oracle_set_record: 32 bytes per instance), and the
+    liveness the forward leaves for the backward - flags[], tile_work[2][tiles], blended[P] - must equal what that record says
+    (tests/fwd_batch_scenes.py: expected_flags, expected_tile_work, expected_blended) on the reference's lists."""
+    if check_flags:
+        oracle.lib().oracle_set_record(1)
+    try:
+        fo, go = run_backend(oracle, sc, None, seed, tile, mode, **kw)
+    finally:
+        if check_flags:
+            oracle.lib().oracle_set_record(0)
     assert grad_keys is None or all(k in go for k in grad_keys), [k for k in grad_keys if k not in go]
     fr, gr = run_backend(hip, sc, torch.device(DEV), seed, tile, mode, binning=_abi.BINNING_RECT, **kw)
     fg, gg = run_backend(hip, sc, torch.device(DEV), seed, tile, mode, binning=_abi.BINNING_ELLIPSE, **kw)
@@ -142,7 +137,7 @@ def _check(hip, oracle, sc, seed=0, tile=15, mode=0, grad_keys=None, elementwise
         nc = hip.state_field("image", fr["img"], "n_contrib", W=W, H=H, dtype=torch.int32, count=W * H)
         assert torch.equal(nc.cpu(), oracle.get_field(fo["geom"], "n_contrib"))
         # exact lists: an order-preserving sub-list of the reference's that keeps every blending instance
-        kr, flr, _ = _tile_pairs(hip, fr, sc, tile)
+        kr, flr, posr = _tile_pairs(hip, fr, sc, tile)
         if fg["R"] > 0:
             ke, fle, _ = _tile_pairs(hip, fg, sc, tile)
             keep = torch.isin(kr, ke)
@@ -151,6 +146,15 @@ def _check(hip, oracle, sc, seed=0, tile=15, mode=0, grad_keys=None, elementwise
         else:
             keep = torch.zeros_like(kr, dtype=torch.bool)
         assert int((flr[~keep] != 0).sum()) == 0
+        if check_flags:
+            want = fs.expected_flags(oracle.get_field(fo["geom"], "contrib_mask"), tile)
+            assert torch.equal(flr.cpu(), want[posr.cpu()]), "flags differ from the oracle's record of who blended what"
+            rg = oracle.get_field(fo["geom"], "ranges").view(-1, 2)
+            nt = rg.shape[0]
+            tw = hip.state_field("image", fr["img"], "tile_work", W=W, H=H, dtype=torch.int32, count=2 * nt).cpu().view(2, nt)
+            assert torch.equal(tw.long(), fs.expected_tile_work(want, rg)), "tile_work"
+            bl = hip.state_field("geometry", fr["geom"], "blended", P=P, F=F, dtype=torch.uint8, count=P).cpu()
+            assert torch.equal(bl, fs.expected_blended(want, oracle.get_field(fo["geom"], "point_list"), P)), "blended"
     oracle.release(fo["geom"])
     return fg, gg
 
@@ -291,7 +295,8 @@ def test_exact_binning_never_drops_a_blending_instance(hip, seed):
 @pytest.mark.parametrize("seed", range(int(os.environ.get("OLSR_PARITY_SEEDS", "10"))))
 def test_random_scenes_against_the_oracle(hip, oracle, seed):
     """Randomised full parity (both binning modes, lists, images, gradients) over F, tile, backward mode, SH
-    degree, camera pose, background, scale and opacity distributions."""
+    degree, camera pose, background, scale and opacity distributions.  The oracle records which pixels blended every list
+    entry, and the liveness the forward hands the backward (flags, tile_work, blended) is held to that record."""
     g = torch.Generator().manual_seed(5000 + seed)
     r = lambda: float(torch.rand(1, generator=g))
     F = [0, 3, 15, 16, 32][seed % 5]
@@ -306,7 +311,8 @@ def test_random_scenes_against_the_oracle(hip, oracle, seed):
     sc.opacities[:] = torch.sigmoid(torch.randn(sc.P, 1, generator=g) * 2.5 - 0.5).reshape(sc.opacities.shape)
     # pose / 3-D gradients of strongly anisotropic splats are ill-conditioned (see the needle test): compare the
     # composite-level gradients for every scene and the full chain where the scene is tame
-    _check(hip, oracle, sc, seed=seed, tile=tile, mode=mode, scale_modifier=0.6 + r(), grad_keys=COMPOSITE_GRADS)
+    _check(hip, oracle, sc, seed=seed, tile=tile, mode=mode, scale_modifier=0.6 + r(), grad_keys=COMPOSITE_GRADS,
+           check_flags=True)
 
 
 def test_transparent_scene_walks_whole_lists(hip, oracle):
