@@ -192,7 +192,13 @@ typedef struct olsr_scene {
  * simply pays for both); on exit the array holds this frame's order.  Sort keys are defined for all P Gaussians (the view-space
  * depth also for Gaussians outside the frustum, a monotone function of it behind the near plane), so that the order is a
  * property of the pose and not of what is visible.  olsr_forward (the synchronising entry) ignores the field, and so do
- * sorts that take the multi-kernel passes (more than 67 M Gaussians). */
+ * sorts that take the multi-kernel passes (more than 67 M Gaussians).
+ * An array holds the order of exactly ONE frame in flight: a forward reads and rewrites it from its repair to its emission,
+ * so two frames that may overlap on the device (different streams, OLSR_FLAG_FRAMES_IN_FLIGHT lanes) need an array each —
+ * sharing one gives the reader an order that nothing has proved.  The emission reads the array with 16-byte loads: allocate it
+ * 16-byte aligned.  A frame that contains a Gaussian whose sort key is 0xFFFFFFFF (view-depth bits all ones: a NaN with every
+ * payload bit set, e.g. positions in memory filled with 0xFF) ALWAYS takes the radix passes: that key is the repair's padding,
+ * and a proof that cannot tell a Gaussian from padding is not accepted. */
 
 /* Per-tile depth cut-offs (round 4; an opt-in for SEQUENCES of nearly identical views: the ~100 tracking iterations of a
  * frame).  The forward composite reads a tile's depth-sorted list only until every pixel of the tile is saturated — at config 3

@@ -16,9 +16,9 @@
 // sorted pairs must ascend strictly, and its last pair must be smaller than the smallest pair of the next window, which it
 // reads from phase A's output (two sorted half-windows: two loads).  All P adjacent pairs strictly ascending means sorted AND
 // no index twice, i.e. a permutation of [0, P) in the reference's order.  Anything else — a Gaussian that moved further, a
-// carry array that holds zeros, garbage or the order of another scene — raises `miss`, and the radix passes that are
-// enqueued behind these two launches run instead of returning at once (k_sort.hip: run_if).  The result never depends on the
-// carried array.
+// carry array that holds zeros, garbage or the order of another scene, a real key equal to the padding's (oc_pad_high) —
+// raises `miss`, and the radix passes that are enqueued behind these two launches run instead of returning at once
+// (k_sort.hip: run_if).  The result never depends on the carried array.
 //
 // Windows are independent: no ticket, no published counts, no look-back — the two launches are bound by one gather of the
 // keys and a handful of LDS round trips per element.  The merge sort is the rank form (an element's place in the merged run
@@ -114,8 +114,13 @@ __device__ __forceinline__ u64* oc_window_sort(u64* a, u64* b) {
   return a;
 }
 
-// pairs that stand in for ranks outside [0, P): below every real pair (real keys are >= 1, k_preprocess.hip) / above them,
-// distinct, and already in order
+// pairs that stand in for ranks outside [0, P): distinct, already in order, and below every real pair (real keys are >= 1,
+// k_preprocess.hip) / above every real pair of a repair that stays a hit.  A real key CAN equal the high pads' 0xFFFFFFFF —
+// preprocess writes the bits of the view depth, and a NaN with all bits set is one —, and such a pair (0xFFFFFFFF, g >= l)
+// would sort behind a pad, which phase A would then store as if it were rank l's Gaussian: a duplicate index between
+// strictly ascending pairs.  So phase A raises `miss` for every real rank whose key is 0xFFFFFFFF (OC_KEY_PAD below): in a
+// frame that stays a hit the pads are the only holders of that key, and the argument in the header holds.
+constexpr u32 OC_KEY_PAD = 0xFFFFFFFFu;
 __device__ __forceinline__ u64 oc_pad_low(int l) { return (u64)(u32)l; }
 __device__ __forceinline__ u64 oc_pad_high(int l) { return 0xFFFFFFFF00000000ull | (u64)(u32)l; }
 
@@ -136,8 +141,9 @@ __global__ __launch_bounds__(T) void order_repair_a_kernel(int P, const u32* __r
     if (i < P) {
       const u32 g = carry[i];
       const bool ok = g < (u32)P;  // (an array that never held an order: index nothing with it)
-      bad |= !ok;
-      c = ((u64)(ok ? keys[g] : 0xFFFFFFFFu) << 32) | (u64)g;
+      const u32 key = ok ? keys[g] : OC_KEY_PAD;
+      bad |= key == OC_KEY_PAD;  // an index out of range, or a real key that the high pads do not lie above
+      c = ((u64)key << 32) | (u64)g;
     }
     s0[l] = c;
   }
