@@ -41,7 +41,6 @@ UNITS = [
     ("k_lang_ae.hip", "k_lang_ae.o", []),
     ("k_lang_query.hip", "k_lang_query.o", []),
     ("k_lang_encoder.hip", "k_lang_encoder.o", []),
-    ("k_lang_single_stage.hip", "k_lang_single_stage.o", []),
     ("k_hr_net.hip", "k_hr_net.o", []),
     ("k_knn.hip", "k_knn.o", []),
     ("k_adam.hip", "k_adam.o", []),

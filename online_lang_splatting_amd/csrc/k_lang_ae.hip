@@ -23,7 +23,7 @@
 // -ffp-contract=off holds for this unit like the others; every fma is written out.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
-#include "olsr_lang_ae_device.h"  // the parameter layout AE_W1 .. AE_B4, ae_linear, ae_norm, ae_encode, ae_decode, ae_store_codes
+#include "olsr_lang_ae_device.h"  // the parameter layout AE_W1 .. AE_B4, ae_encode, ae_decode, ae_store_codes
 
 namespace olsr {
 
@@ -138,7 +138,7 @@ __global__ __launch_bounds__(AE_ROWS) void lang_ae_grad_kernel(int N, int vec4, 
   float dr[AE_IN];
   float l1 = 0.f, cosv = 0.f;
   {
-    const float nr_raw = ae_norm<AE_IN>(r), nx_raw = ae_norm<AE_IN>(x);
+    const float nr_raw = lane_norm<AE_IN>(r), nx_raw = lane_norm<AE_IN>(x);
     const float nr = fmaxf(nr_raw, 1e-8f), nx = fmaxf(nx_raw, 1e-8f);
     float rn[AE_IN], xn[AE_IN];
 #pragma unroll

@@ -15,6 +15,15 @@
 //                                are in the B-operand layout of the next product already (neuron on the register, pixel on the
 //                                lane), so the K dot products with the phrase rows are four more MFMAs per 16 x 16 tile and the
 //                                squared norm is a per-lane sum in double.  The 768-wide row is never stored anywhere.
+//   ss_query_sims_kernel         stage A of the single-stage chain (language.single_stage_ae: True, include/
+//                                olsr_single_stage.h; eval/evaluate_langslam.py:266-273, model.py:58-62): no online decoder, the
+//                                general one is 15 -> 24 -> 48 -> 96 -> 192 -> 384 -> 384 -> 768.  The codes go through 15 -> 24 ->
+//                                48 per pixel on the vector unit (decoder.0.weight [24,15] has no 16-byte aligned rows: scalar
+//                                loads, bias-first k-ascending fmaf chains, twelve of the 48 neurons per wave), then 48 -> 96 ->
+//                                192 -> 384 -> 384 out of the image and the same tail.  Its ReLU keeps a NaN
+//                                (DENSE_EPI_RELU_NAN), as torch's does: a NaN code pixel gives NaN similarities for that pixel
+//                                only (a pixel is a column of every product).  lang_query_sims_kernel's fmaxf differs there and
+//                                stays as it is.
 //   lang_query_relevancy_kernel  stage B, per output pixel: bilinear up-sampling of the similarity planes, the pairwise softmax
 //                                against the negatives, the label argmax.
 //   lang_query_smooth_kernel     the 30 x 30 mean (filter2D defaults: correlation, anchor (15,15), reflect-101) separable out of
@@ -27,20 +36,20 @@
 #include "olsr_dense.h"
 #include "olsr_lang_ae_device.h"
 
+#include <type_traits>
+
 namespace olsr {
 
 constexpr int LQ_C = AE_C, LQ_IN = AE_IN;  // the online decoder's ends (olsr_lang_ae_device.h)
-
-constexpr int LQ_M = 64;        // pixels per workgroup
-constexpr int LQ_WAVES = 4;     // 256 threads
-constexpr int LQ_S = 516;       // LDS floats per pixel: 512 + 4 (16 pixels' float4 reads of one k column hit 64 different banks)
 constexpr int LQ_FEAT = OLSR_LANG_QUERY_FEATURE_DIM;
-// the general decoder's layers in the flat array (state_dict order: weight [out,in], bias [out] per layer)
-constexpr int LQ_D0 = 32, LQ_D1 = 192, LQ_D2 = 256, LQ_D3 = 384, LQ_D4 = 512, LQ_D5 = LQ_FEAT;
-constexpr int LQ_OW1 = 0, LQ_OB1 = LQ_OW1 + LQ_D1 * LQ_D0, LQ_OW2 = LQ_OB1 + LQ_D1, LQ_OB2 = LQ_OW2 + LQ_D2 * LQ_D1,
-              LQ_OW3 = LQ_OB2 + LQ_D2, LQ_OB3 = LQ_OW3 + LQ_D3 * LQ_D2, LQ_OW4 = LQ_OB3 + LQ_D3, LQ_OB4 = LQ_OW4 + LQ_D4 * LQ_D3,
-              LQ_OW5 = LQ_OB4 + LQ_D4, LQ_OB5 = LQ_OW5 + LQ_D5 * LQ_D4;
-static_assert(LQ_OB5 + LQ_D5 == OLSR_LANG_QUERY_DECODER_PARAMS, "flat decoder layout");
+// the general decoders' layers in the flat arrays (state_dict order: weight [out,in], bias [out] per layer)
+constexpr int LQ_D[] = {LQ_IN, 192, 256, 384, 512, LQ_FEAT};
+constexpr int SQ_D[] = {LQ_C, 24, 48, 96, 192, 384, 384, LQ_FEAT};
+constexpr auto LQ = flat_mlp(LQ_D, false);
+constexpr auto SQ = flat_mlp(SQ_D, false);
+static_assert(LQ.total == OLSR_LANG_QUERY_DECODER_PARAMS, "flat decoder layout");
+static_assert(SQ.total == OLSR_SS_DECODER_PARAMS, "flat decoder layout");
+static_assert(flat_mlp_aligned(LQ) && flat_mlp_aligned(SQ, 2), "16-byte loads of every weight and bias of the matrix layers");
 
 // F.interpolate(mode="bilinear", align_corners=False) along one axis: the two taps and their weights (ATen UpSample.h:
 // area_pixel_compute_source_index and guard_index_and_lambda, in float as for a float32 tensor)
@@ -72,109 +81,99 @@ struct LqGeom {
 
 // ---- stage A --------------------------------------------------------------------------------------------------------------
 
-// one hidden layer in place: X[64][KIN] -> relu(W X^T + b)^T = X[64][NOUT], a quarter of the neurons per wave
-template <int KIN, int NOUT>
-__device__ __forceinline__ void lq_hidden(float* __restrict__ X, const float* __restrict__ W, const float* __restrict__ bias,
-                                          int wave, int li, int q) {
-  dense_layer<KIN, NOUT, LQ_WAVES, LQ_WAVES, LQ_S, DENSE_EPI_RELU>(X, W, bias, nullptr, nullptr, wave, li, q);
+// a pixel's 15 codes out of the channel-major map, straight or resampled to the decode size
+__device__ __forceinline__ void lq_fetch_codes(const float* __restrict__ codes, const LqGeom& g, int N, int row, float (&c)[LQ_C]) {
+  if (g.resample_codes) {
+    const int oy = row / g.dec_w, ox = row - oy * g.dec_w;
+    const LqTaps ty = lq_taps(oy, g.in_h, g.code_sy), tx = lq_taps(ox, g.in_w, g.code_sx);
+#pragma unroll
+    for (int k = 0; k < LQ_C; ++k) c[k] = lq_sample(codes + (size_t)k * g.in_w * g.in_h, g.in_w, ty, tx);
+  } else {
+#pragma unroll
+    for (int k = 0; k < LQ_C; ++k) c[k] = codes[(size_t)k * N + row];
+  }
+}
+
+// hidden layer I (from 0) of the decoder D in place: X[64][KIN] -> relu(W X^T + b)^T = X[64][NOUT], the first WUSED waves
+// share the neurons
+template <const auto& D, int I, int WUSED, int EPI>
+__device__ __forceinline__ void lq_hidden(float* __restrict__ X, const float* __restrict__ dec, int wave, int li, int q) {
+  dense_layer<D.d[I], D.d[I + 1], LANG_WAVES, WUSED, LANG_S, EPI>(X, dec + D.w[I], dec + D.b[I], nullptr, nullptr, wave, li, q);
 }
 
 // KT: 16-row tiles of phrases (K <= 16 KT)
 template <int KT>
-__global__ __launch_bounds__(LQ_M * LQ_WAVES) void lang_query_sims_kernel(int N, LqGeom g, int K,
-                                                                                 const float* __restrict__ codes,
-                                                                                 const float* __restrict__ online,
-                                                                                 const float* __restrict__ dec,
-                                                                                 const float* __restrict__ phrases,
-                                                                                 float* __restrict__ sims) {
-  extern __shared__ __attribute__((aligned(16))) float X[];  // [64][LQ_S]; afterwards the waves' partial dots and norms
+__global__ __launch_bounds__(LANG_M * LANG_WAVES) void lang_query_sims_kernel(int N, LqGeom g, int K,
+                                                                               const float* __restrict__ codes,
+                                                                               const float* __restrict__ online,
+                                                                               const float* __restrict__ dec,
+                                                                               const float* __restrict__ phrases,
+                                                                               float* __restrict__ sims) {
+  extern __shared__ __attribute__((aligned(16))) float X[];  // [64][LANG_S]; afterwards the waves' partial dots and norms
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, q = lane >> 4;
-  const int row0 = blockIdx.x * LQ_M;
+  const int row0 = blockIdx.x * LANG_M;
   // the pixel's codes (resampled to the decode size if asked) -> online decoder -> X[pixel][0..31]
-  if (tid < LQ_M) {
+  if (tid < LANG_M) {
     const int row = row0 + tid;
     float c[LQ_C];
     if (row < N) {
-      if (g.resample_codes) {
-        const int oy = row / g.dec_w, ox = row - oy * g.dec_w;
-        const LqTaps ty = lq_taps(oy, g.in_h, g.code_sy), tx = lq_taps(ox, g.in_w, g.code_sx);
-#pragma unroll
-        for (int k = 0; k < LQ_C; ++k) c[k] = lq_sample(codes + (size_t)k * g.in_w * g.in_h, g.in_w, ty, tx);
-      } else {
-#pragma unroll
-        for (int k = 0; k < LQ_C; ++k) c[k] = codes[(size_t)k * N + row];
-      }
+      lq_fetch_codes(codes, g, N, row, c);
       float h2[AE_H], r[LQ_IN];
       ae_decode(online, c, h2, r);  // r = y / |y|, as olsr_lang_ae_decode has it
 #pragma unroll
-      for (int k = 0; k < LQ_IN; ++k) X[tid * LQ_S + k] = r[k];
+      for (int k = 0; k < LQ_IN; ++k) X[tid * LANG_S + k] = r[k];
     } else {
 #pragma unroll
-      for (int k = 0; k < LQ_IN; ++k) X[tid * LQ_S + k] = 0.f;
+      for (int k = 0; k < LQ_IN; ++k) X[tid * LANG_S + k] = 0.f;
     }
   }
   __syncthreads();
-  lq_hidden<LQ_D0, LQ_D1>(X, dec + LQ_OW1, dec + LQ_OB1, wave, li, q);
-  lq_hidden<LQ_D1, LQ_D2>(X, dec + LQ_OW2, dec + LQ_OB2, wave, li, q);
-  lq_hidden<LQ_D2, LQ_D3>(X, dec + LQ_OW3, dec + LQ_OB3, wave, li, q);
-  lq_hidden<LQ_D3, LQ_D4>(X, dec + LQ_OW4, dec + LQ_OB4, wave, li, q);
-  // the last layer in blocks of 4 x 16 neurons per wave, consumed as they arrive
-  constexpr int NT = 4, CHUNKS = LQ_D5 / (16 * NT * LQ_WAVES);
-  static_assert(CHUNKS * 16 * NT * LQ_WAVES == LQ_D5, "blocks of 64 neurons per wave");
-  f32x4 sacc[KT][4];  // tile (phrases 16 kt ..) x (pixels 16 pt ..): lane (li, q) holds phrases 16 kt + 4 q + {0..3} of pixel 16 pt + li
-  double nrm[4];      // this lane's part of |y|^2 of pixel 16 pt + li
+  lq_hidden<LQ, 0, 4, DENSE_EPI_RELU>(X, dec, wave, li, q);
+  lq_hidden<LQ, 1, 4, DENSE_EPI_RELU>(X, dec, wave, li, q);
+  lq_hidden<LQ, 2, 4, DENSE_EPI_RELU>(X, dec, wave, li, q);
+  lq_hidden<LQ, 3, 4, DENSE_EPI_RELU>(X, dec, wave, li, q);
+  dense_phrase_sims<LQ.d[4], LQ_FEAT, KT, LANG_WAVES, LANG_S>(X, dec + LQ.w[4], dec + LQ.b[4], phrases, K, N, row0, sims, wave, li,
+                                                              q, tid);
+}
+
+template <int KT>
+__global__ __launch_bounds__(LANG_M * LANG_WAVES) void ss_query_sims_kernel(int N, LqGeom g, int K, const float* __restrict__ codes,
+                                                                             const float* __restrict__ dec,
+                                                                             const float* __restrict__ phrases,
+                                                                             float* __restrict__ sims) {
+  extern __shared__ __attribute__((aligned(16))) float X[];  // [64][LANG_S]; afterwards the waves' partial dots and norms
+  const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63, li = lane & 15, q = lane >> 4;
+  const int row0 = blockIdx.x * LANG_M;
+  // the pixel's codes (resampled to the decode size if asked) -> 15 -> 24 -> 48; wave w keeps neurons 12 w .. 12 w + 11 of the
+  // 48 (the 24 are computed by each of the four: a neuron's chain is the same whoever computes it) -> X[pixel][0..47]
+  {
+    constexpr int D1 = SQ.d[1], PER = SQ.d[2] / LANG_WAVES;
+    const int nb = __builtin_amdgcn_readfirstlane(wave) * PER;
+    const int row = row0 + lane;
+    float h2[PER];
+    if (row < N) {
+      float c[LQ_C], h1[D1];
+      lq_fetch_codes(codes, g, N, row, c);
+      lane_linear<D1, LQ_C>(dec + SQ.w[0], dec + SQ.b[0], c, h1);
 #pragma unroll
-  for (int pt = 0; pt < 4; ++pt) {
-    nrm[pt] = 0.0;
+      for (int k = 0; k < D1; ++k) h1[k] = relu_keep_nan(h1[k]);
+      lane_linear<PER, D1>(dec + SQ.w[1] + nb * D1, dec + SQ.b[1] + nb, h1, h2);
 #pragma unroll
-    for (int kt = 0; kt < KT; ++kt) sacc[kt][pt] = f32x4{0.f, 0.f, 0.f, 0.f};
-  }
-  for (int ch = 0; ch < CHUNKS; ++ch) {
-    const int n0 = (wave * CHUNKS + ch) * NT * 16;
-    f32x4 acc[NT][4];
-    dense_gemm<LQ_D4, NT, LQ_S>(X, dec + LQ_OW5, dec + LQ_OB5, n0, li, q, acc);
+      for (int k = 0; k < PER; ++k) h2[k] = relu_keep_nan(h2[k]);
+    } else {
 #pragma unroll
-    for (int t = 0; t < NT; ++t) {
-#pragma unroll
-      for (int pt = 0; pt < 4; ++pt)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) nrm[pt] = fma((double)acc[t][pt][r], (double)acc[t][pt][r], nrm[pt]);
-#pragma unroll
-      for (int kt = 0; kt < KT; ++kt) {
-        // A[i = li][k = q] = phrase 16 kt + li at neuron n0 + 16 t + 4 q + r; B[k = q][col = li] = acc[t][pt][r] as it lies
-        const int ph = kt * 16 + li;
-        f32x4 pf = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ph < K) pf = *reinterpret_cast<const f32x4*>(phrases + (size_t)ph * LQ_FEAT + n0 + 16 * t + 4 * q);
-#pragma unroll
-        for (int r = 0; r < 4; ++r)
-#pragma unroll
-          for (int pt = 0; pt < 4; ++pt)
-            sacc[kt][pt] = __builtin_amdgcn_mfma_f32_16x16x4f32(pf[r], acc[t][pt][r], sacc[kt][pt], 0, 0, 0);
-      }
+      for (int k = 0; k < PER; ++k) h2[k] = 0.f;
     }
-  }
-  __syncthreads();  // the activations are no longer read
-  float* dots = X;                                                            // [wave][16 KT phrases][64 pixels]
-  double* norms = reinterpret_cast<double*>(X + LQ_WAVES * 16 * KT * LQ_M);  // [wave][q][64 pixels]
 #pragma unroll
-  for (int pt = 0; pt < 4; ++pt) {
-    norms[(wave * 4 + q) * LQ_M + pt * 16 + li] = nrm[pt];
-#pragma unroll
-    for (int kt = 0; kt < KT; ++kt)
-#pragma unroll
-      for (int r = 0; r < 4; ++r) dots[(wave * 16 * KT + kt * 16 + 4 * q + r) * LQ_M + pt * 16 + li] = sacc[kt][pt][r];
+    for (int k = 0; k < PER; ++k) X[lane * LANG_S + nb + k] = h2[k];
   }
   __syncthreads();
-  for (int e = tid; e < K * LQ_M; e += LQ_M * LQ_WAVES) {
-    const int ph = e / LQ_M, px = e - ph * LQ_M;
-    if (row0 + px >= N) continue;
-    double s = 0.0;
-#pragma unroll
-    for (int k = 0; k < LQ_WAVES * 4; ++k) s += norms[k * LQ_M + px];
-    const float d = (dots[(0 * 16 * KT + ph) * LQ_M + px] + dots[(1 * 16 * KT + ph) * LQ_M + px]) +
-                    (dots[(2 * 16 * KT + ph) * LQ_M + px] + dots[(3 * 16 * KT + ph) * LQ_M + px]);
-    sims[(size_t)ph * N + row0 + px] = d / (float)sqrt(s);
-  }
+  lq_hidden<SQ, 2, 3, DENSE_EPI_RELU_NAN>(X, dec, wave, li, q);
+  lq_hidden<SQ, 3, 4, DENSE_EPI_RELU_NAN>(X, dec, wave, li, q);
+  lq_hidden<SQ, 4, 4, DENSE_EPI_RELU_NAN>(X, dec, wave, li, q);
+  lq_hidden<SQ, 5, 4, DENSE_EPI_RELU_NAN>(X, dec, wave, li, q);
+  dense_phrase_sims<SQ.d[6], LQ_FEAT, KT, LANG_WAVES, LANG_S>(X, dec + SQ.w[6], dec + SQ.b[6], phrases, K, N, row0, sims, wave, li,
+                                                              q, tid);
 }
 
 // ---- stage B --------------------------------------------------------------------------------------------------------------
@@ -349,27 +348,30 @@ size_t lang_query_scratch_bytes(const olsr_lang_query_params& p) {
   return n_pos * lq_tiles(p.out_width, p.out_height) * sizeof(LqPartial) + 256;
 }
 
-template <int KT>
-static hipError_t lq_launch_sims(int N, const LqGeom& g, int K, const float* codes, const float* online, const float* dec,
-                                 const float* phrases, float* sims, hipStream_t st) {
-  constexpr size_t act = (size_t)LQ_M * LQ_S * sizeof(float);
-  constexpr size_t red = (size_t)LQ_WAVES * 16 * KT * LQ_M * sizeof(float) + (size_t)LQ_WAVES * 4 * LQ_M * sizeof(double);
-  static_assert(red <= act && act <= 160 * 1024, "one LDS image per workgroup");
-  // more than 64 KiB of dynamic LDS has to be asked for (a host-side attribute of the current device's function: no launch)
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&lang_query_sims_kernel<KT>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)act);
-  if (e != hipSuccess) return e;
-  lang_query_sims_kernel<KT><<<(N + LQ_M - 1) / LQ_M, LQ_M * LQ_WAVES, act, st>>>(N, g, K, codes, online, dec, phrases, sims);
-  return hipSuccess;
+// f(KT) for the number of 16-row phrase tiles that K phrases need
+template <typename F>
+static hipError_t lq_for_phrase_tiles(int K, F f) {
+  if (K <= 16) return f(std::integral_constant<int, 1>());
+  if (K <= 32) return f(std::integral_constant<int, 2>());
+  return f(std::integral_constant<int, 4>());
 }
 
 hipError_t launch_lang_query_sims(const olsr_lang_query_params& p, const float* codes, const float* online, const float* dec,
                                   const float* phrases, float* sims, hipStream_t st) {
   const LqGeom g = lq_geom(p);
   const int N = p.dec_width * p.dec_height;
-  if (p.K <= 16) return lq_launch_sims<1>(N, g, p.K, codes, online, dec, phrases, sims, st);
-  if (p.K <= 32) return lq_launch_sims<2>(N, g, p.K, codes, online, dec, phrases, sims, st);
-  return lq_launch_sims<4>(N, g, p.K, codes, online, dec, phrases, sims, st);
+  return lq_for_phrase_tiles(p.K, [&](auto kt) {
+    return dense_launch(&lang_query_sims_kernel<kt()>, N, LANG_ACT_BYTES, st, N, g, p.K, codes, online, dec, phrases, sims);
+  });
+}
+
+hipError_t launch_ss_query_sims(const olsr_lang_query_params& p, const float* codes, const float* dec, const float* phrases,
+                                float* sims, hipStream_t st) {
+  const LqGeom g = lq_geom(p);
+  const int N = p.dec_width * p.dec_height;
+  return lq_for_phrase_tiles(p.K, [&](auto kt) {
+    return dense_launch(&ss_query_sims_kernel<kt()>, N, LANG_ACT_BYTES, st, N, g, p.K, codes, dec, phrases, sims);
+  });
 }
 
 void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* sims, float* relevancy, float* smoothed,

@@ -401,22 +401,32 @@ int olsr_lang_query_relevancy(const olsr_lang_query_params* p, const float* sims
   return launch_check("lang_query_relevancy");
 }
 
+// what is wrong with a call of one of the two encoders apart from its width list, or nullptr; missing: the entry's own
+// complaint about its arrays (or nullptr), which goes between the sizes and the alignment
+extern "C++" template <typename P>
+static const char* lang_encoder_call_error(const P* p, int32_t N, const float* encoder_params, const char* missing) {
+  if (N < 1) return "N must be positive";
+  if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS) return "unknown input layout";
+  if (!lang_ae_layout_ok(p->code_layout)) return "unknown code layout";
+  if (p->in_layout == OLSR_LANG_ENCODER_IN_CHANNELS && p->plane_stride < (int64_t)N)
+    return "plane_stride must be at least N in the channel layout";
+  if (!(p->bn_eps > 0.0)) return "bn_eps must be positive";
+  if (missing) return missing;
+  if ((uintptr_t)encoder_params & 15u) return "encoder_params must be 16-byte aligned";
+  return nullptr;
+}
+
 int olsr_lang_encoder_encode(const olsr_lang_encoder_params* p, int32_t N, const float* features768, const float* encoder_params,
                              const float* online_params, float* features32, float* codes, void* hip_stream) {
   if (!p) return fail(OLSR_ERR_ARG, "lang_encoder_encode: the parameter struct is NULL");
   if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_QUERY_FEATURE_DIM, 512, 256, 128, 64, OLSR_LANG_AE_IN}))
     return fail(OLSR_ERR_ARG, "lang_encoder_encode: this build encodes the layer widths {768, 512, 256, 128, 64, 32} only");
-  if (N < 1) return fail(OLSR_ERR_ARG, "lang_encoder_encode: N must be positive");
-  if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS)
-    return fail(OLSR_ERR_ARG, "lang_encoder_encode: unknown input layout");
-  if (!lang_ae_layout_ok(p->code_layout)) return fail(OLSR_ERR_ARG, "lang_encoder_encode: unknown code layout");
-  if (p->in_layout == OLSR_LANG_ENCODER_IN_CHANNELS && p->plane_stride < (int64_t)N)
-    return fail(OLSR_ERR_ARG, "lang_encoder_encode: plane_stride must be at least N in the channel layout");
-  if (!(p->bn_eps > 0.0)) return fail(OLSR_ERR_ARG, "lang_encoder_encode: bn_eps must be positive");
-  if (!features768 || !encoder_params) return fail(OLSR_ERR_ARG, "lang_encoder_encode: features768 and encoder_params are required");
-  if (!features32 && !codes) return fail(OLSR_ERR_ARG, "lang_encoder_encode: features32 and codes are both NULL");
-  if (codes && !online_params) return fail(OLSR_ERR_ARG, "lang_encoder_encode: codes need online_params");
-  if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "lang_encoder_encode: encoder_params must be 16-byte aligned");
+  const char* missing = !features768 || !encoder_params ? "features768 and encoder_params are required"
+                        : !features32 && !codes         ? "features32 and codes are both NULL"
+                        : codes && !online_params       ? "codes need online_params"
+                                                        : nullptr;
+  if (const char* e = lang_encoder_call_error(p, N, encoder_params, missing))
+    return fail(OLSR_ERR_ARG, std::string("lang_encoder_encode: ") + e);
   return launch_check("lang_encoder_encode", launch_lang_encoder(*p, N, features768, encoder_params, online_params,
                                                                  features32, codes, (hipStream_t)hip_stream));
 }
@@ -427,16 +437,9 @@ int olsr_ss_encoder_encode(const olsr_ss_encoder_params* p, int32_t N, const flo
   if (!p) return fail(OLSR_ERR_ARG, "ss_encoder_encode: the parameter struct is NULL");
   if (!widths_built(p->n_widths, p->widths, {OLSR_LANG_QUERY_FEATURE_DIM, 384, 192, 96, 48, 24, OLSR_LANG_AE_CODE}))
     return fail(OLSR_ERR_ARG, "ss_encoder_encode: this entry encodes the layer widths {768, 384, 192, 96, 48, 24, 15} only");
-  if (N < 1) return fail(OLSR_ERR_ARG, "ss_encoder_encode: N must be positive");
-  if (p->in_layout != OLSR_LANG_ENCODER_IN_ROWS && p->in_layout != OLSR_LANG_ENCODER_IN_CHANNELS)
-    return fail(OLSR_ERR_ARG, "ss_encoder_encode: unknown input layout");
-  if (!lang_ae_layout_ok(p->code_layout)) return fail(OLSR_ERR_ARG, "ss_encoder_encode: unknown code layout");
-  if (p->in_layout == OLSR_LANG_ENCODER_IN_CHANNELS && p->plane_stride < (int64_t)N)
-    return fail(OLSR_ERR_ARG, "ss_encoder_encode: plane_stride must be at least N in the channel layout");
-  if (!(p->bn_eps > 0.0)) return fail(OLSR_ERR_ARG, "ss_encoder_encode: bn_eps must be positive");
-  if (!features768 || !encoder_params || !codes)
-    return fail(OLSR_ERR_ARG, "ss_encoder_encode: features768, encoder_params and codes are required");
-  if ((uintptr_t)encoder_params & 15u) return fail(OLSR_ERR_ARG, "ss_encoder_encode: encoder_params must be 16-byte aligned");
+  const char* missing = !features768 || !encoder_params || !codes ? "features768, encoder_params and codes are required" : nullptr;
+  if (const char* e = lang_encoder_call_error(p, N, encoder_params, missing))
+    return fail(OLSR_ERR_ARG, std::string("ss_encoder_encode: ") + e);
   return launch_check("ss_encoder_encode", launch_ss_encoder(*p, N, features768, encoder_params, codes, (hipStream_t)hip_stream));
 }
 

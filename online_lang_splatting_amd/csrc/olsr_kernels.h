@@ -305,7 +305,8 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
 hipError_t launch_lang_encoder(const olsr_lang_encoder_params& p, int N, const float* features, const float* params,
                                const float* online, float* features32, float* codes, hipStream_t st);
 
-// k_lang_single_stage.hip: the single-stage chain's encoder 768 -> 15 and stage A of its text query (include/olsr_single_stage.h)
+// k_lang_encoder.hip, k_lang_query.hip: the single-stage chain's encoder 768 -> 15 and stage A of its text query
+// (include/olsr_single_stage.h)
 hipError_t launch_ss_encoder(const olsr_ss_encoder_params& p, int N, const float* features, const float* params, float* codes,
                              hipStream_t st);
 hipError_t launch_ss_query_sims(const olsr_lang_query_params& p, const float* codes, const float* dec, const float* phrases,

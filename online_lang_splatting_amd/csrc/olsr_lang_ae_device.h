@@ -1,9 +1,10 @@
 // olsr_lang_ae_device.h — the online language autoencoder 32 -> 24 -> 15 -> 24 -> 32 of one row, in one lane's registers:
-// the flat parameter layout of olsr_lang_ae_* and the forward halves.  k_lang_ae.hip trains, encodes and decodes with them,
+// the flat parameter layout of olsr_lang_ae_* and the forward halves, on olsr_dense.h's per-lane layers.  k_lang_ae.hip trains, encodes and decodes with them,
 // k_lang_encoder.hip encodes its unit rows, k_lang_query.hip decodes its codes: one sequence of operations, so the three
 // agree bit for bit.  Device only; -ffp-contract=off holds, every fma is written out.
 #pragma once
 #include "../../include/olsr.h"
+#include "olsr_dense.h"  // lane_linear, lane_norm
 
 namespace olsr {
 
@@ -14,37 +15,14 @@ constexpr int AE_W1 = 0, AE_B1 = AE_W1 + AE_H * AE_IN, AE_W2 = AE_B1 + AE_H, AE_
 constexpr int AE_W3 = AE_B2 + AE_C, AE_B3 = AE_W3 + AE_H * AE_C, AE_W4 = AE_B3 + AE_H, AE_B4 = AE_W4 + AE_IN * AE_H;
 static_assert(AE_B4 + AE_IN == AE_NP, "flat parameter layout");
 
-// y = W x + b, W [OUT, IN] row-major; uniform addresses (every lane reads the same parameter)
-template <int OUT, int IN>
-__device__ __forceinline__ void ae_linear(const float* __restrict__ W, const float* __restrict__ b, const float (&x)[IN],
-                                          float (&y)[OUT]) {
-#pragma unroll
-  for (int o = 0; o < OUT; ++o) {
-    float a = b[o];
-#pragma unroll
-    for (int i = 0; i < IN; ++i) a = fmaf(W[o * IN + i], x[i], a);
-    y[o] = a;
-  }
-}
-
-// |v| rounded once: the squares are exact in double, so v / |v| has unit norm to ~1 ulp (a float32 sum of 32 squares alone is
-// off by up to a few ulp, which the rows of decode() would inherit; 111 double fmas per row beside ~9 400 float32 ones)
-template <int K>
-__device__ __forceinline__ float ae_norm(const float (&v)[K]) {
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < K; ++k) s = fma((double)v[k], (double)v[k], s);
-  return (float)sqrt(s);
-}
-
 // encode: h1 = relu(W1 x + b1), c = z / |z| with z = W2 h1 + b2; returns |z|
 __device__ __forceinline__ float ae_encode(const float* __restrict__ P, const float (&x)[AE_IN], float (&h1)[AE_H],
                                            float (&c)[AE_C]) {
-  ae_linear<AE_H, AE_IN>(P + AE_W1, P + AE_B1, x, h1);
+  lane_linear<AE_H, AE_IN>(P + AE_W1, P + AE_B1, x, h1);
 #pragma unroll
   for (int k = 0; k < AE_H; ++k) h1[k] = fmaxf(h1[k], 0.f);
-  ae_linear<AE_C, AE_H>(P + AE_W2, P + AE_B2, h1, c);
-  const float n = ae_norm<AE_C>(c);
+  lane_linear<AE_C, AE_H>(P + AE_W2, P + AE_B2, h1, c);
+  const float n = lane_norm<AE_C>(c);
 #pragma unroll
   for (int k = 0; k < AE_C; ++k) c[k] = c[k] / n;
   return n;
@@ -53,11 +31,11 @@ __device__ __forceinline__ float ae_encode(const float* __restrict__ P, const fl
 // decode: h2 = relu(W3 c + b3), r = y / |y| with y = W4 h2 + b4; returns |y|
 __device__ __forceinline__ float ae_decode(const float* __restrict__ P, const float (&c)[AE_C], float (&h2)[AE_H],
                                            float (&r)[AE_IN]) {
-  ae_linear<AE_H, AE_C>(P + AE_W3, P + AE_B3, c, h2);
+  lane_linear<AE_H, AE_C>(P + AE_W3, P + AE_B3, c, h2);
 #pragma unroll
   for (int k = 0; k < AE_H; ++k) h2[k] = fmaxf(h2[k], 0.f);
-  ae_linear<AE_IN, AE_H>(P + AE_W4, P + AE_B4, h2, r);
-  const float n = ae_norm<AE_IN>(r);
+  lane_linear<AE_IN, AE_H>(P + AE_W4, P + AE_B4, h2, r);
+  const float n = lane_norm<AE_IN>(r);
 #pragma unroll
   for (int k = 0; k < AE_IN; ++k) r[k] = r[k] / n;
   return n;

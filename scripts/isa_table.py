@@ -9,7 +9,8 @@ file without comments and blank lines, without the __hip_cuid_* symbol (a hash o
 taken out of local labels (.LBB<n>_: it shifts when a kernel earlier in the file goes) and the kernel's own symbol replaced by
 a placeholder (its descriptor, which names it, is part of the stream; a renamed kernel still compares).  Equal hashes: the same
 machine code.
---rename-a maps the (demangled) kernel names of build A onto build B's where a kernel was renamed.  --mid adds a column for an
+--rename-a maps the (demangled) kernel names of build A onto build B's where a kernel was renamed.  A kernel that moved to
+another unit under its own name is paired by that name.  --mid adds a column for an
 intermediate build (named like B); a row is equal when all of its columns are.
 Prints the kernels whose figures differ; the JSON holds all of them.
 """
@@ -92,9 +93,15 @@ def main():
             out[f"{key[0]}: {key[1]}" if name in out else name] = build[key]  # (overloads: the mangled name tells them apart)
         return out
 
-    cols = [(g.label_a, by_name(a, g.rename_a))]
+    col_a, col_b = by_name(a, g.rename_a), by_name(b, None)
+    # a kernel of A whose unit is gone from B pairs with the one kernel of that name in B that has no partner of its own
+    for name in [n for n in col_a if n not in col_b]:
+        moved = [n for n in col_b if n not in col_a and n.split(": ", 1)[1] == name.split(": ", 1)[1]]
+        if len(moved) == 1:
+            col_a[moved[0]] = col_a.pop(name)
+    cols = [(g.label_a, col_a)]
     cols += [(g.label_mid, by_name(mid, None))] if g.mid else []
-    cols += [(g.label_b, by_name(b, None))]
+    cols += [(g.label_b, col_b)]
     table = {}
     for name in sorted(set().union(*(c for _, c in cols))):
         row = {label: c.get(name) for label, c in cols}
