@@ -76,6 +76,11 @@ extern "C" {
  * resize functionals of CR/rasterizer.h:34-36 and DGR/rasterize_points.cu:27-33. */
 typedef void *(*olsr_alloc_fn)(void *user, size_t nbytes);
 
+/* Scratch buffers.  Wherever an entry takes a `scratch` pointer sized by an olsr_*_scratch_bytes function, the pointer may
+ * have any alignment: the library rounds it up to 256 bytes and lays its arrays out behind that, and the sizing function
+ * reserves the slack.  The contents need not survive the call unless the entry says so (a plan's scratch is read by its
+ * emit, apply or finish).  One buffer is not of this kind: olsr_hr_net_forward's workspace must be 16-byte aligned. */
+
 /* Caller-side activations folded into the kernels.  The reference applies
  * sigmoid / exp / normalize in PyTorch before every render (GaussianModel.get_opacity / get_scaling /
  * get_rotation, gaussian_splatting/scene/gaussian_model.py:95-105) and autograd chains back through them.
@@ -1087,7 +1092,7 @@ int olsr_hr_net_forward(const olsr_hr_net_params *params, const float *fv, const
  *     gives the same bits;
  *   - emit writes vertices below vert_capacity and faces below face_capacity only; its min_weight is the plan's (the plan's
  *     scratch holds what it decided).  3 * face_capacity must fit an int32: OLSR_ERR_ARG otherwise.
- *   scratch: olsr_tsdf_mesh_scratch_bytes = 4 bytes per voxel, four 32-bit words per block of 256 voxels, and 16.
+ *   scratch: olsr_tsdf_mesh_scratch_bytes: 4 bytes per voxel and four 32-bit words per block of 256 voxels.
  * Limits: X * Y * Z < 2^31 for integrate and init, 3 * X * Y * Z < 2^31 for the extraction. */
 #define OLSR_TSDF_MAX_VIEWS 16
 #define OLSR_TSDF_FEAT_FLOAT 0
@@ -1136,8 +1141,7 @@ int olsr_tsdf_mesh_emit(const olsr_tsdf_volume *volume, float min_weight, const 
  *                 cost one 4 (B + 1)-byte read and a synchronisation of the stream, host tables one small upload into the scratch.
  *   max_n1/2      at least the longest segment of the cloud (sizes the grid); a longer segment is OLSR_ERR_ARG
  *   xyz1, xyz2    device float[total,3], packed
- *   scratch       device, olsr_*_scratch_bytes(B, off1[B], off2[B]) bytes, 256-byte aligned inside; contents need not survive
- *                 between calls.  EMD: per point 8 (the row's cost, double) + 12 (remain x 2, ratio) + 3 x 16 x 4 (cloud 1; 16 x 4
+ *   scratch       device, olsr_*_scratch_bytes(B, off1[B], off2[B]) bytes.  EMD: per point 8 (the row's cost, double) + 12 (remain x 2, ratio) + 3 x 16 x 4 (cloud 1; 16 x 4
  *                 for cloud 2) bytes of partial sums: O(n + m), no match matrix.  Chamfer: 16 x 8 bytes per point.
  * An empty segment on either side is legal: its outputs are NaN (nn: -1), valid[b] = 0.  Non-finite coordinates make that
  * segment's outputs unspecified and touch no other segment.  A segment's outputs depend on its own points only, bit for bit:

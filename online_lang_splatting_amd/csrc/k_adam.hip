@@ -252,13 +252,26 @@ __global__ __launch_bounds__(ISO_T) void isotropic_loss_kernel(int nb, const dou
   if (threadIdx.x == 0) *loss = scale * tot;
 }
 
-size_t isotropic_reg_scratch_bytes(int P) { return (size_t)((P > 0 ? P : 0) + ISO_T - 1) / ISO_T * sizeof(double) + sizeof(double); }
+// the scratch: one partial sum per block
+static double* isotropic_reg_carve(void* buf, int P, size_t& bytes) {
+  Carver c(buf);
+  double* partials = c.take<double>((size_t)((P + ISO_T - 1) / ISO_T));
+  bytes = c.total();
+  return partials;
+}
+
+size_t isotropic_reg_scratch_bytes(int P) {
+  size_t bytes = 0;
+  isotropic_reg_carve(nullptr, P > 0 ? P : 0, bytes);
+  return bytes;
+}
 
 void launch_isotropic_reg(int P, const float* scales, int activations, double weight, float* grad, double* loss,
                           void* scratch, hipStream_t st) {
   const int nb = (P + ISO_T - 1) / ISO_T;
   const AdamReg rk{(float)(weight / (9.0 * (double)P)), (activations & OLSR_ACT_SCALE_EXP) ? 1 : 0};
-  double* partials = loss ? reinterpret_cast<double*>(scratch) : nullptr;
+  size_t bytes;
+  double* partials = loss ? isotropic_reg_carve(scratch, P, bytes) : nullptr;
   isotropic_reg_kernel<<<nb, ISO_T, 0, st>>>(P, scales, rk, grad, partials);
   if (loss) isotropic_loss_kernel<<<1, ISO_T, 0, st>>>(nb, partials, weight / (3.0 * (double)P), loss);
 }

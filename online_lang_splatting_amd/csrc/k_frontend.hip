@@ -44,19 +44,21 @@ struct FeScratch {
   SelectState* state;
   u32* hist;   // [FE_PASSES][256]
   u32* keys;   // [n]
+  static FeScratch carve(void* buf, size_t n, size_t& bytes) {
+    Carver c(buf);
+    FeScratch s;
+    s.state = c.take<SelectState>(1);
+    s.hist = c.take<u32>(FE_PASSES * 256);
+    s.keys = c.take<u32>(n);
+    bytes = c.total();
+    return s;
+  }
 };
 
-__host__ __device__ inline FeScratch fe_carve(void* scratch) {
-  uint8_t* b = reinterpret_cast<uint8_t*>(scratch);
-  FeScratch s;
-  s.state = reinterpret_cast<SelectState*>(b);
-  s.hist = reinterpret_cast<u32*>(b + 64);
-  s.keys = s.hist + FE_PASSES * 256;
-  return s;
-}
-
 size_t frontend_scratch_bytes(int64_t n) {
-  return 64 + (size_t)FE_PASSES * 256 * sizeof(u32) + (size_t)(n > 0 ? n : 0) * sizeof(u32) + 16;
+  size_t bytes = 0;
+  FeScratch::carve(nullptr, (size_t)(n > 0 ? n : 0), bytes);
+  return bytes;
 }
 
 // one key into the workgroup's histogram h[256] of `pass`, when it shares the prefix of the passes before
@@ -288,7 +290,8 @@ hipError_t launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float 
     grad_mask_blocks_kernel<<<grid, FE_THREADS, lds, st>>>(W, H, plane_stride, edge_threshold, image, mask);
     return hipSuccess;
   }
-  const FeScratch sc = fe_carve(scratch);
+  size_t bytes;
+  const FeScratch sc = FeScratch::carve(scratch, (size_t)N, bytes);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   grad_intensity_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(W, H, plane_stride, image, sc);
@@ -320,7 +323,8 @@ __global__ __launch_bounds__(FE_THREADS) void median_depth_keys_kernel(int64_t N
 
 hipError_t launch_median_depth(int64_t N, const float* depth, const float* opacity, const uint8_t* mask, void* scratch,
                                float* median, int32_t* count, hipStream_t st) {
-  const FeScratch sc = fe_carve(scratch);
+  size_t bytes;
+  const FeScratch sc = FeScratch::carve(scratch, (size_t)N, bytes);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   median_depth_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(N, depth, opacity, mask, sc);

@@ -41,31 +41,31 @@ struct SeedState {
   int32_t n_valid, n_keep;
 };
 
+__host__ __device__ inline size_t seed_blocks(size_t N) { return (N + SEED_PIX - 1) / SEED_PIX; }
+
 struct SeedScratch {
   SeedState* state;
   u32* hist;       // [SEED_PASSES][SEED_SELECTS][256]
-  u32* mkey;       // [N] median key of d' per pixel; finish reuses the words as mean_dist2 [n]
+  u32* mkey;       // [N rounded up to 4] median key of d' per pixel; finish reuses the words as mean_dist2 [n]
   int32_t* counts; // [blocks of SEED_PIX]
   int32_t* offsets;
+  static SeedScratch carve(void* buf, size_t N, size_t& bytes) {
+    Carver c(buf);
+    SeedScratch s;
+    s.state = c.take<SeedState>(1);
+    s.hist = c.take<u32>(SEED_PASSES * SEED_SELECTS * 256);
+    s.mkey = c.take<u32>((N + 3) / 4 * 4);
+    s.counts = c.take<int32_t>(seed_blocks(N));
+    s.offsets = c.take<int32_t>(seed_blocks(N));
+    bytes = c.total();
+    return s;
+  }
 };
 
-__host__ __device__ inline size_t seed_blocks(size_t N) { return (N + SEED_PIX - 1) / SEED_PIX; }
-
-__host__ __device__ inline SeedScratch seed_carve(void* scratch, size_t N) {
-  uint8_t* b = reinterpret_cast<uint8_t*>(scratch);
-  SeedScratch s;
-  s.state = reinterpret_cast<SeedState*>(b);
-  s.hist = reinterpret_cast<u32*>(b + 64);
-  s.mkey = s.hist + SEED_PASSES * SEED_SELECTS * 256;
-  s.counts = reinterpret_cast<int32_t*>(s.mkey + (N + 3) / 4 * 4);
-  s.offsets = s.counts + seed_blocks(N);
-  return s;
-}
-
 size_t keyframe_seed_scratch_bytes(int W, int H) {
-  const size_t N = (W > 0 && H > 0) ? (size_t)W * (size_t)H : 0;
-  return 64 + (size_t)SEED_PASSES * SEED_SELECTS * 256 * sizeof(u32) + (N + 3) / 4 * 4 * sizeof(u32) +
-         2 * seed_blocks(N) * sizeof(int32_t) + 16;
+  size_t bytes = 0;
+  SeedScratch::carve(nullptr, (W > 0 && H > 0) ? (size_t)W * (size_t)H : 0, bytes);
+  return bytes;
 }
 
 // murmur3's finaliser: a bijection of 32 bits
@@ -281,7 +281,8 @@ hipError_t launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const f
                                      const float* exposure, const float* w2c, const olsr_map_buffers& rows,
                                      int32_t* pix_index, void* scratch, int32_t* status, float* aux, hipStream_t st) {
   const int64_t N = (int64_t)p.W * p.H;
-  const SeedScratch sc = seed_carve(scratch, (size_t)N);
+  size_t bytes;
+  const SeedScratch sc = SeedScratch::carve(scratch, (size_t)N, bytes);
   const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SEED_PASSES * SEED_SELECTS * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   const int hb = (int)((N + SEED_HIST_PIX - 1) / SEED_HIST_PIX), nb = (int)seed_blocks((size_t)N);
@@ -298,7 +299,8 @@ hipError_t launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const f
 
 void launch_keyframe_seed_finish(const olsr_keyframe_seed_params& p, int n, const olsr_map_buffers& rows, const float* aux,
                                  void* scratch, void* knn_scratch, hipStream_t st) {
-  const SeedScratch sc = seed_carve(scratch, (size_t)p.W * (size_t)p.H);
+  size_t bytes;
+  const SeedScratch sc = SeedScratch::carve(scratch, (size_t)p.W * (size_t)p.H, bytes);
   float* d2 = reinterpret_cast<float*>(sc.mkey);   // n <= W H words; the plan is done with them
   launch_knn(n, rows.means3D, d2, knn_scratch, st);
   seed_scales<<<(n + SEED_THREADS - 1) / SEED_THREADS, SEED_THREADS, 0, st>>>(n, d2, aux, rows.scales);

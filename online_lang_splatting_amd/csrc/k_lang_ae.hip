@@ -262,18 +262,34 @@ __global__ __launch_bounds__(AE_ROWS) void lang_ae_decode_kernel(int N, const fl
 }
 
 static inline int ae_blocks(int N) { return (N + AE_ROWS - 1) / AE_ROWS; }
-static inline size_t ae_partials_bytes(int N) { return ((size_t)ae_blocks(N) * AE_PSTRIDE * sizeof(float) + 255) / 256 * 256; }
 static inline bool ae_vec4(const float* features) { return ((uintptr_t)features & 15u) == 0; }
 
-// [gradient partials: blocks x 2352 float | loss partials: blocks x 2 double] behind a 256-byte aligned base
-size_t lang_ae_scratch_bytes(int N) { return ae_partials_bytes(N) + (size_t)ae_blocks(N) * 2 * sizeof(double) + 256; }
+struct AeScratch {
+  float* partials;        // [blocks][AE_PSTRIDE] gradient partials
+  double* loss_partials;  // [blocks][2]
+  static AeScratch carve(void* buf, int N, size_t& bytes) {
+    Carver c(buf);
+    AeScratch s;
+    s.partials = c.take<float>((size_t)ae_blocks(N) * AE_PSTRIDE);
+    s.loss_partials = c.take<double>((size_t)ae_blocks(N) * 2);
+    bytes = c.total();
+    return s;
+  }
+};
+
+size_t lang_ae_scratch_bytes(int N) {
+  size_t bytes = 0;
+  AeScratch::carve(nullptr, N > 0 ? N : 0, bytes);
+  return bytes;
+}
 
 void launch_lang_ae_train_step(const olsr_lang_ae_params& p, int N, const float* features, float* params, float* exp_avg,
                                float* exp_avg_sq, int32_t* step_dev, float* loss, float* codes, float* grad_out, void* scratch,
                                hipStream_t st) {
-  char* base = (char*)(((uintptr_t)scratch + 255) / 256 * 256);
-  float* partials = (float*)base;
-  double* loss_partials = (double*)(base + ae_partials_bytes(N));
+  size_t bytes;
+  const AeScratch sc = AeScratch::carve(scratch, N, bytes);
+  float* partials = sc.partials;
+  double* loss_partials = sc.loss_partials;
   const int nb = ae_blocks(N);
   LangAeScalars k{};
   k.k_l1 = (float)(1.0 / ((double)N * AE_IN));

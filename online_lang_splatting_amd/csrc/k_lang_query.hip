@@ -342,10 +342,18 @@ static LqGeom lq_geom(const olsr_lang_query_params& p) {
 
 static inline size_t lq_tiles(int w, int h) { return (size_t)((w + LQ_TILE - 1) / LQ_TILE) * ((h + LQ_TILE - 1) / LQ_TILE); }
 
-// [per positive and 32 x 32 tile of the output one LqPartial] behind a 256-byte aligned base
+// the scratch: per positive and 32 x 32 tile of the output one LqPartial
+static LqPartial* lq_carve(void* buf, const olsr_lang_query_params& p, size_t& bytes) {
+  Carver c(buf);
+  LqPartial* partials = c.take<LqPartial>((size_t)(p.n_pos > 0 ? p.n_pos : 0) * lq_tiles(p.out_width, p.out_height));
+  bytes = c.total();
+  return partials;
+}
+
 size_t lang_query_scratch_bytes(const olsr_lang_query_params& p) {
-  const size_t n_pos = p.n_pos > 0 ? (size_t)p.n_pos : 0;
-  return n_pos * lq_tiles(p.out_width, p.out_height) * sizeof(LqPartial) + 256;
+  size_t bytes = 0;
+  lq_carve(nullptr, p, bytes);
+  return bytes;
 }
 
 // f(KT) for the number of 16-row phrase tiles that K phrases need
@@ -383,7 +391,8 @@ void launch_lang_query_relevancy(const olsr_lang_query_params& p, const float* s
   lang_query_relevancy_kernel<<<(unsigned)((n_out + 255) / 256), 256, 0, st>>>(g, p.K, p.n_pos, p.n_labels, sims, relevancy,
                                                                               labels);
   if (p.n_pos <= 0) return;
-  LqPartial* partials = (LqPartial*)(((uintptr_t)scratch + 255) / 256 * 256);
+  size_t bytes;
+  LqPartial* partials = lq_carve(scratch, p, bytes);
   const dim3 grid((W + LQ_TILE - 1) / LQ_TILE, (H + LQ_TILE - 1) / LQ_TILE, p.n_pos);
   lang_query_smooth_kernel<<<grid, 256, 0, st>>>(W, H, relevancy, smoothed, blended, partials);
   lang_query_reduce_kernel<<<p.n_pos, 256, 0, st>>>(W, (int)lq_tiles(W, H), partials, score, coord, minmax);

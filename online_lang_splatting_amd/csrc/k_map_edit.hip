@@ -33,26 +33,26 @@ constexpr uint8_t ME_KEEP = 1, ME_CLONE = 2, ME_CHILD = 4;
 
 __host__ __device__ inline int me_blocks(int P) { return (P + ME_ROWS - 1) / ME_ROWS; }
 
-// scratch: [class bytes, P rounded to 16] [block counts int32 3 x nb] [block offsets int32 3 x nb]
-size_t map_edit_scratch_bytes(int P) {
-  const size_t nb = (size_t)me_blocks(P > 0 ? P : 0);
-  return ((size_t)(P > 0 ? P : 0) + 15) / 16 * 16 + 2 * 3 * nb * sizeof(int32_t) + 16;
-}
-
 struct MeScratch {
-  uint8_t* cls;
-  int32_t* counts;
-  int32_t* offsets;
+  uint8_t* cls;      // [P rounded up to 16] class bytes
+  int32_t* counts;   // [3 x nb] block counts
+  int32_t* offsets;  // [3 x nb] block offsets
+  static MeScratch carve(void* buf, int P, size_t& bytes) {
+    Carver c(buf);
+    const size_t nb = (size_t)me_blocks(P);
+    MeScratch s;
+    s.cls = c.take<uint8_t>(((size_t)P + 15) / 16 * 16);
+    s.counts = c.take<int32_t>(3 * nb);
+    s.offsets = c.take<int32_t>(3 * nb);
+    bytes = c.total();
+    return s;
+  }
 };
 
-__host__ __device__ inline MeScratch me_carve(void* scratch, int P) {
-  uint8_t* b = reinterpret_cast<uint8_t*>(scratch);
-  const size_t nb = (size_t)me_blocks(P);
-  MeScratch s;
-  s.cls = b;
-  s.counts = reinterpret_cast<int32_t*>(b + ((size_t)P + 15) / 16 * 16);
-  s.offsets = s.counts + 3 * nb;
-  return s;
+size_t map_edit_scratch_bytes(int P) {
+  size_t bytes = 0;
+  MeScratch::carve(nullptr, P > 0 ? P : 0, bytes);
+  return bytes;
 }
 
 __device__ inline float me_max3(float a, float b, float c) { return fmaxf(fmaxf(a, b), c); }
@@ -274,7 +274,8 @@ __global__ __launch_bounds__(ME_ROWS) void map_edit_apply(int P, int M, int F, i
 void launch_map_edit_plan(int P, const olsr_map_edit_params& p, const olsr_map_buffers& src, const uint8_t* drop_mask,
                           void* scratch, int32_t* status, hipStream_t st) {
   const int nb = me_blocks(P);
-  MeScratch sc = me_carve(scratch, P);
+  size_t bytes;
+  MeScratch sc = MeScratch::carve(scratch, P, bytes);
   if (nb > 0) map_edit_classify<<<nb, ME_ROWS, 0, st>>>(P, p, src, drop_mask, sc);
   map_edit_prefix<<<1, ME_PREFIX_THREADS, 0, st>>>(nb, p.n_append, sc, status);
 }
@@ -285,7 +286,8 @@ void launch_map_edit_apply(int P, int M, int F, const olsr_map_edit_params& p, c
   const int nb = me_blocks(P);
   const int na = p.n_append > 0 ? (p.n_append + ME_ROWS - 1) / ME_ROWS : 0;
   if (nb + na == 0) return;
-  MeScratch sc = me_carve(const_cast<void*>(scratch), P);
+  size_t bytes;
+  MeScratch sc = MeScratch::carve(const_cast<void*>(scratch), P, bytes);
   olsr_map_buffers app{};
   if (append) app = *append;
   map_edit_apply<<<nb + na, ME_ROWS, 0, st>>>(P, M, F, nb, p, src, z, app, sc, status, dst_capacity, dst, src_index);

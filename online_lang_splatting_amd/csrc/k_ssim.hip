@@ -248,21 +248,32 @@ __global__ __launch_bounds__(SSIM_THREADS) void ssim_grad_kernel(int W, int H, f
 
 static inline dim3 ssim_grid(int W, int H) { return dim3((W + SSIM_TW - 1) / SSIM_TW, (H + SSIM_TH - 1) / SSIM_TH, 3); }
 
-static inline size_t ssim_partials_bytes(int W, int H) {
-  const dim3 g = ssim_grid(W, H);
-  return ((size_t)g.x * g.y * g.z * 2 * sizeof(double) + 255) / 256 * 256;
-}
+struct SsimScratch {
+  double* partials;  // [2 per block]
+  float* planes;     // Dmu[3,H,W] | Ds1[3,H,W] | Ds12[3,H,W]: the kernels index all three from this one pointer
+  static SsimScratch carve(void* buf, int W, int H, size_t& bytes) {
+    Carver c(buf);
+    const dim3 g = ssim_grid(W, H);
+    SsimScratch s;
+    s.partials = c.take<double>((size_t)g.x * g.y * g.z * 2);
+    s.planes = c.take<float>((size_t)9 * H * W);
+    bytes = c.total();
+    return s;
+  }
+};
 
-// [partials | Dmu[3,H,W] | Ds1[3,H,W] | Ds12[3,H,W]] behind a 256-byte aligned base
 size_t refinement_loss_scratch_bytes(int W, int H) {
-  return ssim_partials_bytes(W, H) + (size_t)9 * H * W * sizeof(float) + 256;
+  size_t bytes = 0;
+  SsimScratch::carve(nullptr, W > 0 ? W : 0, H > 0 ? H : 0, bytes);
+  return bytes;
 }
 
 void launch_refinement_loss(int W, int H, float lambda, const float* image, const float* gt_image, float* dL_dimage,
                             float* loss, void* scratch, hipStream_t st) {
-  char* base = (char*)(((uintptr_t)scratch + 255) / 256 * 256);
-  double* partials = (double*)base;
-  float* planes = (float*)(base + ssim_partials_bytes(W, H));
+  size_t bytes;
+  const SsimScratch sc = SsimScratch::carve(scratch, W, H, bytes);
+  double* partials = sc.partials;
+  float* planes = sc.planes;
   const dim3 grid = ssim_grid(W, H);
   auto al16 = [](const void* q) { return ((uintptr_t)q & 15u) == 0; };
   const bool vec4 = (W % 4) == 0 && al16(image) && al16(gt_image);  // (the planes are 256-byte aligned)

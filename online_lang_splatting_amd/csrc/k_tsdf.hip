@@ -135,12 +135,25 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_integrate(olsr_tsdf_volume vo
 }
 
 // ---- the surface point cloud -----------------------------------------------------------------------------------------------
-// scratch: [block counts int32 nb] [block offsets int32 nb], nb = blocks of TS_THREADS voxels
 __host__ __device__ inline size_t ts_blocks(size_t N) { return (N + TS_THREADS - 1) / TS_THREADS; }
+static size_t ts_voxels(int X, int Y, int Z) { return (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0); }
+
+struct TsSurfaceScratch {
+  int32_t *counts, *offsets;  // [nb] each, nb = blocks of TS_THREADS voxels
+  static TsSurfaceScratch carve(void* buf, size_t N, size_t& bytes) {
+    Carver c(buf);
+    TsSurfaceScratch s;
+    s.counts = c.take<int32_t>(ts_blocks(N));
+    s.offsets = c.take<int32_t>(ts_blocks(N));
+    bytes = c.total();
+    return s;
+  }
+};
 
 size_t tsdf_surface_scratch_bytes(int X, int Y, int Z) {
-  const size_t N = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
-  return 2 * ts_blocks(N) * sizeof(int32_t) + 16;
+  size_t bytes = 0;
+  TsSurfaceScratch::carve(nullptr, ts_voxels(X, Y, Z), bytes);
+  return bytes;
 }
 
 // bit a of the result: the edge from voxel i = (x, y, z) along axis a (0 x, 1 y, 2 z) is owned by it and crosses zero
@@ -250,12 +263,28 @@ __global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_surface_prefix(int nb,
 // the voxel's own edges and for the neighbours' edges a cube's faces name alike.  The emit pass reads that word first: a voxel
 // away from the surface costs it 4 bytes.  The triangle table (olsr_mc_table.h, 2 KiB) is copied to LDS by every workgroup:
 // each lane indexes it with its own configuration, which through the scalar constant path would be one load per lane.
-// scratch: [vertex counts nb] [vertex offsets nb] [face counts nb] [face offsets nb] [voxel words X*Y*Z], 32 bits each
 static_assert(TS_THREADS == 256, "the table copy and the word's rank fields assume 256 voxels per block");
 
+struct TsMeshScratch {
+  u32 *vcounts, *voffsets, *fcounts, *foffsets;  // [nb] each: vertices and faces per block, and their prefixes
+  u32* words;                                    // [X * Y * Z] the voxel words
+  static TsMeshScratch carve(void* buf, size_t N, size_t& bytes) {
+    Carver c(buf);
+    TsMeshScratch s;
+    s.vcounts = c.take<u32>(ts_blocks(N));
+    s.voffsets = c.take<u32>(ts_blocks(N));
+    s.fcounts = c.take<u32>(ts_blocks(N));
+    s.foffsets = c.take<u32>(ts_blocks(N));
+    s.words = c.take<u32>(N);
+    bytes = c.total();
+    return s;
+  }
+};
+
 size_t tsdf_mesh_scratch_bytes(int X, int Y, int Z) {
-  const size_t N = (size_t)(X > 0 ? X : 0) * (size_t)(Y > 0 ? Y : 0) * (size_t)(Z > 0 ? Z : 0);
-  return (4 * ts_blocks(N) + N) * sizeof(u32) + 16;
+  size_t bytes = 0;
+  TsMeshScratch::carve(nullptr, ts_voxels(X, Y, Z), bytes);
+  return bytes;
 }
 
 // bits: ts_crossings' result for voxel i; config: bit c set when corner c = (c & 1, c >> 1 & 1, c >> 2 & 1) of the cube the
@@ -314,11 +343,14 @@ __global__ __launch_bounds__(TS_THREADS) void tsdf_mesh_count(olsr_tsdf_volume v
 // exclusive prefixes of the vertex and the face counts in block order; status = {vertices, faces, 0, 0}.  The faces are summed
 // without sign (up to 5 per voxel: beyond 2^31 in the largest volumes) and reported clamped; the emit entry refuses a
 // face_capacity whose 3-fold does not fit an int32.
-__global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_mesh_prefix(int nb, u32* __restrict__ scratch,
+__global__ __launch_bounds__(TS_PREFIX_THREADS) void tsdf_mesh_prefix(int nb, const u32* __restrict__ vcounts,
+                                                                       u32* __restrict__ voffsets,
+                                                                       const u32* __restrict__ fcounts,
+                                                                       u32* __restrict__ foffsets,
                                                                        int32_t* __restrict__ status) {
   __shared__ u32 s_w[TS_PREFIX_THREADS / 64];
-  const u32 n_verts = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, scratch, scratch + nb, s_w);
-  const u32 n_faces = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, scratch + 2 * (size_t)nb, scratch + 3 * (size_t)nb, s_w);
+  const u32 n_verts = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, vcounts, voffsets, s_w);
+  const u32 n_faces = single_block_excl_scan<TS_PREFIX_THREADS / 64>(nb, fcounts, foffsets, s_w);
   if (threadIdx.x == 0) {
     status[0] = (int32_t)n_verts;
     status[1] = (int32_t)(n_faces < 0x7fffffffu ? n_faces : 0x7fffffffu);
@@ -335,16 +367,14 @@ __device__ __forceinline__ float ts_gradient(const float* __restrict__ t, int j,
   return 0.5f * (t[j + stride] - t[j - stride]);
 }
 
-__global__ __launch_bounds__(TS_THREADS) void tsdf_mesh_emit(olsr_tsdf_volume vol, const u32* __restrict__ scratch, int nb,
-                                                             int vert_capacity, int face_capacity, float* __restrict__ points,
+__global__ __launch_bounds__(TS_THREADS) void tsdf_mesh_emit(olsr_tsdf_volume vol, const u32* __restrict__ voffsets,
+                                                             const u32* __restrict__ foffsets,
+                                                             const u32* __restrict__ words, int vert_capacity, int face_capacity, float* __restrict__ points,
                                                              float* __restrict__ normals, float* __restrict__ feats,
                                                              int32_t* __restrict__ voxel_index, int32_t* __restrict__ faces) {
   __shared__ u64 table[256];
   table[threadIdx.x] = MC_TABLE[threadIdx.x];
   __syncthreads();
-  const u32* voffsets = scratch + nb;
-  const u32* foffsets = scratch + 3 * (size_t)nb;
-  const u32* words = scratch + 4 * (size_t)nb;
   const int N = vol.X * vol.Y * vol.Z;
   const int YZ = vol.Y * vol.Z;
   const int i = blockIdx.x * TS_THREADS + threadIdx.x;
@@ -430,32 +460,39 @@ void launch_tsdf_integrate(const olsr_tsdf_volume& vol, int n_views, const olsr_
 }
 
 void launch_tsdf_surface_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st) {
-  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
-  int32_t* counts = reinterpret_cast<int32_t*>(scratch);
-  int32_t* offsets = counts + nb;
-  tsdf_surface<false><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, counts, nullptr, 0, nullptr, nullptr, nullptr);
-  tsdf_surface_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, counts, offsets, status);
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int nb = (int)ts_blocks(N);
+  size_t bytes;
+  const TsSurfaceScratch sc = TsSurfaceScratch::carve(scratch, N, bytes);
+  tsdf_surface<false><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, sc.counts, nullptr, 0, nullptr, nullptr, nullptr);
+  tsdf_surface_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, sc.counts, sc.offsets, status);
 }
 
 void launch_tsdf_surface_emit(const olsr_tsdf_volume& vol, float min_weight, const void* scratch, int capacity, float* points,
                               float* feats, int32_t* voxel_index, hipStream_t st) {
-  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
-  const int32_t* offsets = reinterpret_cast<const int32_t*>(scratch) + nb;
-  tsdf_surface<true><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, nullptr, offsets, capacity, points, feats, voxel_index);
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int nb = (int)ts_blocks(N);
+  size_t bytes;
+  const TsSurfaceScratch sc = TsSurfaceScratch::carve(const_cast<void*>(scratch), N, bytes);
+  tsdf_surface<true><<<nb, TS_THREADS, 0, st>>>(vol, min_weight, nullptr, sc.offsets, capacity, points, feats, voxel_index);
 }
 
 void launch_tsdf_mesh_plan(const olsr_tsdf_volume& vol, float min_weight, void* scratch, int32_t* status, hipStream_t st) {
-  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
-  u32* s = reinterpret_cast<u32*>(scratch);
-  tsdf_mesh_count<<<nb, TS_THREADS, 0, st>>>(vol, min_weight, s, s + 2 * (size_t)nb, s + 4 * (size_t)nb);
-  tsdf_mesh_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, s, status);
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  const int nb = (int)ts_blocks(N);
+  size_t bytes;
+  const TsMeshScratch sc = TsMeshScratch::carve(scratch, N, bytes);
+  tsdf_mesh_count<<<nb, TS_THREADS, 0, st>>>(vol, min_weight, sc.vcounts, sc.fcounts, sc.words);
+  tsdf_mesh_prefix<<<1, TS_PREFIX_THREADS, 0, st>>>(nb, sc.vcounts, sc.voffsets, sc.fcounts, sc.foffsets, status);
 }
 
 void launch_tsdf_mesh_emit(const olsr_tsdf_volume& vol, const void* scratch, int vert_capacity, int face_capacity, float* points,
                            float* normals, float* feats, int32_t* voxel_index, int32_t* faces, hipStream_t st) {
-  const int nb = (int)ts_blocks((size_t)vol.X * vol.Y * vol.Z);
-  tsdf_mesh_emit<<<nb, TS_THREADS, 0, st>>>(vol, reinterpret_cast<const u32*>(scratch), nb, vert_capacity, face_capacity, points,
-                                            normals, feats, voxel_index, faces);
+  const size_t N = (size_t)vol.X * vol.Y * vol.Z;
+  size_t bytes;
+  const TsMeshScratch sc = TsMeshScratch::carve(const_cast<void*>(scratch), N, bytes);
+  tsdf_mesh_emit<<<(int)ts_blocks(N), TS_THREADS, 0, st>>>(vol, sc.voffsets, sc.foffsets, sc.words, vert_capacity, face_capacity,
+                                                           points, normals, feats, voxel_index, faces);
 }
 
 }  // namespace olsr

@@ -285,7 +285,9 @@ size_t olsr_backward_scratch_bytes(int64_t rows, int32_t F) {
 
 size_t olsr_fused_loss_scratch_bytes(int32_t width, int32_t height, int32_t tile) {
   if (width <= 0 || height <= 0 || (tile != 15 && tile != 16)) return 0;
-  return align_up(tile_count(width, height, tile) * 5 * sizeof(float)) + ALIGN;
+  size_t bytes = 0;
+  loss_partials_carve(nullptr, tile_count(width, height, tile), bytes);
+  return bytes;
 }
 
 int olsr_forward(const olsr_scene* scene, olsr_alloc_fn geometry_alloc, void* geometry_user,
@@ -354,7 +356,8 @@ int olsr_forward_async_loss(const olsr_scene* scene, void* geometry_buffer, void
     if (scene->P <= 0)  // nothing is rendered (the images are the background): the stand-alone kernels define this case
       return fail(OLSR_ERR_ARG, "fused loss: P must be > 0 (use olsr_mapping_loss / olsr_tracking_loss on an empty render)");
     lf = *loss;
-    lf.scratch = align_ptr(loss->scratch);
+    size_t bytes;
+    lf.scratch = loss_partials_carve(loss->scratch, tile_count(scene->width, scene->height, scene->tile), bytes);
   }
   ForwardCall c;
   c.st = (hipStream_t)hip_stream;
@@ -519,9 +522,9 @@ int olsr_debug_backward_ordered(const olsr_scene* scene, const void* geometry_bu
   const GeometryState g = GeometryState::carve(const_cast<void*>(geometry_buffer), (size_t)s.P, grad_row(s.F));
   const ImageState im = ImageState::carve(const_cast<void*>(image_buffer), (size_t)d.W * d.H, (size_t)d.ntiles);
   const BinningState b = BinningState::carve(const_cast<void*>(binning_buffer), (size_t)num_rendered);
-  float* rows = align_ptr<float>(scratch);
-  uint8_t* used = (uint8_t*)rows + align_up((size_t)num_rendered * (size_t)grad_row(s.F) * sizeof(float));
-  launch_render_backward_ordered(s, d, g, b, im, num_rendered, dL_dout_color, dL_dout_language, dL_dout_depth, rows, used,
+  size_t bytes;
+  const OrderedBwdScratch sc = OrderedBwdScratch::carve(scratch, (size_t)num_rendered, grad_row(s.F), bytes);
+  launch_render_backward_ordered(s, d, g, b, im, num_rendered, dL_dout_color, dL_dout_language, dL_dout_depth, sc.rows, sc.used,
                                  dL_dmeans2D, dL_dconic, dL_dopacity, dL_dcolors, dL_dlanguage, dL_ddepths, condition != 0,
                                  (hipStream_t)hip_stream);
   return launch_check("ordered backward");

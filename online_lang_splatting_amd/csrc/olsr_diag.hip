@@ -329,7 +329,9 @@ int olsr_debug_activate(int32_t P, int32_t activations, const float* opacities_r
 
 size_t olsr_debug_backward_ordered_scratch_bytes(int64_t num_rendered, int32_t F) {
   if (num_rendered < 0 || !supported_F(F)) return 0;
-  return align_up((size_t)num_rendered * (size_t)grad_row(F) * sizeof(float)) + align_up((size_t)num_rendered) + 2 * ALIGN;
+  size_t bytes = 0;
+  OrderedBwdScratch::carve(nullptr, (size_t)num_rendered, grad_row(F), bytes);
+  return bytes;
 }
 
 }  // extern "C"

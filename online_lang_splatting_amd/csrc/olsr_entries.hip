@@ -247,8 +247,9 @@ int olsr_knn_mean_dist2(int32_t P, const float* points, float* mean_dist2, void*
 }
 
 size_t olsr_mapping_loss_scratch_bytes(int32_t width, int32_t height) {
-  if (width <= 0 || height <= 0) return ALIGN;
-  return (size_t)loss_blocks(width, height) * 5 * sizeof(float) + ALIGN;
+  size_t bytes = 0;
+  loss_partials_carve(nullptr, (size_t)loss_blocks(width > 0 ? width : 0, height > 0 ? height : 0), bytes);
+  return bytes;
 }
 
 int olsr_mapping_loss(const olsr_loss_params* params, const float* image, const float* depth, const float* language,
@@ -265,7 +266,8 @@ int olsr_mapping_loss(const olsr_loss_params* params, const float* image, const 
   if (p.F > 0 && gt_language && (p.lang_width <= 0 || p.lang_height <= 0))
     return fail(OLSR_ERR_ARG, "the language target size must be positive");
   hipStream_t st = (hipStream_t)hip_stream;
-  float* partials = align_ptr<float>(scratch);
+  size_t bytes;
+  float* partials = loss_partials_carve(scratch, (size_t)loss_blocks(p.width, p.height), bytes);
   launch_mapping_loss(p, image, depth, language, gt_image, gt_depth, p.F > 0 ? gt_language : nullptr, exposure, nullptr,
                       nullptr, false, dL_dimage, dL_ddepth, dL_dlanguage, loss, dL_dexposure, partials, st);
   return launch_check("mapping_loss");
@@ -281,14 +283,14 @@ int olsr_tracking_loss(const olsr_loss_params* params, const float* image, const
   if (!image || !depth || !opacity || !gt_image || !gt_depth || !dL_dimage || !dL_ddepth || !loss || !scratch)
     return fail(OLSR_ERR_ARG, "image, depth, opacity, their targets, the gradient outputs, loss and scratch are required");
   hipStream_t st = (hipStream_t)hip_stream;
-  float* partials = align_ptr<float>(scratch);
+  size_t bytes;
+  float* partials = loss_partials_carve(scratch, (size_t)loss_blocks(p.width, p.height), bytes);
   launch_mapping_loss(p, image, depth, nullptr, gt_image, gt_depth, nullptr, exposure, opacity, grad_mask, true, dL_dimage,
                       dL_ddepth, nullptr, loss, dL_dexposure, partials, st);
   return launch_check("tracking_loss");
 }
 
 size_t olsr_refinement_loss_scratch_bytes(int32_t width, int32_t height) {
-  if (width <= 0 || height <= 0) return ALIGN;
   return refinement_loss_scratch_bytes(width, height);
 }
 
@@ -301,7 +303,7 @@ int olsr_refinement_loss(int32_t width, int32_t height, float lambda_dssim, cons
   return launch_check("refinement_loss");
 }
 
-size_t olsr_lang_ae_scratch_bytes(int32_t N) { return N <= 0 ? ALIGN : lang_ae_scratch_bytes(N); }
+size_t olsr_lang_ae_scratch_bytes(int32_t N) { return lang_ae_scratch_bytes(N); }
 
 static bool lang_ae_layout_ok(int32_t layout) {
   return layout == OLSR_LANG_AE_CODES_ROWS || layout == OLSR_LANG_AE_CODES_CHANNELS;

@@ -71,6 +71,28 @@ inline size_t tile_count(int w, int h, int tile) {
   return (size_t)tiles_along(w, tile) * (size_t)tiles_along(h, tile);
 }
 
+// ---- scratch layouts that two of the host sources share (each file's own are beside its kernels)
+// the losses' partial sums, five floats for each of n blocks (stand-alone: loss_blocks) or tiles (fused into the forward)
+inline float* loss_partials_carve(void* buf, size_t n, size_t& bytes) {
+  Carver c(buf);
+  float* partials = c.take<float>(5 * n);
+  bytes = c.total();
+  return partials;
+}
+// the ordered debug backward: one gradient row and one flag byte per instance
+struct OrderedBwdScratch {
+  float* rows;    // [R][grad_row(F)]
+  uint8_t* used;  // [R]
+  static OrderedBwdScratch carve(void* buf, size_t R, int grad_row_floats, size_t& bytes) {
+    Carver c(buf);
+    OrderedBwdScratch s;
+    s.rows = c.take<float>(R * (size_t)grad_row_floats);
+    s.used = c.take<uint8_t>(R);
+    bytes = c.total();
+    return s;
+  }
+};
+
 // ---- host state of the synchronising (drop-in) entry, olsr_dropin.hip
 // the instance count on the host: arm() before the depth sort's histogram kernel is launched, wait() after the sort
 int pinned_count_arm(FusedHouse& house);

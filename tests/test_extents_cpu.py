@@ -3,8 +3,11 @@ null-base carve must hand out ascending, 256-byte aligned, disjoint ranges that 
 is not 256-byte aligned uses up) before the size it returns, and the size must not shrink when a size argument grows — a
 buffer sized for a capacity must hold every smaller count (olsr_forward_async carves a capacity-sized binning buffer).
 
-A sizing function whose entry lays its scratch out by hand leaves no records: it is listed with carved=False, checked for
-monotony alone, and must indeed leave none (moving it onto Carver means flipping its flag here and gaining the layout checks).
+Every scratch of more than one array, and every one whose base the library rounds up, is carved.  The two sizing functions
+whose entries still lay their buffer out by hand leave no records: they are listed with carved=False, checked for monotony
+alone, and must indeed leave none.  olsr_backward_scratch_bytes sizes a single array and its byte count takes part in the
+drop-in backward's row policy; olsr_hr_net_workspace_bytes sizes a workspace whose 16-byte alignment is an argument check and
+whose exact size tests/test_hr_net_abi_cpu.py pins.
 
 The two radix sorts' status words: whatever keys-per-thread and block shape the plan picks or a test forces, the rows the
 passes publish (blocks x 128 words x 4 passes) fit the room the state's carve leaves for them behind the tickets, digit totals
@@ -47,25 +50,26 @@ ROWS = [
     ("olsr_query_eval_scratch_bytes", lambda L, P, H, W: L.olsr_query_eval_scratch_bytes(P, H, W), [(1, (1, 7), 65535), (2, (2, 33), 1 << 20), (2, (2, 33), 1 << 20)],
      [], True),   # (its documented domain: 1 <= P <= 65535, 2 <= H, W <= 2^20)
     ("olsr_image_psnr_scratch_bytes", lambda L: L.olsr_image_psnr_scratch_bytes(), [], [], True),
-    # ---- laid out by hand in their kernels' files: the size alone
-    ("olsr_backward_scratch_bytes", lambda L, rows, F: L.olsr_backward_scratch_bytes(rows, F), [(0, None)], [F_ALL], False),
     ("olsr_debug_backward_ordered_scratch_bytes", lambda L, R, F: L.olsr_debug_backward_ordered_scratch_bytes(R, F), [(0, None)], [F_ALL],
-     False),
+     True),
     ("olsr_fused_loss_scratch_bytes", lambda L, w, h, t: L.olsr_fused_loss_scratch_bytes(w, h, t), [(1, (1, 37)), (1, (1, 37))], [(15, 16)],
-     False),
-    ("olsr_mapping_loss_scratch_bytes", lambda L, w, h: L.olsr_mapping_loss_scratch_bytes(w, h), [(0, (1, 37)), (0, (1, 37))], [], False),
-    ("olsr_refinement_loss_scratch_bytes", lambda L, w, h: L.olsr_refinement_loss_scratch_bytes(w, h), [(0, (1, 37)), (0, (1, 37))], [], False),
-    ("olsr_isotropic_reg_scratch_bytes", lambda L, P: L.olsr_isotropic_reg_scratch_bytes(P), [(0, None)], [], False),
-    ("olsr_map_edit_scratch_bytes", lambda L, P: L.olsr_map_edit_scratch_bytes(P), [(0, None)], [], False),
-    ("olsr_keyframe_seed_scratch_bytes", lambda L, W, H: L.olsr_keyframe_seed_scratch_bytes(W, H), [(1, (1, 37)), (1, (1, 37))], [], False),
-    ("olsr_frontend_scratch_bytes", lambda L, n: L.olsr_frontend_scratch_bytes(n), [(0, None)], [], False),
-    ("olsr_lang_ae_scratch_bytes", lambda L, N: L.olsr_lang_ae_scratch_bytes(N), [(0, None)], [], False),
-    ("olsr_lang_query_scratch_bytes", _lang_query_bytes, [(0, (1, 3)), (1, (1, 33)), (1, (1, 33))], [], False),
-    ("olsr_hr_net_workspace_bytes", lambda L, h, w: L.olsr_hr_net_workspace_bytes(h, w, 1, 1, 1, 1), [(1, (1, 3)), (1, (1, 3))], [], False),
+     True),
+    ("olsr_mapping_loss_scratch_bytes", lambda L, w, h: L.olsr_mapping_loss_scratch_bytes(w, h), [(0, (1, 37)), (0, (1, 37))], [], True),
+    ("olsr_refinement_loss_scratch_bytes", lambda L, w, h: L.olsr_refinement_loss_scratch_bytes(w, h), [(0, (1, 37)), (0, (1, 37))], [], True),
+    ("olsr_isotropic_reg_scratch_bytes", lambda L, P: L.olsr_isotropic_reg_scratch_bytes(P), [(0, None)], [], True),
+    ("olsr_map_edit_scratch_bytes", lambda L, P: L.olsr_map_edit_scratch_bytes(P), [(0, None)], [], True),
+    ("olsr_keyframe_seed_scratch_bytes", lambda L, W, H: L.olsr_keyframe_seed_scratch_bytes(W, H), [(1, (1, 37)), (1, (1, 37))], [], True),
+    ("olsr_frontend_scratch_bytes", lambda L, n: L.olsr_frontend_scratch_bytes(n), [(0, None)], [], True),
+    ("olsr_lang_ae_scratch_bytes", lambda L, N: L.olsr_lang_ae_scratch_bytes(N), [(0, None)], [], True),
+    ("olsr_lang_query_scratch_bytes", _lang_query_bytes, [(0, (1, 3)), (1, (1, 33)), (1, (1, 33))], [], True),
     ("olsr_tsdf_surface_scratch_bytes", lambda L, X, Y, Z: L.olsr_tsdf_surface_scratch_bytes(X, Y, Z),
-     [(0, (1, 7)), (0, (1, 7)), (0, (1, 7))], [], False),
+     [(0, (1, 7)), (0, (1, 7)), (0, (1, 7))], [], True),
     ("olsr_tsdf_mesh_scratch_bytes", lambda L, X, Y, Z: L.olsr_tsdf_mesh_scratch_bytes(X, Y, Z), [(0, (1, 7)), (0, (1, 7)), (0, (1, 7))],
-     [], False),
+     [], True),
+    # ---- laid out by hand: the size alone.  The row scratch is a single array whose byte count takes part in the drop-in
+    # backward's row policy; the workspace's 16-byte alignment is an argument check and its exact size is pinned
+    ("olsr_backward_scratch_bytes", lambda L, rows, F: L.olsr_backward_scratch_bytes(rows, F), [(0, None)], [F_ALL], False),
+    ("olsr_hr_net_workspace_bytes", lambda L, h, w: L.olsr_hr_net_workspace_bytes(h, w, 1, 1, 1, 1), [(1, (1, 3)), (1, (1, 3))], [], False),
 ]
 
 

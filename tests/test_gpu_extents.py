@@ -18,30 +18,30 @@ Shapes straddle the kernels' block quanta; each row of the table names the quant
 | olsr_forward + olsr_backward, non-finite rows | the mixture scene of tests/nonfinite_scenes.py at P 257: 45x30 with 15 language channels (tile 15), 64x48 with none (tile 16); both binnings and modes, misaligned as well | as above; radii 0, 2^20 - 1, 2^20 and 2^31 - 1, NaN and infinite means, depths and conics | as above |
 | forced sort paths | P 1025, both tiles and modes | legacy passes, kpt 2/4/8/12/16 x 256/1024 threads, one-launch sort off, compaction off | as above |
 | olsr_forward_async | binning sized for R, R + 1, R - 1 (overflow) | carve by capacity | state: Carver |
-| olsr_debug_backward_ordered | P 257 | one row per instance | by hand in olsr_diag.hip (outer guards only) |
+| olsr_debug_backward_ordered | P 257 | one row per instance | Carver (rows, then the flag bytes) |
 | olsr_knn_mean_dist2 | P 1, 2, 3, 4, 63, 64, 65, 4095, 4096, 4097 | KNN_BOX 64, superbox 64 boxes = 4096, SORT_CHUNK 4096 | Carver |
 | olsr_mark_visible | P 1, 255, 257 | 256 threads | none |
 | olsr_mask_smooth, olsr_query_eval | 64x64, 65x63, 70x75 | QE_TILE 64 | Carver |
 | olsr_image_psnr | n 1, 3, 4, 5, 1024 * 1024 + 1 | 4 elements / thread, 256 threads, 1024 blocks (grid-stride beyond) | Carver |
-| olsr_accumulate_gradients, olsr_bucket_add, olsr_isotropic_reg | P 1, 63, 64, 65, 129; M 1, 16; F 0, 15, 32 | 64 rows / wave, 256 / block (ISO_T 256) | isotropic_reg: by hand, doubles from the pointer as it is: no misaligned run |
+| olsr_accumulate_gradients, olsr_bucket_add, olsr_isotropic_reg | P 1, 63, 64, 65, 129; M 1, 16; F 0, 15, 32 | 64 rows / wave, 256 / block (ISO_T 256) | isotropic_reg: Carver (one double per block) |
 | olsr_sparse_exchange_mask / _pack / _unpack | P 1, 1023, 1024, 1025; capacity = rows, rows - 1 | 1024 rows per scan block (scratch ints) | int32[ceil(P / 1024)] from the caller |
 | olsr_adam_step, _sum, _masked, _groups, _groups_reg | P 1, 63, 64, 65, 129; M 1, 16; F 0, 15, 32 | 64 rows per mask word, 256 per block | none: parameters, moments, buckets and masks between guards |
-| olsr_grad_mask | global: 65x63, 64x64, 17x241 (4095, 4096, 4097 pixels); blocks: 65x63, 64x64, 33x65 | FE_CHUNK 4096, 256 threads, 32 x 32 image blocks | by hand in k_frontend.hip from the pointer as it is: no misaligned run |
+| olsr_grad_mask | global: 65x63, 64x64, 17x241 (4095, 4096, 4097 pixels); blocks: 65x63, 64x64, 33x65 | FE_CHUNK 4096, 256 threads, 32 x 32 image blocks | Carver (global mode; the block mode takes none) |
 | olsr_median_depth | N 1, 4095, 4096, 4097; a mask and none | FE_CHUNK 4096 | as above |
 | olsr_covisibility, olsr_keyframe_decide | P 1, 2047, 2048, 2049; K 0, 1, 16 | 8 Gaussians per thread, 2048 per block | none |
-| olsr_mapping_loss, olsr_tracking_loss | 45x30 (a width that is no multiple of 4), 157x101; F 0, 15; a mask and none | four pixels per load, blocks of 256 | per-block partials, base rounded up by hand (outer guards) |
-| olsr_refinement_loss | 45x30, 157x101 | 32 x 16 tiles | partials and three [3,H,W] planes, base rounded up by hand (outer guards) |
+| olsr_mapping_loss, olsr_tracking_loss | 45x30 (a width that is no multiple of 4), 157x101; F 0, 15; a mask and none | four pixels per load, blocks of 256 | Carver (per-block partials) |
+| olsr_refinement_loss | 45x30, 157x101 | 32 x 16 tiles | Carver (partials; the three [3,H,W] planes as one array) |
 | olsr_emd_cost, olsr_chamfer | B 1 and 3 with one empty segment; 255 / 257 / 65 / 63 points | CM_TILE 256 | Carver |
 | olsr_debug_activate | P 1, 255, 256, 257 | 256 threads | none |
 | olsr_pose_step, _gated, olsr_window_pose_step | V 1, 3 | one wave per view, an 80-float state and 2 status words each | none |
-| olsr_forward_async_loss | 45x30 (tile 15), 157x101 (tile 16); mapping with 15 language channels, tracking with a mask | the composite's tiles; a width that is no multiple of 4 | state: Carver; the loss's per-tile partials: by hand (outer guards) |
-| olsr_lang_ae_train_step / _encode / _decode | N 1, 255, 256, 257; codes as rows and as channels | 256 rows per block, one partial gradient per block | by hand (outer guards) |
-| olsr_lang_query_sims / _relevancy | 24x40, 33x31 | 64 pixels per tile of stage A (960 = 15 tiles, 1023 = 16 less one) | by hand (outer guards) |
+| olsr_forward_async_loss | 45x30 (tile 15), 157x101 (tile 16); mapping with 15 language channels, tracking with a mask | the composite's tiles; a width that is no multiple of 4 | state: Carver; the loss's per-tile partials: Carver |
+| olsr_lang_ae_train_step / _encode / _decode | N 1, 255, 256, 257; codes as rows and as channels | 256 rows per block, one partial gradient per block | Carver (train step; encode and decode take none) |
+| olsr_lang_query_sims / _relevancy | 24x40, 33x31 | 64 pixels per tile of stage A (960 = 15 tiles, 1023 = 16 less one) | Carver (relevancy; sims takes none) |
 | olsr_lang_encoder_encode | N 1, 63, 64, 65; both code layouts | 64 rows per block | none |
 | olsr_hr_net_forward | its golden sizes, 2x3 and 3x5 coarse pixels | no multiple of any tile | workspace by hand, 16-byte aligned by contract: no misaligned run |
-| olsr_tsdf_init / _integrate / _surface_* / _mesh_* | 8x8x8, 9x7x5; vertex and face capacity = the planned count, and one less | 256 voxels per block (512 = two blocks, 315 = one and a ragged one) | by hand (outer guards) |
-| olsr_map_edit_plan / _apply | P 1, 255, 256, 257; the destination holds exactly P_new rows | 256 source rows per block | by hand (outer guards) |
-| olsr_keyframe_seed_plan / _finish | 40x24, the smallest golden image; the staging holds exactly (W H) / downsample rows | - | by hand (outer guards); the kNN scratch: Carver |
+| olsr_tsdf_init / _integrate / _surface_* / _mesh_* | 8x8x8, 9x7x5; vertex and face capacity = the planned count, and one less | 256 voxels per block (512 = two blocks, 315 = one and a ragged one) | Carver (surface and mesh; init and integrate take none) |
+| olsr_map_edit_plan / _apply | P 1, 255, 256, 257; the destination holds exactly P_new rows | 256 source rows per block | Carver |
+| olsr_keyframe_seed_plan / _finish | 40x24, the smallest golden image; the staging holds exactly (W H) / downsample rows | - | Carver; the kNN scratch: Carver |
 
 Floating-point atomics: none of the entries above accumulates with them (the backward sums rows in a fixed order, the losses
 and metrics add per-block partials in block order), so every row compares the guarded runs with the plain run by bits.
@@ -646,8 +646,7 @@ def test_bucket_add(hip, P, masked):
 @pytest.mark.parametrize("P", BUCKET_P + (255, 256, 257))
 def test_isotropic_reg(hip, P):
     """Yardstick: tests/window_ba_ref.py — the gradient bit for bit, the loss within 6 x 2^-24 x weight x max s of the float64
-    statement (tests/test_gpu_mapping_ba.py::test_isotropic_reg).  The scratch is laid out by hand (one double per block of 256
-    rows and the total, from the pointer as it is): outer guards only, and no misaligned run — doubles need their alignment."""
+    statement (tests/test_gpu_mapping_ba.py::test_isotropic_reg).  The scratch is carved: one double per block of 256 rows."""
     import window_ba_ref as ref
     from test_gpu_adam import A
     from test_gpu_mapping_ba import ISO_LOSS_BOUND
@@ -659,9 +658,9 @@ def test_isotropic_reg(hip, P):
 
     def entry(case):
         grad, loss = case.new("grad", (P, 3), F32), case.new("loss", (1,), torch.float64)
-        scratch = case.scratch(L.olsr_isotropic_reg_scratch_bytes(P), misalign_ok=False)
+        scratch = case.scratch(L.olsr_isotropic_reg_scratch_bytes(P))
         _check_rc(L.olsr_isotropic_reg(P, x.data_ptr(), 0, weight, grad.data_ptr(), loss.data_ptr(), scratch.data_ptr(), _stream()))
-    out = three_ways(entry, misaligned=False)
+    out = three_ways(entry)
     want, _ = ref.isotropic_rows(s, False, weight)
     assert A.same_bits(out["grad"].cpu().numpy(), want).all()
     assert abs(float(out["loss"]) - float(ref.isotropic_loss(s, False, weight))) <= ISO_LOSS_BOUND * weight * s.max()
@@ -794,8 +793,8 @@ def test_sparse_exchange(hip, P):
 
 # ------------------------------------------------------------------------------------------------ the front end
 # k_frontend.hip: 256 threads, 16 elements per thread of a pass over N (FE_CHUNK = 4096), the threshold pass one pixel per
-# thread (256), the covisibility pass 8 Gaussians per thread (2048 per block).  The scratch is laid out by hand from the pointer
-# as it is (a 64-byte state with 64-bit words, four histograms, N keys): outer guards only, no misaligned run.
+# thread (256), the covisibility pass 8 Gaussians per thread (2048 per block).  The scratch is carved: the select's state, four
+# histograms, N keys.
 @pytest.mark.parametrize("W,Hh,mode", [(65, 63, "global"), (64, 64, "global"), (17, 241, "global"),   # 4095, 4096, 4097 pixels
                                        (65, 63, "blocks"), (64, 64, "blocks"), (33, 65, "blocks")])   # blocks of 1 x 2 / 2 x 2 / 2 x 1
 def test_grad_mask(hip, W, Hh, mode):
@@ -809,9 +808,9 @@ def test_grad_mask(hip, W, Hh, mode):
 
     def entry(case):
         mask = case.new("mask", (Hh, W), F32)
-        scratch = case.scratch(L.olsr_frontend_scratch_bytes(N), misalign_ok=False) if mode == "global" else None
+        scratch = case.scratch(L.olsr_frontend_scratch_bytes(N)) if mode == "global" else None
         _check_rc(L.olsr_grad_mask(W, Hh, N, 0 if mode == "blocks" else 1, thr, t.data_ptr(), mask.data_ptr(), _p(scratch), _stream()))
-    out = three_ways(entry, misaligned=False)
+    out = three_ways(entry)
     assert same(out["mask"].cpu().numpy(), want)
 
 
@@ -825,10 +824,10 @@ def test_median_depth(hip, N):
     for mask, dev_mask in ((None, None), (m, tm)):
         def entry(case):
             med, cnt = case.new("median", (1,), F32), case.new("count", (1,), I32)
-            scratch = case.scratch(L.olsr_frontend_scratch_bytes(N), misalign_ok=False)
+            scratch = case.scratch(L.olsr_frontend_scratch_bytes(N))
             _check_rc(L.olsr_median_depth(N, td.data_ptr(), to.data_ptr(), _p(dev_mask), scratch.data_ptr(), med.data_ptr(),
                                           cnt.data_ptr(), _stream()))
-        out = three_ways(entry, misaligned=False)
+        out = three_ways(entry)
         want, n = R.median_depth(d, o, mask)
         assert int(out["count"]) == n and same(out["median"].cpu().numpy()[0], np.float32(want))
 
@@ -871,7 +870,7 @@ def test_covisibility_and_keyframe_decide(hip, P):
 
 # ------------------------------------------------------------------------------------------------ the losses
 # 45 x 30: a width that is no multiple of 4 (the pixel passes load four pixels where a row allows it), 157 x 101: several blocks
-# each way with ragged edges.  Scratch: per-block partial sums behind a base the entries round up by hand (outer guards only).
+# each way with ragged edges.  Scratch: per-block partial sums, carved.
 LOSS_SIZES = [(45, 30), (157, 101)]
 
 
@@ -958,7 +957,7 @@ def test_tracking_loss(hip, W, Hh, masked):
 @pytest.mark.parametrize("W,Hh", LOSS_SIZES)
 def test_refinement_loss(hip, W, Hh):
     """Yardstick: tests/ssim_ref.py in float64, the error held to a multiple of the float32 restatement's own
-    (tests/test_gpu_ssim.py's _check).  Scratch: partial sums and three [3,H,W] planes behind a base rounded up by hand."""
+    (tests/test_gpu_ssim.py's _check).  Scratch: partial sums and three [3,H,W] planes (one array), carved."""
     import ssim_ref
     import test_gpu_ssim as TS
     L = _L()
@@ -1169,8 +1168,7 @@ def test_forward_async_loss(hip, W, Hh, tile, tracking):
     """olsr_forward_async_loss: the forward with the mapping (15 language channels) or the tracking loss (with a gradient mask)
     in the composite's epilogue.  Yardstick: the two-kernel path on the same render, under the assertions of
     tests/test_gpu_loss.py::test_fused_mapping_loss_equals_the_two_kernel_path — images and cotangents bit for bit, the loss
-    under _close, the exposure gradient within FUSED_EXPOSURE_ATOL.  State buffers: Carver; the loss's per-tile partial sums:
-    by hand (outer guards)."""
+    under _close, the exposure gradient within FUSED_EXPOSURE_ATOL.  State buffers and the loss's per-tile partial sums: Carver."""
     import test_gpu_loss as TL
     from online_lang_splatting_amd import losses
     L = _L()
@@ -1206,7 +1204,7 @@ def test_forward_async_loss(hip, W, Hh, tile, tracking):
         g = dict(loss=case.new("loss", (4,), F32), dL_dimage=case.new("dL_dimage", (3, Hh, W), F32),
                  dL_ddepth=case.new("dL_ddepth", (1, Hh, W), F32), dL_dexposure=case.new("dL_dexposure", (2,), F32),
                  dL_dlanguage=case.new("dL_dlanguage", (F, Hh, W), F32) if lang else None)
-        scratch = case.scratch(L.olsr_fused_loss_scratch_bytes(W, Hh, tile), misalign_ok=False)
+        scratch = case.scratch(L.olsr_fused_loss_scratch_bytes(W, Hh, tile))
         lf = _abi.OlsrLossFusion(params=p, tracking=int(tracking), skip_images=0, gt_image=_p(c["gt_image"]), gt_depth=_p(c["gt_depth"]),
                                  gt_language=_p(c["gt_lang"]) if lang else None, exposure=_p(expo),
                                  grad_mask=_p(c["grad_mask"]) if tracking else None, dL_dimage=_p(g["dL_dimage"]),
@@ -1230,8 +1228,8 @@ def test_forward_async_loss(hip, W, Hh, tile, tracking):
 
 
 # ------------------------------------------------------------------------------------------------ the language codec
-# k_lang_codec.hip: 256 rows per block, one float32 partial gradient [2351] per block in the scratch (laid out by hand: outer
-# guards, no misaligned run): one row, one row short of a block, a whole block, one row into the second
+# k_lang_codec.hip: 256 rows per block, one float32 partial gradient [2351] per block in the scratch (carved: the gradient
+# partials, then the loss partials): one row, one row short of a block, a whole block, one row into the second
 _CODEC_REFS = {}
 
 
@@ -1266,10 +1264,10 @@ def test_lang_ae(hip, N, layout):
         m, v = case.inout("exp_avg", torch.zeros_like(fd)), case.inout("exp_avg_sq", torch.zeros_like(fd))
         step = case.inout("step", torch.zeros(1, dtype=I32, device=DEV))
         loss, codes, grad = case.new("loss", (4,), F32), case.new("codes", code_shape, F32), case.new("grad", (R.N_PARAMS,), F32)
-        scratch = case.scratch(L.olsr_lang_ae_scratch_bytes(N), misalign_ok=False)
+        scratch = case.scratch(L.olsr_lang_ae_scratch_bytes(N))
         _check_rc(L.olsr_lang_ae_train_step(C.byref(hp), N, xd.data_ptr(), params.data_ptr(), m.data_ptr(), v.data_ptr(), step.data_ptr(),
                                             loss.data_ptr(), codes.data_ptr(), grad.data_ptr(), scratch.data_ptr(), _stream()))
-    out = three_ways(train, misaligned=False)
+    out = three_ways(train)
     label = f"N = {N} {layout}"
     grad, loss = out["grad"].cpu(), out["loss"].cpu()
     codes = out["codes"].cpu() if layout == "rows" else out["codes"].cpu().t()
@@ -1298,7 +1296,7 @@ def test_lang_ae(hip, N, layout):
 
 # ------------------------------------------------------------------------------------------------ text queries
 # k_lang_query.hip: stage A takes 64 pixels per tile of the matrix cores, stage B works in 16 x 16 and 32 x 8 pixel tiles: 24 x 40
-# = 960 pixels is 15 whole tiles of 64, 33 x 31 = 1023 one pixel short of 16, with odd extents.  Scratch: by hand (outer guards).
+# = 960 pixels is 15 whole tiles of 64, 33 x 31 = 1023 one pixel short of 16, with odd extents.  Scratch: carved.
 @pytest.mark.parametrize("h,w,n_pos,n_labels", [(24, 40, 3, 2), (33, 31, 2, 0)])
 def test_lang_query(hip, h, w, n_pos, n_labels):
     """olsr_lang_query_sims and _relevancy at the codes' own size.  Yardstick: tests/lang_query_ref.py under the statements of
@@ -1326,12 +1324,12 @@ def test_lang_query(hip, h, w, n_pos, n_labels):
                  mask=case.new("mask", (n_pos, h, w), U8))
         if n_labels > 0:
             o["labels"] = case.new("labels", (h, w), I32)
-        scratch = case.scratch(L.olsr_lang_query_scratch_bytes(C.byref(p)), misalign_ok=False)
+        scratch = case.scratch(L.olsr_lang_query_scratch_bytes(C.byref(p)))
         _check_rc(L.olsr_lang_query_relevancy(C.byref(p), sims.data_ptr(), o["relevancy"].data_ptr(), o["smoothed"].data_ptr(),
                                               o["blended"].data_ptr(), o["score"].data_ptr(), o["coord"].data_ptr(),
                                               o["minmax"].data_ptr(), o["mask"].data_ptr(), _p(o.get("labels")), scratch.data_ptr(),
                                               _stream()))
-    out = three_ways(relevancy, misaligned=False)
+    out = three_ways(relevancy)
     hip_out = {k: v.cpu() for k, v in out.items()}
     hip_out["similarities"] = sims.cpu()
     _check_outputs(f"{w} x {h}", case_, hip_out, t64, t32)
@@ -1401,7 +1399,8 @@ def test_hr_net_forward(hip):
 
 # ------------------------------------------------------------------------------------------------ TSDF fusion and extraction
 # k_tsdf.hip: a voxel per thread, 256 per block; the extraction counts and prefixes per block of 256 voxels.  8 x 8 x 8 = 512
-# voxels: two whole blocks; 9 x 7 x 5 = 315: one and a ragged one, odd extents.  Scratch: by hand (outer guards).
+# voxels: two whole blocks; 9 x 7 x 5 = 315: one and a ragged one, odd extents.  Scratch: carved (the block counts and offsets;
+# for the mesh the vertices' and the faces', then the voxel words).
 @pytest.mark.parametrize("dim", [(8, 8, 8), (9, 7, 5)])
 def test_tsdf(hip, dim):
     """olsr_tsdf_init + _integrate (five views in one launch), _surface_plan / _emit and _mesh_plan / _emit with capacities equal
@@ -1442,13 +1441,13 @@ def test_tsdf(hip, dim):
     assert n > 1
     for cap in (n, n - 1):
         def surface(case):
-            scratch = case.scratch(L.olsr_tsdf_surface_scratch_bytes(X, Y, Z), misalign_ok=False)
+            scratch = case.scratch(L.olsr_tsdf_surface_scratch_bytes(X, Y, Z))
             status = case.new("status", (2,), I32)
             _check_rc(L.olsr_tsdf_surface_plan(C.byref(vol), 0.0, scratch.data_ptr(), status.data_ptr(), _stream()))
             pts, fe, idx = case.new("points", (cap, 3), F32), case.new("feats", (cap, feature), F32), case.new("index", (cap,), I32)
             _check_rc(L.olsr_tsdf_surface_emit(C.byref(vol), 0.0, scratch.data_ptr(), cap, pts.data_ptr(), fe.data_ptr(), idx.data_ptr(),
                                                _stream()))
-        out = three_ways(surface, misaligned=False)
+        out = three_ways(surface)
         assert out["status"].tolist() == [n, 0]
         assert torch.equal(out["index"].cpu(), torch.from_numpy(want[2][:cap])), "order"
         assert torch.equal(out["points"].cpu(), torch.from_numpy(want[0][:cap])), "points"
@@ -1459,14 +1458,14 @@ def test_tsdf(hip, dim):
     assert nv == n and nf > 1
     for cv, cf in ((nv, nf), (nv - 1, nf - 1)):
         def extract(case):
-            scratch = case.scratch(L.olsr_tsdf_mesh_scratch_bytes(X, Y, Z), misalign_ok=False)
+            scratch = case.scratch(L.olsr_tsdf_mesh_scratch_bytes(X, Y, Z))
             status = case.new("status", (4,), I32)
             _check_rc(L.olsr_tsdf_mesh_plan(C.byref(vol), 0.0, scratch.data_ptr(), status.data_ptr(), _stream()))
             o = dict(verts=case.new("verts", (cv, 3), F32), norms=case.new("norms", (cv, 3), F32), colors=case.new("colors", (cv, feature), F32),
                      index=case.new("index", (cv,), I32), faces=case.new("faces", (cf, 3), I32))
             _check_rc(L.olsr_tsdf_mesh_emit(C.byref(vol), 0.0, scratch.data_ptr(), cv, cf, o["verts"].data_ptr(), o["norms"].data_ptr(),
                                             o["colors"].data_ptr(), o["index"].data_ptr(), o["faces"].data_ptr(), _stream()))
-        out = three_ways(extract, misaligned=False)
+        out = three_ways(extract)
         assert out["status"].tolist() == [nv, nf, 0, 0]
         assert torch.equal(out["faces"].cpu(), torch.from_numpy(mesh[1][:cf])), "faces"
         assert torch.equal(out["index"].cpu(), torch.from_numpy(want[2][:cv])), "vertex owners"
@@ -1475,8 +1474,9 @@ def test_tsdf(hip, dim):
 
 
 # ------------------------------------------------------------------------------------------------ map edits
-# k_map_edit.hip: a source row per thread, 256 per block (the plan's segment counts are per block).  Scratch: by hand (outer
-# guards).  The destination holds exactly P_new rows (dst_capacity = P_new): every word of it is written.
+# k_map_edit.hip: a source row per thread, 256 per block (the plan's segment counts are per block).  Scratch: carved
+# (class bytes, block counts, block offsets).  The destination holds exactly P_new rows (dst_capacity = P_new): every word of it
+# is written.
 @pytest.mark.parametrize("P", [1, 255, 256, 257])
 def test_map_edit(hip, P):
     """olsr_map_edit_plan + _apply in densify mode (clones, splits and drops).  Yardstick: MapSpec, the CPU specification, under
@@ -1498,7 +1498,7 @@ def test_map_edit(hip, P):
                  exp_avg_sq=(width,), kf_id=(), n_obs=(), stats=(2,), max_radii=())
 
     def entry(case):
-        scratch = case.scratch(L.olsr_map_edit_scratch_bytes(P), misalign_ok=False)
+        scratch = case.scratch(L.olsr_map_edit_scratch_bytes(P))
         status = case.new("status", (8,), I32)
         _check_rc(L.olsr_map_edit_plan(P, C.byref(ep), C.byref(src), None, scratch.data_ptr(), status.data_ptr(), _stream()))
         torch.cuda.synchronize()
@@ -1508,7 +1508,7 @@ def test_map_edit(hip, P):
         dst = m._struct(d)
         _check_rc(L.olsr_map_edit_apply(P, M, F, C.byref(ep), C.byref(src), zd.data_ptr(), None, scratch.data_ptr(), status.data_ptr(),
                                         n, n, C.byref(dst), _p(src_index), _stream()))
-    out = three_ways(entry, misaligned=False)
+    out = three_ways(entry)
     n = int(out["status"][0])
     assert n == want_src.numel()
     got = GaussianMap.from_state(st, FUSED_LRS, DEV)   # the plain run's destination, installed as a map's front buffers
@@ -1522,7 +1522,7 @@ def test_map_edit(hip, P):
 
 # ------------------------------------------------------------------------------------------------ keyframe seeding
 # k_keyframe_seed.hip on the smallest golden image, 40 x 24 = 960 pixels, downsample 8: the staging holds exactly the
-# (W H) / downsample = 120 rows the sample has, so every row is written.  Scratch: by hand (outer guards); the kNN scratch of
+# (W H) / downsample = 120 rows the sample has, so every row is written.  Scratch: carved; the kNN scratch of
 # olsr_keyframe_seed_finish is olsr_knn_mean_dist2's (Carver).
 def test_keyframe_seed(hip):
     """olsr_keyframe_seed_plan + _finish.  Yardstick: tests/keyframe_seed_ref.py under tests/test_gpu_keyframe_seed.py's
@@ -1545,7 +1545,7 @@ def test_keyframe_seed(hip):
         st = {k: case.new(k, (cap,) + tail, F32) for k, tail in tails.items()}
         pix = case.new("pix_index", (cap,), I32)
         rows = _abi.OlsrMapBuffers(**{k: st[k].data_ptr() for k in tails})
-        scratch = case.scratch(L.olsr_keyframe_seed_scratch_bytes(W, Hh), misalign_ok=False)
+        scratch = case.scratch(L.olsr_keyframe_seed_scratch_bytes(W, Hh))
         status, aux = case.new("status", (8,), I32, written=False), case.new("aux", (4,), F32)
         _check_rc(L.olsr_keyframe_seed_plan(C.byref(p), img.data_ptr(), dep.data_ptr(), None, w2c.data_ptr(), C.byref(rows),
                                             pix.data_ptr(), scratch.data_ptr(), status.data_ptr(), aux.data_ptr(), _stream()))
@@ -1555,7 +1555,7 @@ def test_keyframe_seed(hip):
         _check_rc(L.olsr_keyframe_seed_finish(C.byref(p), n_keep, C.byref(rows), aux.data_ptr(), scratch.data_ptr(), knn.data_ptr(),
                                               _stream()))
         case.out["status"] = status[:2]
-    out = three_ways(entry, misaligned=False)
+    out = three_ways(entry)
     n_keep = int(out["status"][1])
     got = {k: out[k][:n_keep] for k in list(tails) + ["pix_index"]}
     got.update(n_valid=out["status"][0], median_depth=out["aux"][0], point_size=out["aux"][1], n_keep=n_keep)

@@ -97,10 +97,11 @@ def test_entries_validate_their_arguments(L):
 
 
 def test_surface_scratch_size(L):
-    # two int32 per block of 256 voxels, and 16 bytes
-    assert L.olsr_tsdf_surface_scratch_bytes(1, 1, 1) == 2 * 4 + 16
-    assert L.olsr_tsdf_surface_scratch_bytes(400, 250, 150) == 2 * 4 * -(-400 * 250 * 150 // 256) + 16
-    assert L.olsr_tsdf_surface_scratch_bytes(0, 5, 5) == 16
+    # two int32 per block of 256 voxels in two carved sub-arrays: each may be padded to 256 bytes, and the base takes up to 256
+    # more (tests/test_extents_cpu.py checks the layout itself)
+    slack = 256 * (2 + 1)
+    for dim, payload in (((1, 1, 1), 2 * 4), ((400, 250, 150), 2 * 4 * -(-400 * 250 * 150 // 256)), ((0, 5, 5), 0)):
+        assert payload <= L.olsr_tsdf_surface_scratch_bytes(*dim) <= payload + slack, dim
 
 
 def test_python_side_without_a_gpu():
