@@ -52,7 +52,7 @@ UNITS = [
     ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),
     ("k_query_eval.hip", "k_query_eval.o", []),
 ]
-HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h"),
+HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_select.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h"),
            os.path.join("..", "..", "include", "olsr_single_stage.h")]
 
 

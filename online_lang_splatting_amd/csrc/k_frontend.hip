@@ -14,11 +14,15 @@
 //   median_depth       keys of the valid depths + first digit, the same select; median and count stay on the device
 //   covisibility       one pass over n_touched and the K visibilities: |cur|, |cur & vis_k|, |vis_k| (integer atomics)
 //   keyframe_decide    one wave: reads the counts and the median word on the device, writes one record for the host
-// The select is written once (select_count / select_hist_kernel / select_digit_kernel / launch_select); its histograms are
-// integer atomics — order-independent —, nothing else is atomic: two runs give the same bits.  The arithmetic is pinned
+// The select's steps — counting a key, flushing a histogram, narrowing to the rank's bucket — are olsr_select.h's, shared with
+// k_keyframe_seed.hip.  Here they run in two forms: over keys in global scratch (select_hist_kernel / select_digit_kernel /
+// launch_select, behind a key kernel that counts digit 0) and over a block's intensities in LDS (grad_mask_blocks_kernel).
+// An element that takes no part is stored as FE_NO_KEY and kept out by select_count's `takes_part` argument.  The histograms
+// are integer atomics — order-independent —, nothing else is atomic: two runs give the same bits.  The arithmetic is pinned
 // statement by statement in include/olsr.h; the translation unit is compiled without FMA contraction (build.py).
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_select.h"
 
 namespace olsr {
 
@@ -26,8 +30,7 @@ constexpr int FE_THREADS = 256;
 constexpr int FE_WAVES = FE_THREADS / 64;
 constexpr int FE_PER_THREAD = 16;                 // elements per thread of a pass over N
 constexpr int FE_CHUNK = FE_THREADS * FE_PER_THREAD;
-constexpr int FE_PASSES = 4;                      // 8-bit digits, most significant first
-constexpr u32 FE_NO_KEY = 0xFFFFFFFFu;            // an element that takes no part (no key of a valid element: a NaN pattern)
+constexpr u32 FE_NO_KEY = 0xFFFFFFFFu;            // stored for an element that takes no part (no valid element's key: a NaN pattern)
 constexpr int FE_GRID_BLOCKS = 32;                // the reference's 32 x 32 image blocks
 constexpr int FE_COVIS_PER_THREAD = 8;
 
@@ -42,13 +45,13 @@ struct SelectState {
 
 struct FeScratch {
   SelectState* state;
-  u32* hist;   // [FE_PASSES][256]
+  u32* hist;   // [SELECT_PASSES][256]
   u32* keys;   // [n]
   static FeScratch carve(void* buf, size_t n, size_t& bytes) {
     Carver c(buf);
     FeScratch s;
     s.state = c.take<SelectState>(1);
-    s.hist = c.take<u32>(FE_PASSES * 256);
+    s.hist = c.take<u32>(SELECT_PASSES * 256);
     s.keys = c.take<u32>(n);
     bytes = c.total();
     return s;
@@ -61,19 +64,6 @@ size_t frontend_scratch_bytes(int64_t n) {
   return bytes;
 }
 
-// one key into the workgroup's histogram h[256] of `pass`, when it shares the prefix of the passes before
-__device__ __forceinline__ void select_count(u32* h, u32 key, int pass, u32 prefix) {
-  if (key == FE_NO_KEY) return;
-  const int shift = 24 - 8 * pass;
-  if (pass > 0 && (key >> (shift + 8)) != prefix) return;
-  atomicAdd(&h[(key >> shift) & 255u], 1u);
-}
-// the workgroup's histogram into the pass's global one (between two barriers of the caller)
-__device__ __forceinline__ void select_flush(const u32* h, u32* g) {
-  const u32 c = h[threadIdx.x];
-  if (c) atomicAdd(&g[threadIdx.x], c);
-}
-
 // digit `pass` (1 ... 3) of the stored keys
 __global__ __launch_bounds__(FE_THREADS) void select_hist_kernel(int64_t N, int pass, FeScratch sc) {
   __shared__ u32 h[256];
@@ -84,7 +74,8 @@ __global__ __launch_bounds__(FE_THREADS) void select_hist_kernel(int64_t N, int 
   for (int r = 0; r < FE_PER_THREAD; ++r) {
     const int64_t i = base + (int64_t)r * FE_THREADS + threadIdx.x;
     if (i >= N) break;
-    select_count(h, sc.keys[i], pass, prefix);
+    const u32 key = sc.keys[i];
+    select_count(h, key != FE_NO_KEY, key, pass, prefix);
   }
   __syncthreads();
   select_flush(h, sc.hist + pass * 256);
@@ -115,16 +106,13 @@ __global__ __launch_bounds__(FE_THREADS) void select_digit_kernel(int pass, FeSc
     s_rank = rank;
   }
   __syncthreads();
-  if (cnt && excl <= rank && rank < excl + cnt) {   // one thread at most
-    s_prefix = (prefix << 8) | (u32)t;
-    s_rank = rank - excl;
-  }
+  select_narrow(cnt, excl, prefix, rank, &s_prefix, &s_rank);   // one thread at most
   __syncthreads();
   if (t == 0) {
     sc.state->prefix = s_prefix;
     sc.state->rank = s_rank;
     sc.state->n = n;
-    if (pass == FE_PASSES - 1) {
+    if (pass == SELECT_PASSES - 1) {
       if (out_median) out_median[0] = n > 0u ? bits2f(s_prefix) : __builtin_nanf("");
       if (out_count) out_count[0] = (int32_t)n;
     }
@@ -134,7 +122,7 @@ __global__ __launch_bounds__(FE_THREADS) void select_digit_kernel(int pass, FeSc
 // the passes after the caller's key kernel, which stored the keys and counted digit 0 into sc.hist[0 .. 256)
 static void launch_select(int64_t N, const FeScratch& sc, float* out_median, int32_t* out_count, hipStream_t st) {
   const int hb = (int)((N + FE_CHUNK - 1) / FE_CHUNK);
-  for (int pass = 0; pass < FE_PASSES; ++pass) {
+  for (int pass = 0; pass < SELECT_PASSES; ++pass) {
     if (pass > 0) select_hist_kernel<<<hb, FE_THREADS, 0, st>>>(N, pass, sc);
     select_digit_kernel<<<1, FE_THREADS, 0, st>>>(pass, sc, out_median, out_count);
   }
@@ -225,20 +213,18 @@ __global__ __launch_bounds__(FE_THREADS) void grad_mask_blocks_kernel(int W, int
   __syncthreads();
   // the lower median of the n intensities: four 8-bit digits, most significant first
   u32 prefix = 0u, rank = (u32)((n - 1) / 2);
-  for (int pass = 0; pass < FE_PASSES; ++pass) {
+  for (int pass = 0; pass < SELECT_PASSES; ++pass) {
     s_h[t] = 0u;
     __syncthreads();
     for (int i = t; i < n; i += FE_THREADS) {
       const int y = i / bw;
-      select_count(s_h, f2bits(s_p[y * pw + (i - y * bw)]), pass, prefix);
+      const u32 key = f2bits(s_p[y * pw + (i - y * bw)]);
+      select_count(s_h, key != FE_NO_KEY, key, pass, prefix);
     }
     __syncthreads();
     const u32 cnt = s_h[t];
     const u32 excl = block_excl_scan<FE_WAVES>(cnt, s_w);
-    if (cnt && excl <= rank && rank < excl + cnt) {   // exactly one thread: n >= 1
-      s_prefix = (prefix << 8) | (u32)t;
-      s_rank = rank - excl;
-    }
+    select_narrow(cnt, excl, prefix, rank, &s_prefix, &s_rank);   // exactly one thread: n >= 1
     __syncthreads();
     prefix = s_prefix;
     rank = s_rank;
@@ -265,7 +251,7 @@ __global__ __launch_bounds__(FE_THREADS) void grad_intensity_keys_kernel(int W, 
     const int y = (int)(i / W), x = (int)(i - (int64_t)y * W);
     const u32 key = f2bits(intensity_global(img, ps, W, H, y, x));
     sc.keys[i] = key;
-    select_count(h, key, 0, 0u);
+    select_count(h, key != FE_NO_KEY, key, 0, 0u);
   }
   __syncthreads();
   select_flush(h, sc.hist);
@@ -292,7 +278,7 @@ hipError_t launch_grad_mask(int W, int H, int64_t plane_stride, int mode, float 
   }
   size_t bytes;
   const FeScratch sc = FeScratch::carve(scratch, (size_t)N, bytes);
-  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
+  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SELECT_PASSES * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   grad_intensity_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(W, H, plane_stride, image, sc);
   launch_select(N, sc, nullptr, nullptr, st);
@@ -315,7 +301,7 @@ __global__ __launch_bounds__(FE_THREADS) void median_depth_keys_kernel(int64_t N
     const bool valid = d > 0.0f && opacity[i] > 0.95f && (mask == nullptr || mask[i] != 0);   // NaN > 0 is false
     const u32 key = valid ? f2bits(d) : FE_NO_KEY;
     sc.keys[i] = key;
-    select_count(h, key, 0, 0u);
+    select_count(h, key != FE_NO_KEY, key, 0, 0u);
   }
   __syncthreads();
   select_flush(h, sc.hist);
@@ -325,7 +311,7 @@ hipError_t launch_median_depth(int64_t N, const float* depth, const float* opaci
                                float* median, int32_t* count, hipStream_t st) {
   size_t bytes;
   const FeScratch sc = FeScratch::carve(scratch, (size_t)N, bytes);
-  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)FE_PASSES * 256 * sizeof(u32), st);
+  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SELECT_PASSES * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   median_depth_keys_kernel<<<(int)((N + FE_CHUNK - 1) / FE_CHUNK), FE_THREADS, 0, st>>>(N, depth, opacity, mask, sc);
   launch_select(N, sc, median, count, st);

@@ -14,7 +14,10 @@
 //             seed_emit               ranks the kept pixels of a block (wave ballots) and writes their rows, in pixel order
 //           The three selects share the passes: the lower and the upper middle element of d' over all W H pixels (the median,
 //           np.median at gaussian_model.py:204) and the n_keep-th smallest sampling key among the valid pixels.  The
-//           histograms are integer atomics — order-independent —, nothing else is atomic: two runs give the same bits.
+//           select's steps are olsr_select.h's (shared with k_frontend.hip); which pixels take part is said here, per
+//           select, and by no reserved key: fmix32 is a bijection, so 0xFFFFFFFF is the sampling key of one pixel index
+//           per seed.  The histograms are integer atomics — order-independent —, nothing else is atomic: two runs give
+//           the same bits.
 //   finish  olsr_knn_mean_dist2 on the n new points alone (as the reference does per keyframe), then
 //           scale = logf(sqrtf(max(d2, 1e-7f) * ps)) on all three axes.
 //
@@ -22,6 +25,7 @@
 // contraction (build.py), so the double back-projection and the exposure line are the operations the source writes.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
+#include "olsr_select.h"
 
 namespace olsr {
 
@@ -30,7 +34,6 @@ constexpr int SEED_WAVES = SEED_THREADS / 64;
 constexpr int SEED_PIX = SEED_THREADS;        // pixels per block of count / emit (one per thread)
 constexpr int SEED_HIST_PER_THREAD = 16;      // pixels per thread of a histogram pass
 constexpr int SEED_HIST_PIX = SEED_THREADS * SEED_HIST_PER_THREAD;
-constexpr int SEED_PASSES = 4;                // 8-bit digits, most significant first
 constexpr int SEED_SELECTS = 3;               // lower middle, upper middle of d'; the sampling key threshold
 constexpr int SEED_PREFIX_THREADS = 1024;
 
@@ -45,7 +48,7 @@ __host__ __device__ inline size_t seed_blocks(size_t N) { return (N + SEED_PIX -
 
 struct SeedScratch {
   SeedState* state;
-  u32* hist;       // [SEED_PASSES][SEED_SELECTS][256]
+  u32* hist;       // [SELECT_PASSES][SEED_SELECTS][256]
   u32* mkey;       // [N rounded up to 4] median key of d' per pixel; finish reuses the words as mean_dist2 [n]
   int32_t* counts; // [blocks of SEED_PIX]
   int32_t* offsets;
@@ -53,7 +56,7 @@ struct SeedScratch {
     Carver c(buf);
     SeedScratch s;
     s.state = c.take<SeedState>(1);
-    s.hist = c.take<u32>(SEED_PASSES * SEED_SELECTS * 256);
+    s.hist = c.take<u32>(SELECT_PASSES * SEED_SELECTS * 256);
     s.mkey = c.take<u32>((N + 3) / 4 * 4);
     s.counts = c.take<int32_t>(seed_blocks(N));
     s.offsets = c.take<int32_t>(seed_blocks(N));
@@ -91,10 +94,10 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_hist(int64_t N, int pass, o
   __shared__ u32 h[SEED_SELECTS][256];
   for (int s = 0; s < SEED_SELECTS; ++s) h[s][threadIdx.x] = 0u;
   __syncthreads();
-  const int shift = 24 - 8 * pass;
   u32 prefix[SEED_SELECTS] = {0u, 0u, 0u};
   bool live[SEED_SELECTS] = {true, true, true};
   if (!PASS0) {
+    __builtin_assume(pass > 0);   // (passes 1 ... 3, launch_keyframe_seed_plan: select_count's pass-0 case folds away)
     for (int s = 0; s < SEED_SELECTS; ++s) prefix[s] = sc.state->prefix[s];
     live[2] = sc.state->n_keep > 0;
   }
@@ -114,18 +117,11 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_hist(int64_t N, int pass, o
     const u32 keys[SEED_SELECTS] = {mk, mk, seed_sample_key((u32)i, p.seed)};
     const bool in[SEED_SELECTS] = {true, true, seed_valid(mk, p.depth_trunc)};
 #pragma unroll
-    for (int s = 0; s < SEED_SELECTS; ++s) {
-      if (!in[s] || !live[s]) continue;
-      if (!PASS0 && (keys[s] >> (shift + 8)) != prefix[s]) continue;
-      atomicAdd(&h[s][(keys[s] >> shift) & 255u], 1u);
-    }
+    for (int s = 0; s < SEED_SELECTS; ++s) select_count(h[s], in[s] && live[s], keys[s], PASS0 ? 0 : pass, prefix[s]);
   }
   __syncthreads();
   u32* g = sc.hist + (size_t)pass * SEED_SELECTS * 256;
-  for (int s = 0; s < SEED_SELECTS; ++s) {
-    const u32 c = h[s][threadIdx.x];
-    if (c) atomicAdd(&g[s * 256 + threadIdx.x], c);
-  }
+  for (int s = 0; s < SEED_SELECTS; ++s) select_flush(h[s], g + s * 256);
 }
 
 // One workgroup: for each select, the digit whose bucket holds the rank; after the last pass the status and aux words.
@@ -161,11 +157,7 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_select(int64_t N, int pass,
       if (n_keep > p.capacity) n_keep = p.capacity;   // (never: capacity >= W H / downsample is an argument check)
       rank[2] = n_keep > 0 ? (u32)(n_keep - 1) : 0u;
     }
-    const bool live = s < 2 || n_keep > 0;
-    if (live && cnt && excl <= rank[s] && rank[s] < excl + cnt) {
-      s_prefix[s] = (prefix[s] << 8) | (u32)t;
-      s_rank[s] = rank[s] - excl;
-    }
+    if (s < 2 || n_keep > 0) select_narrow(cnt, excl, prefix[s], rank[s], &s_prefix[s], &s_rank[s]);   // (live selects only)
     __syncthreads();   // s_w is rewritten by the next scan; s_prefix / s_rank are read below
   }
   if (t == 0) {
@@ -174,7 +166,7 @@ __global__ __launch_bounds__(SEED_THREADS) void seed_select(int64_t N, int pass,
     for (int s = 0; s < SEED_SELECTS; ++s) { sc.state->prefix[s] = s_prefix[s]; sc.state->rank[s] = s_rank[s]; }
     sc.state->n_valid = n_valid;
     sc.state->n_keep = n_keep;
-    if (pass == SEED_PASSES - 1) {
+    if (pass == SELECT_PASSES - 1) {
       const float a = bits2f(s_prefix[0]), b = bits2f(s_prefix[1]);
       float median = a;                       // odd N: the middle element
       if ((N & 1) == 0) { const float ab = a + b; median = ab / 2.0f; }
@@ -283,10 +275,10 @@ hipError_t launch_keyframe_seed_plan(const olsr_keyframe_seed_params& p, const f
   const int64_t N = (int64_t)p.W * p.H;
   size_t bytes;
   const SeedScratch sc = SeedScratch::carve(scratch, (size_t)N, bytes);
-  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SEED_PASSES * SEED_SELECTS * 256 * sizeof(u32), st);
+  const hipError_t e = hipMemsetAsync(sc.hist, 0, (size_t)SELECT_PASSES * SEED_SELECTS * 256 * sizeof(u32), st);
   if (e != hipSuccess) return e;
   const int hb = (int)((N + SEED_HIST_PIX - 1) / SEED_HIST_PIX), nb = (int)seed_blocks((size_t)N);
-  for (int pass = 0; pass < SEED_PASSES; ++pass) {
+  for (int pass = 0; pass < SELECT_PASSES; ++pass) {
     if (pass == 0) seed_hist<true><<<hb, SEED_THREADS, 0, st>>>(N, pass, p, image, depth, sc);
     else seed_hist<false><<<hb, SEED_THREADS, 0, st>>>(N, pass, p, image, depth, sc);
     seed_select<<<1, SEED_THREADS, 0, st>>>(N, pass, p, sc, status, aux);

@@ -161,6 +161,61 @@ def test_median_depth_golden(name):
     assert n == int(GOLD[f"med_{name}_count"]) and same(np.float32(got), np.float32(GOLD[f"med_{name}_median"]))
 
 
+ONE, BELOW_ONE, TWO, BELOW_TWO, INF = 0x3F800000, 0x3F7FFFFF, 0x40000000, 0x3FFFFFFF, 0x7F800000
+
+
+def last_digit_keys(N, at_zero=None):
+    """0x3F800000 + k, k a seeded permutation of 0 ... 255 repeated up to N elements: the keys differ in the last 8-bit digit
+    only.  at_zero: the permutation is rotated so that this k stands at the elements 0, 256, ..."""
+    k = np.random.default_rng(256).permutation(256)
+    if at_zero is not None:
+        k = np.roll(k, -int(np.nonzero(k == at_zero)[0][0]))
+    return (ONE + k[np.arange(N) % 256]).astype(np.uint32)
+
+
+def split(lo, n_lo, hi, n_hi):
+    return np.array([lo] * n_lo + [hi] * n_hi, dtype=np.uint32)
+
+
+# name -> (key bits, mask or None, the median's bits where they can be stated without the model, else None)
+SELECT_DIGIT_CASES = {
+    "last_digit_256": (last_digit_keys(256), None, 0x3F80007F),
+    "last_digit_257_one_repeated": (last_digit_keys(257), None, None),
+    "all_equal_65": (np.full(65, 0x40490FDB, dtype=np.uint32), None, 0x40490FDB),
+    "left_of_low_carry": (split(BELOW_ONE, 32, ONE, 32), None, BELOW_ONE),
+    "right_of_low_carry": (split(BELOW_ONE, 31, ONE, 33), None, ONE),
+    "left_of_top_carry": (split(BELOW_TWO, 32, TWO, 32), None, BELOW_TWO),
+    "right_of_top_carry": (split(BELOW_TWO, 31, TWO, 33), None, TWO),
+    "inf_is_the_median": (split(INF, 40, ONE, 25), None, INF),
+    # FE_CHUNK = 4096: element 4096 is the only one of the second histogram workgroup, and it decides between the two
+    # middle candidates 0x3F80007F and 0x3F800080 (asserted against the model below)
+    "second_workgroup_4097": (last_digit_keys(4097, at_zero=128), None, 0x3F800080),
+    "second_workgroup_4097_masked": (last_digit_keys(4097, at_zero=127), np.arange(4097) % 3 != 2, 0x3F80007F),
+}
+
+
+@pytest.mark.parametrize("name", list(SELECT_DIGIT_CASES))
+def test_median_depth_every_digit(name):
+    """Depths built from bit patterns (opacity 1) so that the select's later passes decide: test_median_depth's depths are
+    small integers over 64, whose low 16 key bits are zero.  Keys that differ in the last digit only, a repeated value, equal
+    keys, a rank on either side of a 255 -> 0 carry into the next digit (low digits and the top one), +inf as the median, and
+    two histogram workgroups whose second holds one element that the median depends on — with and without elements that
+    take no part lying between those that do."""
+    bits, mask, stated = SELECT_DIGIT_CASES[name]
+    d, o = bits.view(np.float32), np.ones(bits.size, np.float32)
+    want, n = R.median_depth(d, o, mask)
+    assert n == (bits.size if mask is None else int(mask.sum()))
+    if stated is not None:
+        assert int(np.float32(want).view(np.uint32)) == stated, hex(int(np.float32(want).view(np.uint32)))
+    if bits.size == 4097:   # without element 4096 the model selects the other middle candidate
+        other, _ = R.median_depth(d[:4096], o[:4096], None if mask is None else mask[:4096])
+        assert {int(np.float32(v).view(np.uint32)) for v in (want, other)} == {0x3F80007F, 0x3F800080}
+        assert mask is None or (bool(mask[4096]) and not mask[2::3].any() and int(mask.sum()) == 4097 - 1365)
+    got, gn = gpu_median(d, o, mask)
+    print(name, "median bits", hex(int(np.float32(got).view(np.uint32))), "count", gn)
+    assert gn == n and same(np.float32(got), np.float32(want)), (name, got, want, gn, n)
+
+
 def gpu_decide(params, n_touched, vis, median, cur_pose, kf_poses):
     """olsr_covisibility + olsr_keyframe_decide through the C ABI -> (cur uint8 [P], counts int64 [33], record int32[8], float32[40])"""
     from online_lang_splatting_amd import _abi

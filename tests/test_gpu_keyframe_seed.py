@@ -219,6 +219,38 @@ def test_count_edges(hip, n_valid, factor, n_keep):
         check_scales(out, ref)
 
 
+@pytest.mark.parametrize("seed,key5,downsample,n_keep,kept", [(1015369654, 0xFFFFFFFF, 1, 64, True), (1015369654, 0xFFFFFFFF, 2, 32, False),
+                                                             (1702866605, 0, 64, 1, True), (1702866605, 0, 16, 4, True)])
+def test_extreme_sampling_keys(hip, seed, key5, downsample, n_keep, kept):
+    """The sampling key is fmix32(i ^ seed * 0x9E3779B9), a bijection of the 32-bit words, so 0xFFFFFFFF and 0 are the keys of
+    one pixel index each per seed, and both are keys like any other: the all-ones word must be counted by the select.  The
+    seeds come from inverting the function for pixel 5: seed = (fmix32^-1(key) ^ 5) * 0x9E3779B9^-1 mod 2^32 (fmix32's steps
+    are xor-shifts and odd multipliers, each invertible).  With 1015369654 pixel 5 has the largest key of the frame, 0xFFFFFFFF:
+    kept when every valid pixel is, dropped at half; with 1702866605 it has the smallest, 0: the one pixel kept of 64, and
+    one of four.  As in test_count_edges nothing is appended when n_keep < 4; pix_index is read from the staging buffer."""
+    W, H = 8, 8
+    image, depth = make_frame(W, H, 41)
+    keys = R.sample_keys(W * H, seed)
+    assert int(keys[5]) == key5 and int(keys.argmax() if key5 else keys.argmin()) == 5
+    kw = dict(downsample=downsample, seed=seed)
+    ref = R.seed_rows_ref(image, depth, W2C, _intrinsics(W, H), **kw)
+    assert ref["n_valid"] == W * H and ref["n_keep"] == n_keep and (5 in ref["pix_index"]) == kept
+    if n_keep == 1:
+        assert ref["pix_index"].tolist() == [5]
+    cap = W * H // downsample + 3
+    runs = []
+    for _ in range(2):
+        st = _sentinel_staging(cap)
+        out = run(image, depth, W2C, _intrinsics(W, H), staging=st, **kw)
+        check_plan(out, ref, 1)
+        same_bits(st["pix_index"][:n_keep], ref["pix_index"], "pix_index of the plan")
+        assert bool((st["pix_index"][n_keep:] == -7).all())
+        assert out["means3D"].shape[0] == (n_keep if n_keep >= 4 else 0)
+        runs.append({k: bits(v).copy() for k, v in list(st.items()) + [(k, out[k]) for k in ("n_valid", "median_depth", "point_size")]})
+    for k in runs[0]:
+        assert np.array_equal(runs[0][k], runs[1][k]), ("two runs differ", k)
+
+
 def test_point_size(hip):
     W, H = 40, 24
     intr = _intrinsics(W, H)
