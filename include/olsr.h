@@ -745,7 +745,10 @@ typedef struct olsr_loss_params {
   float alpha;                     /* config["Training"]["alpha"], default 0.95 */
   float rgb_boundary_threshold;    /* config["Training"]["rgb_boundary_threshold"] */
   float lamda_lang;                /* BackEnd.lamda_lang (1.0), utils/slam_backend.py:80 */
-  int32_t _pad0;
+  float one_minus_alpha;           /* the depth term's weight, (float)(1.0 - alpha) formed from the caller's DOUBLE alpha as the
+                                      reference forms it (a Python double meeting a float32 tensor); 0: the library uses
+                                      1.f - alpha, which carries the float alpha's own rounding alpha / (1 - alpha) times
+                                      enlarged (3 ulp of the weight at 0.95) */
 } olsr_loss_params;
 size_t olsr_mapping_loss_scratch_bytes(int32_t width, int32_t height);
 int olsr_mapping_loss(const olsr_loss_params *params, const float *image, const float *depth,

@@ -324,7 +324,7 @@ class OlsrLossParams(C.Structure):
 
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("F", C.c_int32), ("lang_width", C.c_int32),
                 ("lang_height", C.c_int32), ("initialization", C.c_int32), ("alpha", C.c_float),
-                ("rgb_boundary_threshold", C.c_float), ("lamda_lang", C.c_float), ("_pad0", C.c_int32)]
+                ("rgb_boundary_threshold", C.c_float), ("lamda_lang", C.c_float), ("one_minus_alpha", C.c_float)]
 
 
 class OlsrLossFusion(C.Structure):

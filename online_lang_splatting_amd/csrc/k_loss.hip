@@ -47,7 +47,7 @@ __device__ __forceinline__ void store_px(float* __restrict__ plane, size_t p, co
 // function ignores the cotangent of its opacity output, DGR/diff_gaussian_rasterization/__init__.py:333-343.)
 template <int F, int VEC, bool TRACK>
 __global__ __launch_bounds__(LOSS_THREADS) void mapping_loss_kernel(
-    int W, int H, int lw, int lh, int use_exposure, float alpha, float thr, float lamda,
+    int W, int H, int lw, int lh, int use_exposure, float alpha, float one_minus_alpha, float thr, float lamda,
     const float* __restrict__ image, const float* __restrict__ depth, const float* __restrict__ lang,
     const float* __restrict__ gt_image, const float* __restrict__ gt_depth, const float* __restrict__ gt_lang,
     const float* __restrict__ exposure, const float* __restrict__ opacity, const float* __restrict__ grad_mask,
@@ -90,7 +90,7 @@ __global__ __launch_bounds__(LOSS_THREADS) void mapping_loss_kernel(
     {
       const PixVec<VEC> gd = load_px<VEC>(gt_depth, p), x = load_px<VEC>(depth, p);
       PixVec<VEC> d;
-      const float wd = (1.f - alpha) / (float)HW;
+      const float wd = one_minus_alpha / (float)HW;
 #pragma unroll
       for (int i = 0; i < VEC; ++i) d.v[i] = loss_depth_term<TRACK>(x.v[i], gd.v[i], op.v[i], wd, s);
       store_px<VEC>(d_depth, p, d);
@@ -158,6 +158,7 @@ LossFinalArgs loss_final_args(const float* partials, int nb, const olsr_loss_par
   a.F = tracking ? 0 : p.F;
   a.has_lang = (!tracking && has_lang) ? 1 : 0;
   a.alpha = p.alpha;
+  a.one_minus_alpha = loss_depth_weight(p);
   a.lamda = p.lamda_lang;
   a.loss = loss;
   a.d_exposure = dL_dexposure;
@@ -183,9 +184,9 @@ void launch_mapping_loss(const olsr_loss_params& p, const float* image, const fl
   const int nb = (int)((threads + LOSS_THREADS - 1) / LOSS_THREADS);  // <= loss_blocks(): the scratch is sized for VEC = 1
   const int use_exposure = (exposure != nullptr && !p.initialization) ? 1 : 0;
 #define OLSR_LOSS_ARGS                                                                                           \
-  p.width, p.height, p.lang_width, p.lang_height, use_exposure, p.alpha, p.rgb_boundary_threshold, p.lamda_lang, \
-      image, depth, language, gt_image, gt_depth, gt_language, exposure, opacity, grad_mask, dL_dimage, dL_ddepth, \
-      dL_dlanguage, partials
+  p.width, p.height, p.lang_width, p.lang_height, use_exposure, p.alpha, loss_depth_weight(p),                   \
+      p.rgb_boundary_threshold, p.lamda_lang, image, depth, language, gt_image, gt_depth, gt_language, exposure,   \
+      opacity, grad_mask, dL_dimage, dL_ddepth, dL_dlanguage, partials
 #define OLSR_LOSS(FV)                                                                       \
   case FV:                                                                                  \
     if (vec4)                                                                               \

@@ -442,7 +442,7 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
       fl.d_image[p] = loss_rgb_term<TRACK>(acc[0] + T * bg[0], g0, m, op, fl.use_exposure, ea, eb, wrgb, sums);
       fl.d_image[HW + p] = loss_rgb_term<TRACK>(acc[1] + T * bg[1], g1, m, op, fl.use_exposure, ea, eb, wrgb, sums);
       fl.d_image[2 * HW + p] = loss_rgb_term<TRACK>(acc[2] + T * bg[2], g2, m, op, fl.use_exposure, ea, eb, wrgb, sums);
-      fl.d_depth[p] = loss_depth_term<TRACK>(acc[3], fl.gt_depth[p], op, (1.f - fl.alpha) / (float)HW, sums);
+      fl.d_depth[p] = loss_depth_term<TRACK>(acc[3], fl.gt_depth[p], op, fl.one_minus_alpha / (float)HW, sums);
     }
     if constexpr (F > 0 && !TRACK) {
       if (fl.gt_lang != nullptr) {  // (uniform)
@@ -564,6 +564,7 @@ static void launch_fwd_t(const olsr_scene& s, const FrameDims& d, const Geometry
   fl.use_exposure = (lf.exposure != nullptr && !lf.params.initialization) ? 1 : 0;
   fl.write_images = lf.skip_images ? 0 : 1;
   fl.alpha = lf.params.alpha;
+  fl.one_minus_alpha = loss_depth_weight(lf.params);
   fl.thr = lf.params.rgb_boundary_threshold;
   fl.lamda = lf.params.lamda_lang;
   // (depth cut-offs are an option of the tracking loop: olsr_api.hip refuses them with the mapping loss)

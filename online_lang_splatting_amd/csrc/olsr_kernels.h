@@ -56,10 +56,13 @@ void launch_row_compaction(const uint8_t* flags, int64_t n_host, const int32_t* 
 // tile_work[0], sum of tile_work[1], rows_seq, 0} (the drop-in path sizes its backward scratch from them without a
 // synchronisation); live_rows: ImageState::live_rows, zero on entry, the staging of those sums
 // (reduced by one block of the tile-order kernel when a forward carries the fused loss epilogue; see k_loss.hip below)
+// the depth term's weight 1 - alpha: the caller's (float)(1.0 - alpha), or 1.f - alpha where the field was left 0 (include/olsr.h)
+inline float loss_depth_weight(const olsr_loss_params& p) { return p.one_minus_alpha != 0.f ? p.one_minus_alpha : 1.f - p.alpha; }
 struct LossFinalArgs {
   const float* partials;  // [nb][LOSS_SUMS], or null: nothing to do
   int nb, W, H, F, has_lang;
   float alpha, lamda;
+  float one_minus_alpha;   // loss_depth_weight(params)
   float* loss;
   float* d_exposure;       // written if use_exposure, zeroed if zero_exposure, may be null
   int use_exposure, zero_exposure;

@@ -66,6 +66,7 @@ struct FusedLossArgs {
   float* partials;  // [tiles][LOSS_SUMS]
   int lw, lh, use_exposure, write_images;
   float alpha, thr, lamda;
+  float one_minus_alpha;  // loss_depth_weight(params)
 };
 
 // The final reduction of a loss's partial sums (per block of the stand-alone loss kernel, per tile of the forward composite's
@@ -89,7 +90,7 @@ __device__ __forceinline__ void loss_final_block(const LossFinalArgs& a, double 
     for (int k = 0; k < LOSS_SUMS; ++k) t[k] = (red[0][k] + red[1][k]) + (red[2][k] + red[3][k]);
     const double HW = (double)a.H * (double)a.W;
     const double l_rgb = (double)a.alpha * t[0] / (3.0 * HW);
-    const double l_depth = (1.0 - (double)a.alpha) * t[1] / HW;
+    const double l_depth = (double)a.one_minus_alpha * t[1] / HW;
     const double l_lang = (a.has_lang && a.F > 0) ? (double)a.lamda * t[2] / ((double)a.F * HW) : 0.0;
     a.loss[0] = (float)(l_rgb + l_depth + l_lang);
     a.loss[1] = (float)l_rgb;

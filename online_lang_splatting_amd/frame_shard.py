@@ -773,7 +773,7 @@ class RasterWorkspace:
                                 lang_width=gt_language.shape[2] if lang else 0,
                                 lang_height=gt_language.shape[1] if lang else 0, initialization=int(bool(initialization)),
                                 alpha=float(alpha), rgb_boundary_threshold=float(rgb_boundary_threshold),
-                                lamda_lang=float(lamda_lang))
+                                lamda_lang=float(lamda_lang), one_minus_alpha=1.0 - float(alpha))
         ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
         if dL_dexposure_out is not None and dL_dexposure_out.numel() != 2:
             raise RuntimeError("forward_loss: dL_dexposure_out must hold two floats")

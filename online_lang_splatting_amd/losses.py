@@ -90,7 +90,8 @@ def mapping_loss(image, depth, language, gt_image, gt_depth, gt_language=None, e
     p = _abi.OlsrLossParams(width=W, height=H, F=F, lang_width=0 if gt_language is None else gt_language.shape[2],
                             lang_height=0 if gt_language is None else gt_language.shape[1],
                             initialization=int(bool(initialization)), alpha=float(alpha),
-                            rgb_boundary_threshold=float(rgb_boundary_threshold), lamda_lang=float(lamda_lang))
+                            rgb_boundary_threshold=float(rgb_boundary_threshold), lamda_lang=float(lamda_lang),
+                            one_minus_alpha=1.0 - float(alpha))   # in double, as the reference forms it
     out = dict(loss=torch.empty(4, **f32), dL_dimage=torch.empty(3, H, W, **f32), dL_ddepth=torch.empty(1, H, W, **f32),
                dL_dlanguage=torch.empty(F, H, W, **f32),
                dL_dexposure=(torch.empty(2, **f32) if dL_dexposure_out is None
@@ -129,7 +130,8 @@ def tracking_loss(image, depth, opacity, gt_image, gt_depth, grad_mask=None, exp
     exposure = _exposure(exposure, dev)
     f32 = dict(dtype=torch.float32, device=dev)
     p = _abi.OlsrLossParams(width=W, height=H, F=0, lang_width=0, lang_height=0, initialization=0, alpha=float(alpha),
-                            rgb_boundary_threshold=float(rgb_boundary_threshold), lamda_lang=0.0)
+                            rgb_boundary_threshold=float(rgb_boundary_threshold), lamda_lang=0.0,
+                            one_minus_alpha=1.0 - float(alpha))
     out = dict(loss=torch.empty(4, **f32), dL_dimage=torch.empty(3, H, W, **f32), dL_ddepth=torch.empty(1, H, W, **f32),
                dL_dexposure=torch.empty(2, **f32))
     L = lib()

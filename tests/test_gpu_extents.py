@@ -1192,7 +1192,8 @@ def test_forward_async_loss(hip, W, Hh, tile, tracking):
         two = losses.mapping_loss(first.out["color"], first.out["depth"], first.out["language"], c["gt_image"], c["gt_depth"],
                                   c["gt_lang"], expo)
     p = _abi.OlsrLossParams(width=W, height=Hh, F=F if lang else 0, lang_width=lw if lang else 0, lang_height=lh if lang else 0,
-                            initialization=0, alpha=0.95, rgb_boundary_threshold=0.01, lamda_lang=1.0)
+                            initialization=0, alpha=0.95, rgb_boundary_threshold=0.01, lamda_lang=1.0,
+                            one_minus_alpha=1.0 - 0.95)   # as losses.py fills it: the yardstick below goes through losses.py
 
     def entry(case):
         geom, img = case.scratch(L.olsr_geometry_bytes(P, F)), case.scratch(L.olsr_image_bytes(W, Hh, tile))
