@@ -184,6 +184,37 @@ def same_bits(a, b):
     return bool(((a == b) | (a.isnan() & b.isnan())).all())
 
 
+def first_difference(a, b):
+    """None when a and b hold the same bits (same_bits), else (flat index, a there, b there, how many differ)."""
+    a, b = a.detach().cpu().float().reshape(-1), b.detach().cpu().float().reshape(-1)
+    bad = ~((a == b) | (a.isnan() & b.isnan()))
+    if not bool(bad.any()):
+        return None
+    i = int(bad.nonzero()[0])
+    return i, float(a[i]), float(b[i]), int(bad.sum())
+
+
+def assert_tau_sum_fixed_order(g, where=""):
+    """dL_dtau_sum is a deterministic function of the dL_dtau the same backward wrote: 128-Gaussian block partials
+    (wave butterfly, then the two waves in order), then tau_final_kernel's strided pass over them (tests/bwd_sums_ref.py:
+    tau_sum restates both, addition by addition).  `g`: the backward's dict with dL_dtau [P, 6] and dL_dtau_sum [6].
+    Asserts the EQUALITY, and that the sum lies within tau_sum_bound (derived from the depth of that order) of the exact
+    sum - the latter where dL_dtau is finite."""
+    import numpy as np
+    import bwd_sums_ref as ref
+    x = g["dL_dtau"].detach().cpu().float().reshape(-1, 6).numpy()
+    got = g["dL_dtau_sum"].detach().cpu().float().reshape(6)
+    with np.errstate(invalid="ignore", over="ignore"):
+        want = torch.from_numpy(ref.tau_sum(x))
+    d = first_difference(got, want)
+    assert d is None, (f"{where}dL_dtau_sum is not the fixed-order sum of dL_dtau (P = {x.shape[0]}): component {d[0]} is "
+                       f"{d[1]!r}, the model gives {d[2]!r}; {d[3]} of 6 differ")
+    if bool(np.isfinite(x).all()):
+        exact, bound = ref.tau_sum_bound(x)
+        err = np.abs(got.double().numpy() - exact)
+        assert bool((err <= bound).all()), f"{where}dL_dtau_sum: |sum - exact| = {err} above the derived bound {bound}"
+
+
 def tile_pairs(hip, f, sc, tile):
     """(tile * P + Gaussian) per sorted list position, the per-position blend flags, and the positions."""
     W, H, F, R = sc.camera.width, sc.camera.height, sc.F, f["R"]

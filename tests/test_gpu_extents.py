@@ -58,7 +58,7 @@ import torch
 import extent_harness as H
 from online_lang_splatting_amd import _abi
 from online_lang_splatting_amd.scene import make_scene
-from parity_common import assert_elementwise, fwd_args, rel_err, run_backend
+from parity_common import assert_elementwise, assert_tau_sum_fixed_order, fwd_args, rel_err, run_backend
 
 pytestmark = pytest.mark.gpu
 DEV = H.DEV
@@ -253,6 +253,7 @@ def _against_oracle(out, fo, go, binning, name):
     tau_sum = go["dL_dtau"].double().sum(0).float()
     r, _ = rel_err(out["dL_dtau_sum"], tau_sum)
     assert r <= TP.RTOL, f"{name}: dL_dtau_sum: rel {r:.2e}"
+    assert_tau_sum_fixed_order(out, where=f"{name}: ")
     assert int(out["status"][1]) == 0, name
 
 

@@ -16,7 +16,7 @@ import fwd_batch_scenes as fs
 from online_lang_splatting_amd import _abi
 from online_lang_splatting_amd.scene import default_camera, make_scene
 from parity_common import (ELEM_MIN_FRACTION, assert_elementwise, assert_ordered_equals_oracle, assert_rounding_only,
-                           fwd_args, ordered_backward, rel_err, run_backend, tile_pairs)
+                           assert_tau_sum_fixed_order, fwd_args, ordered_backward, rel_err, run_backend, tile_pairs)
 
 pytestmark = pytest.mark.gpu
 RTOL = 1e-4
@@ -129,6 +129,8 @@ def _check(hip, oracle, sc, seed=0, tile=15, mode=0, grad_keys=None, elementwise
             # largest of the six — a per-element statement about six numbers would be a statement about summation noise
             r, _ = rel_err(g_["dL_dtau_sum"], tau_sum)
             assert r <= RTOL, f"{name}: dL_dtau_sum: rel {r:.2e}"
+            # ... and, the summation order being fixed, to EQUALITY with that order's sum of the product's own dL_dtau
+            assert_tau_sum_fixed_order(g_, where=f"{name}: ")
             if log is not None:
                 log.append(dict(name=f"{name}:dL_dtau_sum", max_norm_rel=r, n=6))
     if fo["R"] > 0:
