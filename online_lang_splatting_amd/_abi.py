@@ -236,6 +236,17 @@ SS_DECODER_STATE = tuple(e for k, (i, o) in enumerate(zip(SS_DECODER_WIDTHS, SS_
                          for e in ((f"decoder.{2 * k}.weight", (o, i)), (f"decoder.{2 * k}.bias", (o,))))
 
 
+# a frame's ingest (include/olsr_frame_ingest.h)
+INGEST_DEPTH_U16, INGEST_DEPTH_F32 = 0, 1
+
+
+class OlsrFrameIngestParams(C.Structure):
+    """struct olsr_frame_ingest_params, include/olsr_frame_ingest.h."""
+
+    _fields_ = [("W", C.c_int32), ("H", C.c_int32), ("depth_type", C.c_int32), ("_pad0", C.c_int32),
+                ("plane_stride", C.c_int64), ("depth_scale", C.c_double)]
+
+
 class OlsrSsEncoderParams(C.Structure):
     """struct olsr_ss_encoder_params, include/olsr_single_stage.h."""
 

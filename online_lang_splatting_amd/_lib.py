@@ -1,4 +1,5 @@
-"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h and include/olsr_single_stage.h) and declares its prototypes.
+"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h, include/olsr_single_stage.h and include/olsr_frame_ingest.h) and
+declares its prototypes.
 
 There is no fallback: if the library is missing or a symbol is absent this raises, loudly.
 """
@@ -21,6 +22,9 @@ EXPORTS = (
 # every symbol include/olsr_single_stage.h declares (the same library)
 EXPORTS_SINGLE_STAGE = ("olsr_ss_encoder_encode", "olsr_ss_query_sims")
 
+# every symbol include/olsr_frame_ingest.h declares (the same library)
+EXPORTS_FRAME_INGEST = ("olsr_frame_ingest",)
+
 _lib = None
 
 
@@ -39,7 +43,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m online_lang_splatting_amd.build` "
             "(hipcc, gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE if not hasattr(L, s)]
+    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE + EXPORTS_FRAME_INGEST if not hasattr(L, s)]
     if missing:
         raise ImportError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
@@ -146,6 +150,8 @@ def lib():
     L.olsr_covisibility.argtypes, L.olsr_covisibility.restype = [i64, vp, C.POINTER(_abi.OlsrCovisViews), vp, vp, vp], C.c_int
     L.olsr_keyframe_decide.argtypes = [C.POINTER(_abi.OlsrKeyframeDecideParams)] + [vp] * 6
     L.olsr_keyframe_decide.restype = C.c_int
+    L.olsr_frame_ingest.argtypes = [C.POINTER(_abi.OlsrFrameIngestParams)] + [vp] * 5
+    L.olsr_frame_ingest.restype = C.c_int
     L.olsr_bucket_add.argtypes, L.olsr_bucket_add.restype = [i32, i32] + [vp] * 9, C.c_int
     L.olsr_knn_scratch_bytes.argtypes, L.olsr_knn_scratch_bytes.restype = [i32], sz
     L.olsr_knn_mean_dist2.argtypes, L.olsr_knn_mean_dist2.restype = [i32, vp, vp, vp, vp], C.c_int

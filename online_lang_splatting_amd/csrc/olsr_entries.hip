@@ -683,6 +683,27 @@ int olsr_keyframe_decide(const olsr_keyframe_decide_params* p, const int64_t* co
   return launch_check("keyframe_decide");
 }
 
+// ---- a frame's ingest (include/olsr_frame_ingest.h)
+int olsr_frame_ingest(const olsr_frame_ingest_params* p, const uint8_t* rgb, const void* depth, float* image, float* depth_out,
+                      void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "frame_ingest: params are required");
+  if (p->W <= 0 || p->H <= 0) return fail(OLSR_ERR_ARG, "frame_ingest: W and H must be > 0");
+  const int64_t N = (int64_t)p->W * (int64_t)p->H;
+  if (N > (int64_t)0x7FFFFFFF) return fail(OLSR_ERR_ARG, "frame_ingest: W * H must fit an int32");
+  if (p->plane_stride < N) return fail(OLSR_ERR_ARG, "frame_ingest: plane_stride must be >= W * H");
+  if (p->depth_type != OLSR_INGEST_DEPTH_U16 && p->depth_type != OLSR_INGEST_DEPTH_F32)
+    return fail(OLSR_ERR_ARG, "frame_ingest: depth_type must be OLSR_INGEST_DEPTH_U16 or OLSR_INGEST_DEPTH_F32");
+  if (!(p->depth_scale > 0.0) || !std::isfinite(p->depth_scale))
+    return fail(OLSR_ERR_ARG, "frame_ingest: depth_scale must be finite and > 0");
+  if (!rgb || !depth || !image || !depth_out)
+    return fail(OLSR_ERR_ARG, "frame_ingest: rgb, depth, image and depth_out are required");
+  const uintptr_t depth_align = p->depth_type == OLSR_INGEST_DEPTH_U16 ? 2 : 4;
+  if ((uintptr_t)depth % depth_align || (uintptr_t)image % 4 || (uintptr_t)depth_out % 4)
+    return fail(OLSR_ERR_ARG, "frame_ingest: depth must be aligned to its element size, image and depth_out to 4 bytes");
+  launch_frame_ingest(*p, rgb, depth, image, depth_out, (hipStream_t)hip_stream);
+  return launch_check("frame_ingest");
+}
+
 // what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)
 static const char* tsdf_volume_error(const olsr_tsdf_volume* v, bool surface) {
   if (!v) return "volume is required";

@@ -5,6 +5,7 @@
 
 #include "../../include/olsr.h"
 #include "../../include/olsr_single_stage.h"
+#include "../../include/olsr_frame_ingest.h"
 #include "olsr_state.h"
 
 namespace olsr {
@@ -259,6 +260,10 @@ hipError_t launch_covisibility(int64_t P, const int32_t* n_touched, const olsr_c
                                int64_t* counts, hipStream_t st);
 void launch_keyframe_decide(const olsr_keyframe_decide_params& p, const int64_t* counts, const float* median,
                             const float* cur_pose, const float* kf_poses, void* record, hipStream_t st);
+
+// k_frame_ingest.hip: a frame's ingest (include/olsr_frame_ingest.h)
+void launch_frame_ingest(const olsr_frame_ingest_params& p, const uint8_t* rgb, const void* depth, float* image,
+                         float* depth_out, hipStream_t st);
 
 // k_pose.hip
 void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,

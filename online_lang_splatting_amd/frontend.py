@@ -1,5 +1,6 @@
 """Host side of the front end's frame step (include/olsr.h, "front end: the frame step"; csrc/k_frontend.hip): the tracking
-mask, the median depth after tracking, and the keyframe test with the window policy.
+mask, the median depth after tracking, and the keyframe test with the window policy — and of the frame's ingest ahead of
+them (include/olsr_frame_ingest.h; csrc/k_frame_ingest.hip).
 
 Replaces what the reference's front end does once per frame in PyTorch ops with host reads (utils/slam_frontend.py:577-676):
 Camera.compute_grad_mask (utils/camera_utils.py:123-152), get_median_depth (utils/slam_utils.py:168-179), is_keyframe /
@@ -59,6 +60,46 @@ def tracking_mask(image: torch.Tensor, edge_threshold: float, mode: str = "block
         check(L.olsr_grad_mask(W, H, int(image.stride(0)), MODES[mode], float(edge_threshold), image.data_ptr(), out.data_ptr(),
                                scratch.data_ptr() if scratch is not None else None, _stream(dev)))
     return out
+
+
+def ingest_frame(rgb_u8: torch.Tensor, depth: torch.Tensor, depth_scale: float, out_image: Optional[torch.Tensor] = None,
+                 out_depth: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """A frame as the dataset decodes it -> what every other entry consumes, in one launch (include/olsr_frame_ingest.h):
+    rgb_u8 uint8 [H,W,3] (interleaved, contiguous, any byte address), depth [H,W] uint16 or float32 (contiguous) ->
+    (image float32 [3,H,W] = float32(clamp(float64(byte) / 255, 0, 1)), depth float32 [H,W] = float32(float64(d) / depth_scale)),
+    the statements of ReplicaDataset / TUMDataset.__getitem__ and of the depth conversion in get_loss_tracking /
+    add_new_keyframe.  out_image: float32 [3,H,W] with contiguous rows and any plane stride; out_depth: contiguous float32 of
+    H W elements.  The datasets' undistortion (cv2.remap) is not part of it."""
+    _gpu("ingest_frame", rgb_u8, depth)
+    _need("ingest_frame", rgb_u8.dim() == 3 and rgb_u8.shape[2] == 3 and rgb_u8.dtype == torch.uint8, "rgb_u8 must be uint8 [H,W,3]")
+    H, W = int(rgb_u8.shape[0]), int(rgb_u8.shape[1])
+    _need("ingest_frame", H > 0 and W > 0, "the frame must not be empty")
+    _need("ingest_frame", rgb_u8.is_contiguous(), "rgb_u8 must be contiguous")
+    dev = rgb_u8.device
+    _need("ingest_frame", depth.dtype in (torch.uint16, torch.float32), "depth must be uint16 or float32")
+    _need("ingest_frame", depth.device == dev and tuple(depth.shape) == (H, W) and depth.is_contiguous(),
+          "depth must be a contiguous [H,W] tensor on the image's device")
+    depth_scale = float(depth_scale)
+    _need("ingest_frame", depth_scale > 0.0 and depth_scale != float("inf"), "depth_scale must be finite and > 0")
+    if out_image is None:
+        out_image = torch.empty(3, H, W, dtype=torch.float32, device=dev)
+    else:
+        _gpu("ingest_frame", out_image)
+        _need("ingest_frame", out_image.device == dev and out_image.dtype == torch.float32 and tuple(out_image.shape) == (3, H, W)
+              and out_image.stride(2) == 1 and out_image.stride(1) == W and out_image.stride(0) >= W * H,
+              "out_image must be float32 [3,H,W] with contiguous rows on the image's device")
+    if out_depth is None:
+        out_depth = torch.empty(H, W, dtype=torch.float32, device=dev)
+    else:
+        _gpu("ingest_frame", out_depth)
+        _need("ingest_frame", out_depth.device == dev and out_depth.dtype == torch.float32 and out_depth.numel() == W * H and
+              out_depth.is_contiguous(), "out_depth must be a contiguous float32 tensor of H W elements on the image's device")
+    p = _abi.OlsrFrameIngestParams(W=W, H=H, depth_type=_abi.INGEST_DEPTH_U16 if depth.dtype == torch.uint16 else _abi.INGEST_DEPTH_F32,
+                                   plane_stride=int(out_image.stride(0)), depth_scale=depth_scale)
+    with torch.cuda.device(dev):
+        check(lib().olsr_frame_ingest(C.byref(p), rgb_u8.data_ptr(), depth.data_ptr(), out_image.data_ptr(), out_depth.data_ptr(),
+                                      _stream(dev)))
+    return out_image, out_depth
 
 
 def median_depth(depth: torch.Tensor, opacity: torch.Tensor, mask: Optional[torch.Tensor] = None,
