@@ -27,8 +27,9 @@
  * olsr_adam_step_groups, olsr_adam_step_groups_reg with olsr_isotropic_reg), olsr_map_edit_plan / _apply (densify, prune, extend on the device), olsr_knn_mean_dist2,
  * olsr_keyframe_seed_plan / _finish (a keyframe's new Gaussians from its RGB-D image), olsr_grad_mask, olsr_median_depth,
  * olsr_covisibility and olsr_keyframe_decide (the front end's frame step around the tracking loop).
- * Two groups of entries of the same library are declared in headers of their own, which include this one:
- * olsr_single_stage.h (the single-stage language chain) and olsr_frame_ingest.h (a frame's ingest ahead of the frame step).
+ * Three groups of entries of the same library are declared in headers of their own, which include this one:
+ * olsr_single_stage.h (the single-stage language chain), olsr_frame_ingest.h (a frame's ingest ahead of the frame step) and
+ * olsr_map_io.h (the map as the reference's PLY record, packed and unpacked on the device).
  */
 #ifndef OLSR_H_INCLUDED
 #define OLSR_H_INCLUDED

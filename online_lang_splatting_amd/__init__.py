@@ -25,10 +25,11 @@ from .query_eval import QueryEvaluator, frame_metrics, smooth_masks  # noqa: F40
 from .keyframe_seed import seed_rows  # noqa: F401,E402  (a keyframe's new Gaussians from its RGB-D image, on the device)
 from .frontend import KeyframeSelector, ingest_frame, median_depth, tracking_mask  # noqa: F401,E402  (the front end's frame step)
 from .slam_iterations import KeyframeWindow  # noqa: F401,E402  (mapping's bundle adjustment: window poses and exposures)
-from .slam import OnlineSlam, ate_rmse  # noqa: F401,E402  (the online session: RGB-D frames in, poses and a map out)
+from .slam import OnlineSlam, ate_rmse, ate_statistics  # noqa: F401,E402  (the online session: RGB-D frames in, poses and a map out)
+from . import map_io  # noqa: F401,E402  (the map on disk: point_cloud.ply packed on the device, the resumable .npz)
 from .losses import isotropic_loss  # noqa: F401,E402  (the mapping loss's isotropic regulariser)
 
-__all__ = ["render", "OnlineSlam", "ate_rmse", "ingest_frame", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "SingleStageEncoder", "SingleStageDecoder", "SingleStageQuery", "SingleStageTargets", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "OnlineSlam", "ate_rmse", "ate_statistics", "map_io", "ingest_frame", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "SingleStageEncoder", "SingleStageDecoder", "SingleStageQuery", "SingleStageTargets", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "query_eval", "QueryEvaluator", "smooth_masks", "frame_metrics", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

@@ -247,6 +247,10 @@ class OlsrFrameIngestParams(C.Structure):
                 ("plane_stride", C.c_int64), ("depth_scale", C.c_double)]
 
 
+# the map's point_cloud.ply record (include/olsr_map_io.h, OLSR_MAP_PLY_*)
+MAP_PLY_MAX_M, MAP_PLY_MAX_F, MAP_PLY_MAX_WIDTH, MAP_PLY_BLOCK_ROWS, MAP_PLY_MAX_COLS = 16, 32, 94, 64, 6016
+
+
 class OlsrSsEncoderParams(C.Structure):
     """struct olsr_ss_encoder_params, include/olsr_single_stage.h."""
 

@@ -1,5 +1,5 @@
-"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h, include/olsr_single_stage.h and include/olsr_frame_ingest.h) and
-declares its prototypes.
+"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h, include/olsr_single_stage.h, include/olsr_frame_ingest.h and
+include/olsr_map_io.h) and declares its prototypes.
 
 There is no fallback: if the library is missing or a symbol is absent this raises, loudly.
 """
@@ -25,6 +25,9 @@ EXPORTS_SINGLE_STAGE = ("olsr_ss_encoder_encode", "olsr_ss_query_sims")
 # every symbol include/olsr_frame_ingest.h declares (the same library)
 EXPORTS_FRAME_INGEST = ("olsr_frame_ingest",)
 
+# every symbol include/olsr_map_io.h declares (the same library)
+EXPORTS_MAP_IO = ("olsr_map_ply_width", "olsr_map_ply_pack", "olsr_map_ply_unpack")
+
 _lib = None
 
 
@@ -43,7 +46,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m online_lang_splatting_amd.build` "
             "(hipcc, gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE + EXPORTS_FRAME_INGEST if not hasattr(L, s)]
+    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE + EXPORTS_FRAME_INGEST + EXPORTS_MAP_IO if not hasattr(L, s)]
     if missing:
         raise ImportError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
@@ -152,6 +155,9 @@ def lib():
     L.olsr_keyframe_decide.restype = C.c_int
     L.olsr_frame_ingest.argtypes = [C.POINTER(_abi.OlsrFrameIngestParams)] + [vp] * 5
     L.olsr_frame_ingest.restype = C.c_int
+    L.olsr_map_ply_width.argtypes, L.olsr_map_ply_width.restype = [i32, i32], C.c_int
+    L.olsr_map_ply_pack.argtypes, L.olsr_map_ply_pack.restype = [i32, i32, i32, mb, vp, vp], C.c_int
+    L.olsr_map_ply_unpack.argtypes, L.olsr_map_ply_unpack.restype = [i32, i32, i32, i32, C.POINTER(i32), vp, mb, vp], C.c_int
     L.olsr_bucket_add.argtypes, L.olsr_bucket_add.restype = [i32, i32] + [vp] * 9, C.c_int
     L.olsr_knn_scratch_bytes.argtypes, L.olsr_knn_scratch_bytes.restype = [i32], sz
     L.olsr_knn_mean_dist2.argtypes, L.olsr_knn_mean_dist2.restype = [i32, vp, vp, vp, vp], C.c_int

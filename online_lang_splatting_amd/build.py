@@ -48,13 +48,15 @@ UNITS = [
     ("k_keyframe_seed.hip", "k_keyframe_seed.o", []),
     ("k_frontend.hip", "k_frontend.o", []),
     ("k_frame_ingest.hip", "k_frame_ingest.o", []),
+    ("k_map_io.hip", "k_map_io.o", []),
     ("k_pose.hip", "k_pose.o", []),
     ("k_tsdf.hip", "k_tsdf.o", []),
     ("k_cloud_metrics.hip", "k_cloud_metrics.o", []),
     ("k_query_eval.hip", "k_query_eval.o", []),
 ]
 HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_select.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h"),
-           os.path.join("..", "..", "include", "olsr_single_stage.h"), os.path.join("..", "..", "include", "olsr_frame_ingest.h")]
+           os.path.join("..", "..", "include", "olsr_single_stage.h"), os.path.join("..", "..", "include", "olsr_frame_ingest.h"),
+           os.path.join("..", "..", "include", "olsr_map_io.h")]
 
 
 def hipcc():

@@ -1,5 +1,5 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, TSDF fusion, point-cloud metrics, the 2-D evaluation's query scoring.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, the map's PLY record, TSDF fusion, point-cloud metrics, the 2-D evaluation's query scoring.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -702,6 +702,61 @@ int olsr_frame_ingest(const olsr_frame_ingest_params* p, const uint8_t* rgb, con
     return fail(OLSR_ERR_ARG, "frame_ingest: depth must be aligned to its element size, image and depth_out to 4 bytes");
   launch_frame_ingest(*p, rgb, depth, image, depth_out, (hipStream_t)hip_stream);
   return launch_check("frame_ingest");
+}
+
+// ---- the map <-> the point_cloud.ply record array (include/olsr_map_io.h)
+// what is wrong with the sizes of a record, if anything
+static const char* map_ply_sizes_error(int32_t M, int32_t F) {
+  if (M != 1 && M != 4 && M != 9 && M != 16) return "M must be a perfect square in 1 ... 16";
+  if (F < 0 || F > OLSR_MAP_PLY_MAX_F) return "F must lie in 0 ... 32";
+  return nullptr;
+}
+
+// what is wrong with the parameter arrays of a map that an entry reads or writes, if anything
+static const char* map_ply_buffers_error(const olsr_map_buffers* b, int32_t F) {
+  if (!b) return "the map's buffers are required";
+  if (!b->means3D || !b->shs || !b->opacities || !b->scales || !b->rotations || (F > 0 && !b->language))
+    return "means3D, shs, opacities, scales, rotations and (F > 0) language are required";
+  if (((uintptr_t)b->means3D | (uintptr_t)b->shs | (uintptr_t)b->opacities | (uintptr_t)b->scales | (uintptr_t)b->rotations |
+       (uintptr_t)b->language) % 4)
+    return "every array must be aligned to 4 bytes";
+  return nullptr;
+}
+
+int olsr_map_ply_width(int32_t M, int32_t F) {
+  if (const char* e = map_ply_sizes_error(M, F)) return fail(OLSR_ERR_ARG, std::string("map_ply_width: ") + e);
+  return 14 + 3 * M + F;
+}
+
+int olsr_map_ply_pack(int32_t P, int32_t M, int32_t F, const olsr_map_buffers* src, float* rows, void* hip_stream) {
+  if (const char* e = map_ply_sizes_error(M, F)) return fail(OLSR_ERR_ARG, std::string("map_ply_pack: ") + e);
+  if (P < 0) return fail(OLSR_ERR_ARG, "map_ply_pack: P must be >= 0");
+  if (P == 0) return OLSR_OK;
+  if (const char* e = map_ply_buffers_error(src, F)) return fail(OLSR_ERR_ARG, std::string("map_ply_pack: ") + e);
+  if (!rows || (uintptr_t)rows % 4) return fail(OLSR_ERR_ARG, "map_ply_pack: rows is required, aligned to 4 bytes");
+  launch_map_ply_pack(P, M, F, *src, rows, (hipStream_t)hip_stream);
+  return launch_check("map_ply_pack");
+}
+
+int olsr_map_ply_unpack(int32_t P, int32_t M, int32_t F, int32_t n_cols, const int32_t* col, const float* rows,
+                        const olsr_map_buffers* dst, void* hip_stream) {
+  if (const char* e = map_ply_sizes_error(M, F)) return fail(OLSR_ERR_ARG, std::string("map_ply_unpack: ") + e);
+  if (P < 0) return fail(OLSR_ERR_ARG, "map_ply_unpack: P must be >= 0");
+  if (n_cols < 1 || n_cols > OLSR_MAP_PLY_MAX_COLS)
+    return fail(OLSR_ERR_ARG, "map_ply_unpack: n_cols must lie in 1 ... OLSR_MAP_PLY_MAX_COLS");
+  if (!col) return fail(OLSR_ERR_ARG, "map_ply_unpack: col is required");
+  const int width = 14 + 3 * M + F, lang0 = 6 + 3 * M;
+  for (int j = 0; j < width; ++j) {
+    if (col[j] >= n_cols || col[j] < -1) return fail(OLSR_ERR_ARG, "map_ply_unpack: a col[j] lies outside -1 ... n_cols - 1");
+    // (a normal is never stored: its entry is not read)
+    if (col[j] == -1 && !(j >= 3 && j < 6) && !(j >= lang0 && j < lang0 + F))
+      return fail(OLSR_ERR_ARG, "map_ply_unpack: only a normal or a language channel may be absent (col[j] = -1)");
+  }
+  if (P == 0) return OLSR_OK;
+  if (const char* e = map_ply_buffers_error(dst, F)) return fail(OLSR_ERR_ARG, std::string("map_ply_unpack: ") + e);
+  if (!rows || (uintptr_t)rows % 4) return fail(OLSR_ERR_ARG, "map_ply_unpack: rows is required, aligned to 4 bytes");
+  launch_map_ply_unpack(P, M, F, n_cols, col, rows, *dst, (hipStream_t)hip_stream);
+  return launch_check("map_ply_unpack");
 }
 
 // what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)

@@ -6,6 +6,7 @@
 #include "../../include/olsr.h"
 #include "../../include/olsr_single_stage.h"
 #include "../../include/olsr_frame_ingest.h"
+#include "../../include/olsr_map_io.h"
 #include "olsr_state.h"
 
 namespace olsr {
@@ -264,6 +265,11 @@ void launch_keyframe_decide(const olsr_keyframe_decide_params& p, const int64_t*
 // k_frame_ingest.hip: a frame's ingest (include/olsr_frame_ingest.h)
 void launch_frame_ingest(const olsr_frame_ingest_params& p, const uint8_t* rgb, const void* depth, float* image,
                          float* depth_out, hipStream_t st);
+
+// k_map_io.hip: the map <-> the point_cloud.ply record array (include/olsr_map_io.h); col: host, [14 + 3 M + F]
+void launch_map_ply_pack(int P, int M, int F, const olsr_map_buffers& src, float* rows, hipStream_t st);
+void launch_map_ply_unpack(int P, int M, int F, int n_cols, const int32_t* col, const float* rows, const olsr_map_buffers& dst,
+                           hipStream_t st);
 
 // k_pose.hip
 void launch_pose_step(const olsr_pose_params& p, const float* dL_dtau_sum, const float* dL_dexposure, const float* proj,

@@ -343,6 +343,47 @@ class GaussianMap:
         m.adam.step_count = max(m.adam.group_steps)
         return m
 
+    @classmethod
+    def blank(cls, P, M, F, lrs: Dict[str, float], device, capacity=None, percent_dense=0.01):
+        """A map of P rows whose parameters are still to be written (load_ply fills them on the device); moments, statistics,
+        max_radii, kf_id and n_obs zero."""
+        dev = torch.device(device)
+        f32 = dict(dtype=torch.float32, device=dev)
+        cap = max(int(capacity) if capacity is not None else cls._grow(P), P)
+        m = cls(torch.empty(0, 3, **f32), torch.empty(0, M, 3, **f32) if M else None, torch.empty(0, 1, **f32),
+                torch.empty(0, 3, **f32), torch.empty(0, 4, **f32), torch.empty(0, F, **f32) if F else None, lrs, capacity=cap,
+                percent_dense=percent_dense, device=dev)
+        m.P = int(P)
+        b = m._bufs[m._front]
+        for k in ("exp_avg", "exp_avg_sq", "stats", "max_radii", "kf_id", "n_obs"):
+            b[k][:m.P].zero_()
+        m._views()
+        return m
+
+    # ---- the map on disk (map_io.py) ----
+    def save_ply(self, path):
+        """GaussianModel.save_ply: point_cloud.ply with the raw parameters, packed on the device (map_io.save_ply)."""
+        from . import map_io
+        map_io.save_ply(self, path)
+
+    @classmethod
+    def load_ply(cls, path, lrs: Dict[str, float], device, F=None, capacity=None, percent_dense=0.01):
+        """GaussianModel.load_ply: a map from a point_cloud.ply; optimiser state and accumulators zero (map_io.load_ply).
+        F=None keeps the language channels the file has, F=0 drops them as the reference does."""
+        from . import map_io
+        return map_io.load_ply(path, lrs, device, F=F, capacity=capacity, percent_dense=percent_dense)
+
+    def save_state(self, path):
+        """state() as one .npz: the resumable form (map_io.save_state)."""
+        from . import map_io
+        map_io.save_state(self, path)
+
+    @classmethod
+    def load_state(cls, path, lrs: Dict[str, float], device, capacity=None, percent_dense=0.01):
+        """The map save_state wrote, through from_state (map_io.load_state)."""
+        from . import map_io
+        return map_io.load_state(path, lrs, device, capacity=capacity, percent_dense=percent_dense)
+
     def new_gradients(self):
         """A backward since the last edit produced gradients for the current parameters: the next step updates every group
         again (MappingStep calls this at the start of each iteration)."""

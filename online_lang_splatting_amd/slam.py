@@ -29,8 +29,14 @@ iteration the kept images are those of the pose after the converging step (Track
 with `Training.seed` (default 0): two runs are bit-identical.
 
 OUT OF SCOPE: `single_thread: False` (tracking against a stale snapshot while the back end maps), the GUI packets,
-pause / unpause, save_gaussians / PLY output, datasets and image decoding, undistortion, and the language backbone (its
-features arrive through `feature_fn`)."""
+pause / unpause, resuming a whole session from disk (the map alone resumes: GaussianMap.save_state / load_state), the .npy
+language dumps and images of eval_rendering, LPIPS, datasets and image decoding, undistortion, and the language backbone
+(its features arrive through `feature_fn`).
+
+The end of the reference's run is here too: `save_gaussians` writes the map as the reference's point_cloud.ply
+(map_io.py), `save_trajectory` the two JSON files of eval_ate."""
+import json
+import os
 from typing import Callable, Dict, List, Optional, Sequence
 
 import numpy as np
@@ -84,6 +90,12 @@ def ate_rmse(est_w2c, gt_w2c) -> float:
     """eval_ate / evaluate_evo (utils/eval_utils.py:24-111) with correct_scale=False, on the host in float64: the camera
     centres of the inverted poses, a rigid Umeyama alignment (rotation and translation, no scale) of the estimate to the
     ground truth, the root mean square of the translation differences.  est_w2c, gt_w2c: [n,4,4] world-to-camera."""
+    return ate_statistics(est_w2c, gt_w2c)["rmse"]
+
+
+def ate_statistics(est_w2c, gt_w2c) -> Dict[str, float]:
+    """evo's APE.get_all_statistics() of the translation part after ate_rmse's alignment: rmse, mean, median, std, min, max
+    and sse of the per-pose distances (what evaluate_evo writes to stats_{label}.json)."""
     def centres(T):
         T = np.asarray(T.detach().cpu() if isinstance(T, torch.Tensor) else T, dtype=np.float64).reshape(-1, 4, 4)
         return np.stack([np.linalg.inv(t)[:3, 3] for t in T])
@@ -99,7 +111,10 @@ def ate_rmse(est_w2c, gt_w2c) -> float:
     R = U @ S @ Vt
     t = my - R @ mx
     err = (x @ R.T + t) - y
-    return float(np.sqrt(np.mean(np.sum(err * err, axis=1))))
+    sq = np.sum(err * err, axis=1)
+    e = np.sqrt(sq)
+    return dict(rmse=float(np.sqrt(np.mean(sq))), mean=float(np.mean(e)), median=float(np.median(e)), std=float(np.std(e)),
+                min=float(np.min(e)), max=float(np.max(e)), sse=float(np.sum(sq)))
 
 
 class OnlineSlam:
@@ -273,6 +288,48 @@ class OnlineSlam:
         """-> (frame ids, w2c [n,4,4] on the device): every frame's estimate; a keyframe's is the bundle adjustment's."""
         ids = sorted(self.poses)
         return ids, torch.stack([self.poses[i] for i in ids]) if ids else torch.zeros(0, 4, 4, device=self.device)
+
+    def save_gaussians(self, save_dir, iteration=None, final=False):
+        """save_gaussians (utils/eval_utils.py:202-211): the map as `point_cloud/final/point_cloud.ply` or
+        `point_cloud/iteration_{iteration}/point_cloud.ply` under save_dir (GaussianMap.save_ply: packed on the device,
+        written through a temporary file).  save_dir=None returns without writing.  -> the file's path or None."""
+        if save_dir is None:
+            return None
+        if self.map is None:
+            raise RuntimeError("save_gaussians: no frame has been tracked yet")
+        if not final and iteration is None:
+            raise ValueError("save_gaussians: an iteration, or final=True")
+        sub = "final" if final else "iteration_{}".format(str(iteration))
+        path = os.path.join(os.fspath(save_dir), "point_cloud", sub, "point_cloud.ply")
+        self.map.save_ply(path)
+        return path
+
+    def save_trajectory(self, save_dir, gt_w2c, iterations=None, final=False) -> float:
+        """eval_ate (utils/eval_utils.py:67-111) over the keyframes so far: `plot/trj_{label}.json` with trj_id, trj_est and
+        trj_gt (camera-to-world 4x4 lists: the float64 inverses of the float32 world-to-camera poses) and
+        `plot/stats_{label}.json` with evo's rmse, mean, median, std, min, max and sse (ate_statistics), label = "final" or
+        the four-digit `iterations`.  gt_w2c: a mapping frame id -> [4,4] world-to-camera.  Host only.  -> the RMSE."""
+        if not final and iterations is None:
+            raise ValueError("save_trajectory: iterations, or final=True")
+        if not self.keyframes:
+            raise RuntimeError("save_trajectory: no keyframe yet")
+
+        def f64(T):
+            T = T.detach().cpu().numpy() if isinstance(T, torch.Tensor) else np.asarray(T)
+            return T.astype(np.float64).reshape(4, 4)
+        ids = [int(k) for k in self.keyframes]
+        est, gt = [f64(self.poses[k]) for k in ids], [f64(gt_w2c[k]) for k in ids]
+        trj = dict(trj_id=ids, trj_est=[np.linalg.inv(T).tolist() for T in est], trj_gt=[np.linalg.inv(T).tolist() for T in gt])
+        stats = ate_statistics(np.stack(est), np.stack(gt))
+        plot_dir = os.path.join(os.fspath(save_dir), "plot")
+        os.makedirs(plot_dir, exist_ok=True)
+        label = "final" if final else "{:04}".format(int(iterations))
+        for name, data in ((f"trj_{label}.json", trj), (f"stats_{label}.json", stats)):
+            tmp = os.path.join(plot_dir, name + ".tmp")
+            with open(tmp, "w", encoding="utf-8") as f:
+                json.dump(data, f, indent=4)
+            os.replace(tmp, os.path.join(plot_dir, name))
+        return stats["rmse"]
 
     def render(self, w2c: torch.Tensor) -> Dict[str, torch.Tensor]:
         """The map seen from a world-to-camera pose: copies of color [3,H,W], depth, opacity [1,H,W], language [F,H,W],
