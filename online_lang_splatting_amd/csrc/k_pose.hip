@@ -18,8 +18,15 @@
 // operation rounded once — the unfused sequence, bit for bit its restatement tests/adam_ref.py (tests/test_gpu_pose.py);
 // torch's CPU build departs from it by its own fused multiply-adds, hence the golden file's tolerances; SE3_exp with the
 // reference's small-angle branches (SO3_exp / V, utils/pose_utils.py:26-58); fp32 matrix products in torch's
-// row-times-column order.  Pinned by golden vectors generated from the reference's own SE3_exp / update_pose / Camera
-// (tests/golden/make_golden_pose.py).
+// row-times-column order.  The geometry half — W, W2, the angle and its branch on angle < 1e-5f, a, b, bV, cV, Rm, Vm, t3,
+// N = E @ T_w2c with its last row reset, the converged flag, the transpose, full_proj, the cofactor inverse — is, like the
+// Adam half, the unfused sequence written below and nothing else: bit for bit its restatement tests/pose_ref.py, given the
+// device's sinf and cosf of the angle (tests/test_gpu_pose_pinned.py: on an MI355X sinf is float32(sin) of the double
+// sine on every case and cosf is within one ulp of it), through olsr_pose_step, the gated and gradient-free calls,
+// olsr_window_pose_step and the device-side step count.  Pinned by golden vectors generated from the reference's own SE3_exp /
+// update_pose / Camera: sequences of tracking's magnitudes (tests/golden/make_golden_pose.py) and single steps that
+// resolve every term, angles up to 1 rad (tests/golden/make_golden_pose_wide.py, tests/test_pose_ref_cpu.py).  Changing
+// the order of an operation here changes bits that those tests hold.
 #include "olsr_device.h"
 #include "olsr_kernels.h"
 

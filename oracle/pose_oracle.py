@@ -8,11 +8,22 @@ tracking loop:
   SO3_exp / V with their small-angle branches                                            utils/pose_utils.py:26-58
   Camera.world_view_transform / full_proj_transform / camera_center                      utils/camera_utils.py:103-117
 
+SE3_exp, the convergence test and the camera matrices are those of tests/pose_ref.py — the one float32 statement of the
+geometry half, which olsr_pose_step equals bit for bit (tests/test_gpu_pose_pinned.py) — fed with the double sine and cosine
+of the float32 angle, rounded to float32; the thresholds are float32, as the reference's tensor comparisons make them.
+
 Pinned by tests/golden/pose.npz, generated from the reference's own functions (tests/golden/make_golden_pose.py,
 tests/test_pose_oracle_golden.py)."""
 import math
+import os
+import sys
 
 import numpy as np
+
+_TESTS = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests")
+if _TESTS not in sys.path:
+    sys.path.insert(0, _TESTS)
+import pose_ref  # noqa: E402
 
 f32 = np.float32
 
@@ -23,24 +34,10 @@ def skew(x):
 
 
 def se3_exp(tau):
-    """utils/pose_utils.py:61-76 (tau = [rho | theta])."""
+    """utils/pose_utils.py:61-76 (tau = [rho | theta]): pose_ref.apply_tau on the identity, where E @ I is E."""
     tau = np.asarray(tau, dtype=f32)
-    rho, theta = tau[:3], tau[3:]
-    W = skew(theta)
-    W2 = (W @ W).astype(f32)
-    angle = f32(np.sqrt(f32(theta[0] * theta[0] + theta[1] * theta[1] + theta[2] * theta[2])))
-    eye = np.eye(3, dtype=f32)
-    if angle < 1e-5:
-        R = eye + W + f32(0.5) * W2
-        V = eye + f32(0.5) * W + f32(1.0 / 6.0) * W2
-    else:
-        s, c = f32(np.sin(angle)), f32(np.cos(angle))
-        R = eye + (s / angle) * W + ((f32(1) - c) / (angle * angle)) * W2
-        V = eye + W * ((f32(1) - c) / (angle * angle)) + W2 * ((angle - s) / (angle * angle * angle))
-    T = np.eye(4, dtype=f32)
-    T[:3, :3] = R
-    T[:3, 3] = (V @ rho).astype(f32)
-    return T
+    s, c = pose_ref.host_sincos(pose_ref.angle_of(tau))
+    return pose_ref.apply_tau(np.eye(4, dtype=f32), tau, s, c)[0].reshape(4, 4)
 
 
 class PoseOracle:
@@ -85,21 +82,23 @@ class PoseOracle:
             self.m[i], self.v[i] = m, v
         self.tau = delta[:6].copy()
         self.exposure = (self.exposure + delta[6:]).astype(f32)
-        self.T_w2c = (se3_exp(self.tau) @ self.T_w2c).astype(f32)
-        self.T_w2c[3] = (0, 0, 0, 1)
-        t = self.tau
-        self.converged = bool(f32(np.sqrt(f32(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3] + t[4] * t[4] + t[5] * t[5])))
-                              < self.thr)
+        s, c = pose_ref.host_sincos(pose_ref.angle_of(self.tau))
+        T16, flag = pose_ref.apply_tau(self.T_w2c, self.tau, s, c, threshold=self.thr)
+        self.T_w2c = T16.reshape(4, 4)
+        self.converged = bool(flag)
         return self.converged
+
+    def _derived(self):
+        return pose_ref.derive(self.T_w2c, self.proj)
 
     @property
     def viewmatrix(self):       # world_view_transform = getWorld2View2(R, T)^T
-        return self.T_w2c.T.copy()
+        return self._derived()[0:16].reshape(4, 4)
 
     @property
     def projmatrix(self):       # full_proj_transform = world_view_transform @ projection_matrix
-        return (self.viewmatrix @ self.proj).astype(f32)
+        return self._derived()[16:32].reshape(4, 4)
 
     @property
     def campos(self):           # world_view_transform.inverse()[3, :3]
-        return np.linalg.inv(self.viewmatrix.astype(np.float64))[3, :3].astype(f32)
+        return self._derived()[32:35]

@@ -1,12 +1,13 @@
 """numpy restatement of mapping's bundle adjustment (include/olsr.h: olsr_window_pose_step, olsr_isotropic_reg,
-olsr_adam_step_groups_reg).  The window step is, per view, the pose step of tests/adam_ref.py (the Adam words, bit for bit
-what the kernel computes) and of oracle/pose_oracle.py (SE3_exp and the camera matrices, to rounding); the regulariser is
-written from the header's arithmetic.  Pinned to the reference's own run by tests/test_window_ba_ref_golden.py
-(tests/golden/window_ba.npz)."""
+olsr_adam_step_groups_reg).  The window step is, per view, the pose step of tests/adam_ref.py (the Adam words) and of
+tests/pose_ref.py (SE3_exp, the convergence flag and the camera matrices): both bit for bit what the kernel computes, given the
+float32 sine and cosine of the angle — here the double ones rounded to float32 (pose_ref.host_sincos), which the device's
+may miss by an ulp (tests/test_gpu_pose_pinned.py searches the neighbours); the regulariser is written from the header's
+arithmetic.  Pinned to the reference's own run by tests/test_window_ba_ref_golden.py (tests/golden/window_ba.npz)."""
 import numpy as np
 
 import adam_ref
-from oracle.pose_oracle import se3_exp
+import pose_ref
 
 f32 = np.float32
 POSE, EXPOSURE = 1, 2
@@ -25,13 +26,8 @@ def make_states(R, T, exposure):
 
 
 def derive_matrices(state, proj):
-    """Words 16..51 of one state from its pose (the oracle's arithmetic: to rounding, not to the bit)."""
-    Tm = state[:16].reshape(4, 4)
-    view = Tm.T.copy()
-    state[16:32] = view.reshape(16)
-    state[32:48] = (view @ np.asarray(proj, dtype=f32)).astype(f32).reshape(16)
-    state[48:51] = np.linalg.inv(view.astype(np.float64))[3, :3].astype(f32)
-    state[51] = 0
+    """Words 16..51 of one state from its pose: pose_ref.derive, the kernel's bits."""
+    state[16:52] = pose_ref.derive(state[:16], proj)
 
 
 def window_step(states, status, flags, grad_tau, grad_exposure, proj, lrs, step=None, gated=None, thr=1e-4):
@@ -48,12 +44,8 @@ def window_step(states, status, flags, grad_tau, grad_exposure, proj, lrs, step=
             a = adam_ref.pose_step_adam(st, grad_tau[v], grad_exposure[v] if fl & EXPOSURE else None, lrs, k)
             st[52:58], st[58:64], st[64:70] = a["tau_m"], a["tau_v"], a["tau"]
             st[70:72], st[72:74], st[74:76] = a["exposure"], a["exposure_m"], a["exposure_v"]
-            Tn = (se3_exp(a["tau"]) @ st[:16].reshape(4, 4)).astype(f32)
-            Tn[3] = (0, 0, 0, 1)
-            st[:16] = Tn.reshape(16)
-            t = a["tau"]
-            nrm = f32(np.sqrt(f32(t[0] * t[0] + t[1] * t[1] + t[2] * t[2] + t[3] * t[3] + t[4] * t[4] + t[5] * t[5])))
-            status[v, 0] = int(nrm < f32(thr))
+            sn, cs = pose_ref.host_sincos(pose_ref.angle_of(a["tau"]))
+            st[:16], status[v, 0] = pose_ref.apply_tau(st[:16], a["tau"], sn, cs, threshold=thr)
             status[v, 1] += 1
         elif fl & EXPOSURE:
             a = adam_ref.pose_step_adam(st, np.zeros(6, f32), grad_exposure[v], lrs, k)
