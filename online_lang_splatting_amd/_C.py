@@ -25,6 +25,7 @@ import threading
 import torch
 
 from . import _abi
+from ._host import ptr, stream_ptr
 from ._lib import check, lib
 
 TILE = 15
@@ -66,9 +67,6 @@ def compiled_binding():
 def _t(x):
     return _EMPTY if x is None else x
 
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _c(t):
@@ -173,7 +171,7 @@ def _forward(F, bg, means3D, colors, language, opacity, scales, rotations, scale
         check(lib().olsr_forward(C.byref(s), _Resizer.cb, u_geom, _Resizer.cb, u_bin, _Resizer.cb, u_img, out_color.data_ptr(),
                                  out_lang.data_ptr() if F > 0 else None, out_depth.data_ptr(),
                                  out_opacity.data_ptr(), radii.data_ptr() if P else None,
-                                 n_touched.data_ptr() if P else None, C.byref(R), _stream(dev)))
+                                 n_touched.data_ptr() if P else None, C.byref(R), stream_ptr(dev)))
     return R.value, out_color, out_lang, radii, geom.t, binning.t, img.t, out_depth, out_opacity, n_touched
 
 
@@ -254,8 +252,7 @@ def _backward(F, bg, means3D, radii, colors, language, scales, rotations, scale_
         rad = radii.contiguous()
 
         def p(name):
-            t = g.get(name)
-            return t.data_ptr() if t is not None and t.numel() > 0 else None
+            return ptr(g.get(name))
         # Row scratch: the library sizes it from the forward's row count (olsr_backward in include/olsr.h) and allocates it
         # through the callback, once or twice; it may die at return (the caching allocator reuses blocks stream-ordered).
         scratch = _Resizer(dev)
@@ -266,7 +263,7 @@ def _backward(F, bg, means3D, radii, colors, language, scales, rotations, scale_
             dl.data_ptr() if dl is not None else None, dd.data_ptr() if dd is not None else None,
             p("dL_dmeans2D"), p("dL_dconic"), p("dL_dopacity"), p("dL_dcolors"), p("dL_dlanguage"), p("dL_ddepths"),
             p("dL_dmeans3D"), p("dL_dcov3D"), p("dL_dsh"), p("dL_dscales"), p("dL_drotations"), p("dL_dtau"),
-            p("dL_dtau_sum"), None, None, _stream(dev)))
+            p("dL_dtau_sum"), None, None, stream_ptr(dev)))
     return g
 
 
@@ -326,7 +323,7 @@ def mark_visible(means3D, viewmatrix, projmatrix):
         with torch.cuda.device(dev):
             m, v, p = _c(means3D), _c(viewmatrix), _c(projmatrix)
             check(lib().olsr_mark_visible(P, m.data_ptr(), v.data_ptr(), p.data_ptr() if p is not None else None,
-                                          present.data_ptr(), _stream(dev)))
+                                          present.data_ptr(), stream_ptr(dev)))
     return present
 
 

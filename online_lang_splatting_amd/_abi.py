@@ -160,12 +160,32 @@ class OlsrPoseParams(C.Structure):
                                            "converged_threshold")] + [("step", C.c_int32), ("_pad0", C.c_int32)]
 
 
+BATCHNORM_FIELDS = ("weight", "bias", "running_mean", "running_var")
+
+
+def _mlp_state(prefix, widths, stride, batchnorm):
+    """The state_dict entries of an nn.Sequential of Linear layers `widths`, `stride` modules per layer (Linear, [BatchNorm1d,]
+    activation), as ((name, shape), ...) in state_dict order, without num_batches_tracked."""
+    out = []
+    for k, (i, o) in enumerate(zip(widths, widths[1:])):
+        out += [(f"{prefix}.{stride * k}.weight", (o, i)), (f"{prefix}.{stride * k}.bias", (o,))]
+        if batchnorm and k < len(widths) - 2:   # BatchNorm1d on the layer's output, ahead of the ReLU
+            out += [(f"{prefix}.{stride * k + 1}.{n}", (o,)) for n in BATCHNORM_FIELDS]
+    return tuple(out)
+
+
+def set_widths(p, widths):
+    """Fills the n_widths / widths[] pair of a parameter struct; returns the struct."""
+    p.n_widths = len(widths)
+    p.widths[:len(widths)] = widths
+    return p
+
+
 # the online language autoencoder (OLSR_LANG_AE_*): compiled-in sizes, the flat parameter array in state_dict order
 LANG_AE_IN, LANG_AE_HIDDEN, LANG_AE_CODE, LANG_AE_PARAMS = 32, 24, 15, 2351
 LANG_AE_CODES_ROWS, LANG_AE_CODES_CHANNELS = 0, 1   # codes as [N,15] rows / as [15,N] = low_dim.T
-LANG_AE_STATE = (("encoder.0.weight", (24, 32)), ("encoder.0.bias", (24,)), ("encoder.2.weight", (15, 24)),
-                 ("encoder.2.bias", (15,)), ("decoder.0.weight", (24, 15)), ("decoder.0.bias", (24,)),
-                 ("decoder.2.weight", (32, 24)), ("decoder.2.bias", (32,)))
+LANG_AE_STATE = (_mlp_state("encoder", (LANG_AE_IN, LANG_AE_HIDDEN, LANG_AE_CODE), 2, False)
+                 + _mlp_state("decoder", (LANG_AE_CODE, LANG_AE_HIDDEN, LANG_AE_IN), 2, False))
 
 
 class OlsrLangAeParams(C.Structure):
@@ -179,8 +199,7 @@ class OlsrLangAeParams(C.Structure):
 LANG_QUERY_MAX_LAYERS, LANG_QUERY_MAX_PHRASES, LANG_QUERY_FEATURE_DIM, LANG_QUERY_DECODER_PARAMS = 8, 64, 768, 745536
 LANG_QUERY_WANT_MASK, LANG_QUERY_WANT_LABELS = 1, 2
 LANG_QUERY_WIDTHS = (32, 192, 256, 384, 512, 768)
-LANG_QUERY_STATE = tuple(e for k, (i, o) in enumerate(zip(LANG_QUERY_WIDTHS, LANG_QUERY_WIDTHS[1:]))
-                         for e in ((f"decoder.{2 * k}.weight", (o, i)), (f"decoder.{2 * k}.bias", (o,))))
+LANG_QUERY_STATE = _mlp_state("decoder", LANG_QUERY_WIDTHS, 2, False)
 
 
 class OlsrLangQueryParams(C.Structure):
@@ -197,23 +216,17 @@ LANG_ENCODER_IN_ROWS, LANG_ENCODER_IN_CHANNELS = 0, 1   # features as [N,768] ro
 LANG_ENCODER_WIDTHS = (768, 512, 256, 128, 64, 32)
 
 
-def _lang_encoder_state():
-    out = []
-    for k, (i, o) in enumerate(zip(LANG_ENCODER_WIDTHS, LANG_ENCODER_WIDTHS[1:])):
-        out += [(f"encoder.{3 * k}.weight", (o, i)), (f"encoder.{3 * k}.bias", (o,))]
-        if k < len(LANG_ENCODER_WIDTHS) - 2:   # BatchNorm1d on the layer's output, ahead of the ReLU
-            out += [(f"encoder.{3 * k + 1}.{n}", (o,)) for n in ("weight", "bias", "running_mean", "running_var")]
-    return tuple(out)
+LANG_ENCODER_STATE = _mlp_state("encoder", LANG_ENCODER_WIDTHS, 3, True)
 
-
-LANG_ENCODER_STATE = _lang_encoder_state()
+# struct olsr_lang_encoder_params and struct olsr_ss_encoder_params declare the same members
+_ENCODER_PARAMS_FIELDS = [("n_widths", C.c_int32), ("widths", C.c_int32 * 8), ("in_layout", C.c_int32), ("code_layout", C.c_int32),
+                          ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
 
 
 class OlsrLangEncoderParams(C.Structure):
     """struct olsr_lang_encoder_params, include/olsr.h."""
 
-    _fields_ = [("n_widths", C.c_int32), ("widths", C.c_int32 * 8), ("in_layout", C.c_int32), ("code_layout", C.c_int32),
-                ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
+    _fields_ = _ENCODER_PARAMS_FIELDS
 
 
 # the single-stage chain 768 -> 15 -> 768 (include/olsr_single_stage.h): one AutoencoderMLP, no online autoencoder
@@ -222,18 +235,8 @@ SS_ENCODER_WIDTHS = (768, 384, 192, 96, 48, 24, 15)
 SS_DECODER_WIDTHS = (15, 24, 48, 96, 192, 384, 384, 768)
 
 
-def _ss_encoder_state():
-    out = []
-    for k, (i, o) in enumerate(zip(SS_ENCODER_WIDTHS, SS_ENCODER_WIDTHS[1:])):
-        out += [(f"encoder.{3 * k}.weight", (o, i)), (f"encoder.{3 * k}.bias", (o,))]
-        if k < len(SS_ENCODER_WIDTHS) - 2:   # BatchNorm1d on the layer's output, ahead of the ReLU
-            out += [(f"encoder.{3 * k + 1}.{n}", (o,)) for n in ("weight", "bias", "running_mean", "running_var")]
-    return tuple(out)
-
-
-SS_ENCODER_STATE = _ss_encoder_state()
-SS_DECODER_STATE = tuple(e for k, (i, o) in enumerate(zip(SS_DECODER_WIDTHS, SS_DECODER_WIDTHS[1:]))
-                         for e in ((f"decoder.{2 * k}.weight", (o, i)), (f"decoder.{2 * k}.bias", (o,))))
+SS_ENCODER_STATE = _mlp_state("encoder", SS_ENCODER_WIDTHS, 3, True)
+SS_DECODER_STATE = _mlp_state("decoder", SS_DECODER_WIDTHS, 2, False)
 
 
 # a frame's ingest (include/olsr_frame_ingest.h)
@@ -254,8 +257,7 @@ MAP_PLY_MAX_M, MAP_PLY_MAX_F, MAP_PLY_MAX_WIDTH, MAP_PLY_BLOCK_ROWS, MAP_PLY_MAX
 class OlsrSsEncoderParams(C.Structure):
     """struct olsr_ss_encoder_params, include/olsr_single_stage.h."""
 
-    _fields_ = [("n_widths", C.c_int32), ("widths", C.c_int32 * 8), ("in_layout", C.c_int32), ("code_layout", C.c_int32),
-                ("plane_stride", C.c_int64), ("bn_eps", C.c_double)]
+    _fields_ = _ENCODER_PARAMS_FIELDS
 
 
 # the high-resolution language feature net (OLSR_HR_NET_*): HighResLanguageFeatureNet's layers in forward order as
@@ -280,7 +282,7 @@ HR_NET_LAYERS = (
     ("upsample3.0", "convT", 128, 256, "upsample3.1"),
     ("final_conv", "conv1", 768, 128, None),
 )
-HR_NET_BN_FIELDS = ("weight", "bias", "running_mean", "running_var")
+HR_NET_BN_FIELDS = BATCHNORM_FIELDS
 
 
 def _hr_net_state():
@@ -350,7 +352,7 @@ class OlsrLossFusion(C.Structure):
                 ("dL_ddepth", _fp), ("dL_dlanguage", _fp), ("loss", _fp), ("dL_dexposure", _fp), ("scratch", _fp)]
 
 
-def _ptr(t):
+def ptr(t):
     """data_ptr of a tensor, or None for an absent (None / empty) one — the reference maps
     empty tensors to nullptr the same way (contiguous().data<float>() of a 0-element tensor,
     tested with `!= nullptr` in CR/forward.cu:320,356)."""
@@ -371,20 +373,20 @@ def make_scene(*, P, D, M, F, width, height, tile, prefiltered, debug, bwd_mode,
     s.binning = int(binning)
     s.activations = int(activations)
     s.flags = int(flags)
-    s.background = _ptr(background)
-    s.means3D = _ptr(means3D)
-    s.shs = _ptr(shs)
-    s.colors_precomp = _ptr(colors_precomp)
-    s.language_precomp = _ptr(language_precomp)
-    s.opacities = _ptr(opacities)
-    s.scales = _ptr(scales)
-    s.rotations = _ptr(rotations)
-    s.cov3D_precomp = _ptr(cov3D_precomp)
-    s.viewmatrix = _ptr(viewmatrix)
-    s.projmatrix = _ptr(projmatrix)
-    s.projmatrix_raw = _ptr(projmatrix_raw)
-    s.cam_pos = _ptr(cam_pos)
-    s.tile_depth_cut = _ptr(tile_depth_cut)
+    s.background = ptr(background)
+    s.means3D = ptr(means3D)
+    s.shs = ptr(shs)
+    s.colors_precomp = ptr(colors_precomp)
+    s.language_precomp = ptr(language_precomp)
+    s.opacities = ptr(opacities)
+    s.scales = ptr(scales)
+    s.rotations = ptr(rotations)
+    s.cov3D_precomp = ptr(cov3D_precomp)
+    s.viewmatrix = ptr(viewmatrix)
+    s.projmatrix = ptr(projmatrix)
+    s.projmatrix_raw = ptr(projmatrix_raw)
+    s.cam_pos = ptr(cam_pos)
+    s.tile_depth_cut = ptr(tile_depth_cut)
     s.backward_row_capacity = int(backward_row_capacity)
-    s.depth_order_carry = _ptr(depth_order_carry)
+    s.depth_order_carry = ptr(depth_order_carry)
     return s

@@ -230,9 +230,10 @@ def debug_activate(activations, opacities=None, scales=None, rotations=None):
         if t is not None and t.numel() != P * per:
             raise RuntimeError("debug_activate: opacities [P(,1)], scales [P,3] and rotations [P,4] of one P")
     out = [None if t is None else torch.empty_like(t) for t in (opacities, scales, rotations)]
-    p = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
-    check(lib().olsr_debug_activate(P, int(activations), p(opacities), p(scales), p(rotations), p(out[0]), p(out[1]), p(out[2]),
-                                    C.c_void_p(torch.cuda.current_stream(given[0].device).cuda_stream)))
+    from ._host import ptr, stream_ptr
+    check(lib().olsr_debug_activate(P, int(activations), ptr(opacities), ptr(scales), ptr(rotations), ptr(out[0]), ptr(out[1]),
+                                    ptr(out[2]),
+                                    stream_ptr(given[0].device)))
     return tuple(out)
 
 

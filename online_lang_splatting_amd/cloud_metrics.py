@@ -11,22 +11,12 @@ approximate matching without the match matrix: the reference fills a dense [m,n]
 and the copy of emd.py the evaluation uses keeps nothing for a backward, so neither the matrix nor a backward is offered here;
 memory is O(n + m).  GPU only; there is no torch fallback.
 """
-import ctypes as C
-
 import numpy as np
 import torch
 
 from . import _abi
+from ._host import ptr, scratch_for, stream_ptr
 from ._lib import check, lib
-
-_scratch = {}   # (device, kind) -> uint8 tensor, grown on demand and reused
-
-
-def _scratch_for(device, kind, nbytes):
-    buf = _scratch.get((device, kind))
-    if buf is None or buf.numel() < nbytes:
-        buf = _scratch[(device, kind)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return buf
 
 
 def _points(who, name, t, device=None):
@@ -76,26 +66,18 @@ def _segments(who, xyz1, off1, xyz2, off2, names=("xyz1", "off1", "xyz2", "off2"
     return xyz1, off1, xyz2, off2, B, int(np.diff(off1).max()), int(np.diff(off2).max())
 
 
-def _ptr(t):
-    return t.data_ptr() if t.numel() else None
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
-
-
 def _emd(who, xyz1, off1, xyz2, off2):
     """-> (cost [B] float64, undivided; residual [B,2] float32; valid [B] int32; n1 [B] as a host array)."""
     xyz1, off1, xyz2, off2, B, max1, max2 = _segments(who, xyz1, off1, xyz2, off2)
     dev = xyz1.device
     L = lib()
-    scratch = _scratch_for(dev, "emd", L.olsr_emd_scratch_bytes(B, int(off1[-1]), int(off2[-1])))
+    scratch = scratch_for(dev, "emd", L.olsr_emd_scratch_bytes(B, int(off1[-1]), int(off2[-1])))
     cost = torch.empty(B, dtype=torch.float64, device=dev)
     residual = torch.empty((B, 2), dtype=torch.float32, device=dev)
     valid = torch.empty(B, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(L.olsr_emd_cost(B, off1.ctypes.data, off2.ctypes.data, max1, max2, _ptr(xyz1), _ptr(xyz2),
-                              cost.data_ptr(), residual.data_ptr(), valid.data_ptr(), scratch.data_ptr(), _stream(dev)))
+        check(L.olsr_emd_cost(B, off1.ctypes.data, off2.ctypes.data, max1, max2, ptr(xyz1), ptr(xyz2),
+                              cost.data_ptr(), residual.data_ptr(), valid.data_ptr(), scratch.data_ptr(), stream_ptr(dev)))
     return cost, residual, valid, np.diff(off1)
 
 
@@ -152,7 +134,7 @@ def chamfer_segments(x, offx, y, offy):
     x, offx, y, offy, B, maxx, maxy = _segments(who, x, offx, y, offy, ("x", "offx", "y", "offy"))
     dev = x.device
     L = lib()
-    scratch = _scratch_for(dev, "chamfer", L.olsr_chamfer_scratch_bytes(B, int(offx[-1]), int(offy[-1])))
+    scratch = scratch_for(dev, "chamfer", L.olsr_chamfer_scratch_bytes(B, int(offx[-1]), int(offy[-1])))
     mean = torch.empty((B, 2), dtype=torch.float64, device=dev)
     valid = torch.empty(B, dtype=torch.int32, device=dev)
     # (points no segment covers keep these values)
@@ -161,9 +143,9 @@ def chamfer_segments(x, offx, y, offy):
     ix = torch.full((x.shape[0],), -1, dtype=torch.int32, device=dev)
     iy = torch.full((y.shape[0],), -1, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        check(L.olsr_chamfer(B, offx.ctypes.data, offy.ctypes.data, maxx, maxy, _ptr(x), _ptr(y),
-                             _ptr(dx), _ptr(ix), _ptr(dy), _ptr(iy), mean.data_ptr(), valid.data_ptr(), scratch.data_ptr(),
-                             _stream(dev)))
+        check(L.olsr_chamfer(B, offx.ctypes.data, offy.ctypes.data, maxx, maxy, ptr(x), ptr(y),
+                             ptr(dx), ptr(ix), ptr(dy), ptr(iy), mean.data_ptr(), valid.data_ptr(), scratch.data_ptr(),
+                             stream_ptr(dev)))
     return mean, dx, ix, dy, iy
 
 

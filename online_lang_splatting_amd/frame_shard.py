@@ -25,6 +25,7 @@ from typing import Dict, List, Sequence
 import torch
 
 from . import _abi
+from ._host import ptr, stream_ptr
 from ._lib import check, lib
 
 
@@ -158,7 +159,7 @@ class GradientBucket:
                 self.row_mask.data_ptr() if self.row_mask is not None else None, other.flat.data_ptr(),
                 other.densify.data_ptr(), other.max_radii.data_ptr(),
                 other.row_mask.data_ptr() if other.row_mask is not None else None,
-                C.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)))
+                stream_ptr(self.flat.device)))
             if self.row_mask is not None and other.row_mask is None:
                 self.rows_unknown()
             return
@@ -183,14 +184,12 @@ class GradientBucket:
         if self.flat.is_cuda:
             P = self.flat.shape[0]
 
-            def p(t):
-                return t.data_ptr() if t is not None and t.numel() > 0 else None
             check(lib().olsr_accumulate_gradients(
-                P, self.layout.M, self.layout.F, 1 if first else 0, p(grads["dL_dmeans3D"]), p(grads.get("dL_dsh")),
-                p(grads["dL_dopacity"]), p(grads["dL_dscales"]), p(grads["dL_drotations"]),
-                p(grads.get("dL_dlanguage")), p(grads["dL_dmeans2D"]), radii.data_ptr(), self.flat.data_ptr(),
+                P, self.layout.M, self.layout.F, 1 if first else 0, ptr(grads["dL_dmeans3D"]), ptr(grads.get("dL_dsh")),
+                ptr(grads["dL_dopacity"]), ptr(grads["dL_dscales"]), ptr(grads["dL_drotations"]),
+                ptr(grads.get("dL_dlanguage")), ptr(grads["dL_dmeans2D"]), radii.data_ptr(), self.flat.data_ptr(),
                 self.densify.data_ptr(), self.max_radii.data_ptr(),
-                C.c_void_p(torch.cuda.current_stream(self.flat.device).cuda_stream)))
+                stream_ptr(self.flat.device)))
             self.rows_unknown()
             return
         if first:
@@ -341,7 +340,7 @@ class GradientBucket:
             # packed buffer sized exactly from a count that is read back - this exchange's one host synchronisation
             L, dev = lib(), self.flat.device
             multi = self._multi(group)
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = stream_ptr(dev)
             mask_p = self.row_mask.data_ptr() if self.row_mask is not None else None
             imax = torch.empty(2 * P, dtype=torch.int32, device=dev)
             scratch = torch.empty(max(1, int(L.olsr_sparse_exchange_scratch_ints(P))), dtype=torch.int32, device=dev)
@@ -437,7 +436,7 @@ class GradientBucket:
                                               device=dev),
                           status=torch.zeros(2, dtype=torch.int32, device=dev))
                 self._capped = st
-            stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            stream = stream_ptr(dev)
             mask_p = self.row_mask.data_ptr() if self.row_mask is not None else None
             check(lib().olsr_sparse_exchange_mask(P, width, self.flat.data_ptr(), mask_p, self.max_radii.data_ptr(),
                                                   st["imax"].data_ptr(), stream))
@@ -564,7 +563,7 @@ class FusedAdam:
         def p(name):
             t = params.get(name)
             return t.data_ptr() + 4 * r0 * per_row[name] if t is not None and t.numel() > 0 else None
-        stream = C.c_void_p(torch.cuda.current_stream(bucket.flat.device).cuda_stream)
+        stream = stream_ptr(bucket.flat.device)
         # rows a bucket's row mask proves zero are not read (olsr_adam_step_masked: the update stays dense, the bits are
         # torch.optim.Adam's); a row range that does not start on a mask word (64 rows) takes the unmasked step
         masked = self.use_row_masks and r0 % 64 == 0 and any(b.row_mask is not None for b in buckets)
@@ -700,8 +699,6 @@ class RasterWorkspace:
     def state_bytes(self):
         return self.geom.numel() + self.img.numel() + self.binning.numel() + self.scratch.numel()
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def set_scene(self, *, bg, means3D, opacities, scales, rotations, shs, language, viewmatrix, projmatrix,
                   projmatrix_raw, campos, tanfovx, tanfovy, sh_degree, scale_modifier=1.0, colors_precomp=None,
@@ -734,7 +731,7 @@ class RasterWorkspace:
             C.byref(self._scene), self.geom.data_ptr(), self.binning.data_ptr(), self.capacity, self.img.data_ptr(),
             o["color"].data_ptr(), o["language"].data_ptr() if self.F > 0 else None, o["depth"].data_ptr(),
             o["opacity"].data_ptr(), o["radii"].data_ptr(), o["n_touched"].data_ptr(), self.num_rendered.data_ptr(),
-            self.tile_order.data_ptr(), self._stream()))
+            self.tile_order.data_ptr(), stream_ptr(self.device)))
         return o
 
     def forward_loss(self, gt_image, gt_depth, gt_language=None, exposure=None, grad_mask=None, *, tracking=False,
@@ -774,7 +771,6 @@ class RasterWorkspace:
                                 lang_height=gt_language.shape[1] if lang else 0, initialization=int(bool(initialization)),
                                 alpha=float(alpha), rgb_boundary_threshold=float(rgb_boundary_threshold),
                                 lamda_lang=float(lamda_lang), one_minus_alpha=1.0 - float(alpha))
-        ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None  # noqa: E731
         if dL_dexposure_out is not None and dL_dexposure_out.numel() != 2:
             raise RuntimeError("forward_loss: dL_dexposure_out must hold two floats")
         dexp = dL_dexposure_out if dL_dexposure_out is not None else fl["dL_dexposure"]
@@ -788,7 +784,7 @@ class RasterWorkspace:
             C.byref(self._scene), self.geom.data_ptr(), self.binning.data_ptr(), self.capacity, self.img.data_ptr(),
             o["color"].data_ptr(), o["language"].data_ptr() if self.F > 0 else None, o["depth"].data_ptr(),
             o["opacity"].data_ptr(), o["radii"].data_ptr(), o["n_touched"].data_ptr(), self.num_rendered.data_ptr(),
-            self.tile_order.data_ptr(), C.byref(lf), self._stream()))
+            self.tile_order.data_ptr(), C.byref(lf), stream_ptr(self.device)))
         return dict(loss=fl["loss"], dL_dimage=fl["dL_dimage"], dL_ddepth=fl["dL_ddepth"],
                     dL_dlanguage=fl["dL_dlanguage"] if lang else None, dL_dexposure=dexp)
 
@@ -808,8 +804,6 @@ class RasterWorkspace:
                 raise RuntimeError(f"backward: tau_sum_out must be a contiguous float32[6] on {self.device}")
             g = dict(g, dL_dtau_sum=tau_sum_out)
 
-        def p(t):
-            return t.data_ptr() if t is not None and t.numel() > 0 else None
         bk = None
         if bucket is not None:
             bk = _abi.OlsrGradBucket(flat=bucket.flat.data_ptr(), densify=bucket.densify.data_ptr(),
@@ -822,11 +816,11 @@ class RasterWorkspace:
         check(lib().olsr_backward(
             C.byref(self._scene), self.out["radii"].data_ptr(), self.geom.data_ptr(), self.capacity,
             self.binning.data_ptr(), self.img.data_ptr(), _abi.ALLOC_FN(0), None, 0, self.scratch.data_ptr(),
-            self.row_capacity, p(dL_dcolor), p(dL_dlanguage), p(dL_ddepth),
-            p(g["dL_dmeans2D"]), p(g["dL_dconic"]), p(g["dL_dopacity"]), p(g["dL_dcolors"]), p(g["dL_dlanguage"]),
-            p(g["dL_ddepths"]), p(g["dL_dmeans3D"]), p(g["dL_dcov3D"]), p(g["dL_dsh"]), p(g["dL_dscales"]),
-            p(g["dL_drotations"]), p(g["dL_dtau"]), p(g["dL_dtau_sum"]), C.byref(bk) if bk is not None else None,
-            self.bwd_status.data_ptr(), self._stream()))
+            self.row_capacity, ptr(dL_dcolor), ptr(dL_dlanguage), ptr(dL_ddepth),
+            ptr(g["dL_dmeans2D"]), ptr(g["dL_dconic"]), ptr(g["dL_dopacity"]), ptr(g["dL_dcolors"]), ptr(g["dL_dlanguage"]),
+            ptr(g["dL_ddepths"]), ptr(g["dL_dmeans3D"]), ptr(g["dL_dcov3D"]), ptr(g["dL_dsh"]), ptr(g["dL_dscales"]),
+            ptr(g["dL_drotations"]), ptr(g["dL_dtau"]), ptr(g["dL_dtau_sum"]), C.byref(bk) if bk is not None else None,
+            self.bwd_status.data_ptr(), stream_ptr(self.device)))
         return g
 
     def backward_status(self):

@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._host import stream_ptr
 from ._lib import check, lib
 
 MODES = {"blocks": _abi.GRAD_MASK_BLOCKS, "global": _abi.GRAD_MASK_GLOBAL}
@@ -30,9 +31,6 @@ def _need(what, cond, msg):
     if not cond:
         raise ValueError(f"{what}: {msg}")
 
-
-def _stream(dev):
-    return C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
 
 
 def tracking_mask(image: torch.Tensor, edge_threshold: float, mode: str = "blocks", out: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -58,7 +56,7 @@ def tracking_mask(image: torch.Tensor, edge_threshold: float, mode: str = "block
         scratch = torch.empty(int(L.olsr_frontend_scratch_bytes(W * H)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         check(L.olsr_grad_mask(W, H, int(image.stride(0)), MODES[mode], float(edge_threshold), image.data_ptr(), out.data_ptr(),
-                               scratch.data_ptr() if scratch is not None else None, _stream(dev)))
+                               scratch.data_ptr() if scratch is not None else None, stream_ptr(dev)))
     return out
 
 
@@ -98,7 +96,7 @@ def ingest_frame(rgb_u8: torch.Tensor, depth: torch.Tensor, depth_scale: float, 
                                    plane_stride=int(out_image.stride(0)), depth_scale=depth_scale)
     with torch.cuda.device(dev):
         check(lib().olsr_frame_ingest(C.byref(p), rgb_u8.data_ptr(), depth.data_ptr(), out_image.data_ptr(), out_depth.data_ptr(),
-                                      _stream(dev)))
+                                      stream_ptr(dev)))
     return out_image, out_depth
 
 
@@ -122,7 +120,7 @@ def median_depth(depth: torch.Tensor, opacity: torch.Tensor, mask: Optional[torc
     scratch = torch.empty(int(L.olsr_frontend_scratch_bytes(N)), dtype=torch.uint8, device=dev)
     with torch.cuda.device(dev):
         check(L.olsr_median_depth(N, depth.data_ptr(), opacity.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                  scratch.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), _stream(dev)))
+                                  scratch.data_ptr(), out[0].data_ptr(), out[1].data_ptr(), stream_ptr(dev)))
     return out
 
 
@@ -202,7 +200,7 @@ class KeyframeSelector:
                                           kf_cutoff=self.kf_cutoff)
         L = lib()
         with torch.cuda.device(dev):
-            st = _stream(dev)
+            st = stream_ptr(dev)
             check(L.olsr_covisibility(P, n_touched.data_ptr(), C.byref(views), cur_vis.data_ptr(), self._counts.data_ptr(), st))
             check(L.olsr_keyframe_decide(C.byref(p), self._counts.data_ptr(), median.data_ptr(), cur_pose.data_ptr(),
                                          kf_poses.data_ptr() if K else None, self._record.data_ptr(), st))

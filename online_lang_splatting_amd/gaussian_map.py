@@ -24,6 +24,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _abi
+from ._host import ptr, stream_ptr
 from ._lib import check, lib
 from .frame_shard import FusedAdam, GradLayout
 
@@ -420,13 +421,10 @@ class GaussianMap:
     @staticmethod
     def _struct(b, P=None):
         def p(k):
-            t = b.get(k)
-            return t.data_ptr() if t is not None and t.numel() > 0 else None
+            return ptr(b.get(k))
         return _abi.OlsrMapBuffers(**{k: p(k) for k in ("means3D", "shs", "opacities", "scales", "rotations", "language",
                                                          "exp_avg", "exp_avg_sq", "kf_id", "n_obs", "stats", "max_radii")})
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- the edit primitive ----
     def _edit(self, ep: _abi.OlsrMapEditParams, drop_mask=None, z=None, append=None, P_new: Optional[int] = None):
@@ -438,7 +436,7 @@ class GaussianMap:
             self._scratch = torch.empty(need, dtype=torch.uint8, device=self.device)
         src = self._struct(self._bufs[self._front])
         check(L.olsr_map_edit_plan(P, C.byref(ep), C.byref(src), drop_mask.data_ptr() if drop_mask is not None else None,
-                                   self._scratch.data_ptr(), self.status.data_ptr(), self._stream()))
+                                   self._scratch.data_ptr(), self.status.data_ptr(), stream_ptr(self.device)))
         if P_new is None:
             P_new = int(self.status[0].item())   # the edit's one host synchronisation: the destination's size
         back = 1 - self._front
@@ -451,7 +449,7 @@ class GaussianMap:
         check(L.olsr_map_edit_apply(P, self.M, self.F, C.byref(ep), C.byref(src), z.data_ptr() if z is not None else None,
                                     C.byref(app) if app is not None else None, self._scratch.data_ptr(),
                                     self.status.data_ptr(), P_new, self._bufs[back]["cap"], C.byref(dst),
-                                    src_index.data_ptr() if P_new > 0 else None, self._stream()))
+                                    src_index.data_ptr() if P_new > 0 else None, stream_ptr(self.device)))
         self._front, self.P = back, P_new
         self.edits += 1
         self._views()

@@ -11,6 +11,7 @@ from collections import OrderedDict
 import torch
 
 from . import _abi, _flat_state
+from ._host import Outputs, planes, require_gpu_device, stream_ptr
 from ._lib import check, lib
 
 N_PACKED = _abi.HR_NET_PARAMS
@@ -86,15 +87,13 @@ class HighResLanguageNet:
     """HighResLanguageFeatureNet with its BatchNorm running statistics as one packed float32 array on `device`."""
 
     def __init__(self, device, state=None, eps: float = BN_EPS):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("HighResLanguageNet: a GPU device is required (there is no torch fallback)")
+        self.device = require_gpu_device(device, "HighResLanguageNet")
         if not float(eps) > 0.0:
             raise RuntimeError(f"hr_net: eps must be positive, got {eps!r}")
         self.flat = torch.zeros(N_PACKED, dtype=torch.float32, device=self.device)
         self.eps = float(eps)
         self._work = {}
-        self._out = {}
+        self._out = Outputs(self.device)
         if state is not None:
             self.load_state_dict(state)
 
@@ -105,24 +104,6 @@ class HighResLanguageNet:
         return unpack_hr_state(self.flat)
 
     # ---- calls ---------------------------------------------------------------------------------------------------------
-    def _planes(self, name, t, channels):
-        """-> (B, h, w, plane stride, [data pointer per item]).  No conversion and no copy: what cannot be read in place is an
-        error."""
-        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-            raise RuntimeError(f"hr_net.forward: {name} must be a float32 tensor on the GPU")
-        if t.device != self.device:
-            raise RuntimeError(f"hr_net.forward: {name} is on {t.device}, expected {self.device}")
-        t = t.detach()
-        if t.dim() == 3:
-            t = t.unsqueeze(0)
-        if t.dim() != 4 or t.shape[1] != channels or min(t.shape[0], t.shape[2], t.shape[3]) < 1:
-            raise RuntimeError(f"hr_net.forward: {name} has shape {tuple(t.shape)}, expected [{channels},h,w] or [B,{channels},h,w]")
-        B, _, h, w = t.shape
-        if (w > 1 and t.stride(3) != 1) or (h > 1 and t.stride(2) != w) or t.stride(1) < h * w:
-            raise RuntimeError(f"hr_net.forward: every channel plane of {name} must be contiguous and the planes must not "
-                               f"overlap (strides {tuple(t.stride())} for shape {tuple(t.shape)})")
-        return int(B), int(h), int(w), int(t.stride(1)), [t[b].data_ptr() for b in range(B)]
-
     def workspace(self, h, w, h3, w3, h2, w2):
         key = (h, w)
         t = self._work.get(key)
@@ -136,20 +117,16 @@ class HighResLanguageNet:
     def forward(self, fv, f3, f2, out=None, launches: int = 0):
         """fv [1,768,h,w], f3 [1,384,h3,w3], f2 [1,192,h2,w2] (or without the batch dimension; B > 1 runs item by item)
         -> [B,768,8h,8w].  Without `out` the result is a reusable buffer: the next call of the same size overwrites it."""
-        B, h, w, sv, pv = self._planes("fv", fv, C_FV)
-        B3, h3, w3, s3, p3 = self._planes("f3", f3, C_F3)
-        B2, h2, w2, s2, p2 = self._planes("f2", f2, C_F2)
+        B, h, w, sv, pv = planes("hr_net.forward: ", "fv", fv, C_FV, self.device)
+        B3, h3, w3, s3, p3 = planes("hr_net.forward: ", "f3", f3, C_F3, self.device)
+        B2, h2, w2, s2, p2 = planes("hr_net.forward: ", "f2", f2, C_F2, self.device)
         if not B == B3 == B2:
             raise RuntimeError(f"hr_net.forward: batch sizes differ ({B}, {B3}, {B2})")
         shape = (B, C_OUT, 8 * h, 8 * w)
         if out is None:
-            out = self._out.get(shape)
-            if out is None:
-                out = self._out[shape] = torch.empty(shape, dtype=torch.float32, device=self.device)
+            out = self._out.get(shape, shape)
         else:
-            if (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
-                    or tuple(out.shape) != shape):
-                raise RuntimeError(f"hr_net.forward: out must be a float32 {list(shape)} tensor on {self.device}")
+            self._out.check_out(f"hr_net.forward: out must be a float32 {list(shape)} tensor", out, shape, contiguous=False)
             if (out.stride(3) != 1 and 8 * w > 1) or out.stride(2) != 8 * w or out.stride(1) < 64 * h * w:
                 raise RuntimeError(f"hr_net.forward: every channel plane of out must be contiguous and the planes must not "
                                    f"overlap (strides {tuple(out.stride())})")
@@ -157,7 +134,7 @@ class HighResLanguageNet:
         p = _abi.OlsrHrNetParams(h=h, w=w, h3=h3, w3=w3, h2=h2, w2=w2, c_fv=C_FV, c_f3=C_F3, c_f2=C_F2, c_out=C_OUT,
                                  launches=int(launches), fv_stride=sv, f3_stride=s3, f2_stride=s2, out_stride=int(out.stride(1)),
                                  bn_eps=self.eps, workspace_bytes=work.numel())
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        stream = stream_ptr(self.device)
         with torch.cuda.device(self.device):
             for b in range(B):
                 check(lib().olsr_hr_net_forward(C.byref(p), pv[b], p3[b], p2[b], self.flat.data_ptr(), work.data_ptr(),

@@ -14,6 +14,7 @@ from typing import Dict, Optional, Sequence
 import torch
 
 from . import _abi
+from ._host import stream_ptr
 from ._lib import check, lib
 
 DEPTH_TRUNC = 100.0   # create_from_color_and_depth(depth_trunc=100.0), gaussian_model.py:211
@@ -82,7 +83,7 @@ def seed_rows(image: torch.Tensor, depth: torch.Tensor, w2c: torch.Tensor, intri
     scratch = torch.empty(int(L.olsr_keyframe_seed_scratch_bytes(W, H)), dtype=torch.uint8, device=dev)
     status, aux = torch.empty(8, **i32), torch.empty(4, **f32)
     with torch.cuda.device(dev):
-        stream = C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+        stream = stream_ptr(dev)
         check(L.olsr_keyframe_seed_plan(C.byref(p), image.data_ptr(), depth.data_ptr(),
                                         exposure.data_ptr() if exposure is not None else None, w2c.data_ptr(), C.byref(rows),
                                         staging["pix_index"].data_ptr(), scratch.data_ptr(), status.data_ptr(), aux.data_ptr(),

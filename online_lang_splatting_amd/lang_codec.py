@@ -7,12 +7,13 @@ Mirrors EncoderDecoderOnline (language/autoencoder/model.py:314-354) and BackEnd
 Adam step, in two launches and without a host read.  GPU only; there is no torch fallback.
 """
 import ctypes as C
-from collections import OrderedDict
 from typing import Optional, Tuple
 
 import torch
 
-from . import _abi, _flat_state
+from . import _abi
+from ._flat_state import FlatNet
+from ._host import Outputs, gpu_float32, stream_ptr
 from ._lib import check, lib
 
 LAYOUTS = {"rows": _abi.LANG_AE_CODES_ROWS, "channels": _abi.LANG_AE_CODES_CHANNELS}
@@ -26,56 +27,36 @@ def _layout(layout):
 
 def _rows(name, t, width, dev):
     """[N, width] float32 rows on the codec's device (no conversion: a CPU or float64 tensor is an error, not a copy)."""
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be a float32 tensor on the GPU")
-    if t.device != dev:
-        raise RuntimeError(f"{name} is on {t.device}, expected {dev}")
+    t = gpu_float32(name, t, dev)
     if t.dim() != 2 or t.shape[1] != width or t.shape[0] < 1:
         raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected [N,{width}] with N >= 1")
-    return t.detach().contiguous()
+    return t.contiguous()
 
 
-_WHAT = ("flat parameter array", "state_dict")
-
-
-def state_views(flat):
-    """name -> view of a flat [2351] tensor in the module's shape, in state_dict order."""
-    return _flat_state.views(flat, _abi.LANG_AE_STATE, "lang_codec", _WHAT[0])
-
-
-def load_state(flat, state):
-    """Copies a state_dict of EncoderDecoderOnline into a flat [2351] tensor; keys and shapes must be the module's."""
-    _flat_state.load(flat, state, _abi.LANG_AE_STATE, "lang_codec", _WHAT, "the sizes 32 / 24 / 15 are compiled into the kernels")
-
-
-class OnlineLanguageCodec:
+class OnlineLanguageCodec(FlatNet):
     """The 32 -> 24 -> 15 -> 24 -> 32 autoencoder with its Adam state, all on `device`.
 
     flat [2351]: the parameters in state_dict order (views of it: self.views); exp_avg / exp_avg_sq: Adam's moments in the
     same order; step_dev int32[1]: the steps done, counted on the device, so that a loop of train_step calls is enqueued
-    without a synchronisation.  Outputs (loss, codes) are reusable buffers: the next call of the same kind overwrites them."""
+    without a synchronisation.  Outputs (loss, codes) are reusable buffers: the next call of the same kind overwrites them.
+    load_state_dict takes a state_dict of EncoderDecoderOnline (a reference online_15_*.pth) and leaves Adam's state as it is."""
+
+    TABLE, WHO, WHAT = _abi.LANG_AE_STATE, "lang_codec", ("flat parameter array", "state_dict")
+    HINT = "the sizes 32 / 24 / 15 are compiled into the kernels"
 
     def __init__(self, device, seed: Optional[int] = None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("OnlineLanguageCodec: a GPU device is required (there is no torch fallback)")
+        super().__init__(device)
         f32 = dict(dtype=torch.float32, device=self.device)
-        self.flat = torch.zeros(_abi.LANG_AE_PARAMS, **f32)
         self.exp_avg = torch.zeros(_abi.LANG_AE_PARAMS, **f32)
         self.exp_avg_sq = torch.zeros(_abi.LANG_AE_PARAMS, **f32)
         self.step_dev = torch.zeros(1, dtype=torch.int32, device=self.device)
         self.loss = torch.zeros(4, **f32)
         self._scratch = None
         self._scratch_n = 0
-        self._out = {}
+        self._out = Outputs(self.device)
         self.reset_parameters(seed)
 
     # ---- parameters ----------------------------------------------------------------------------------------------------
-    @property
-    def views(self):
-        """name -> view of `flat` in the module's shape."""
-        return state_views(self.flat)
-
     def reset_parameters(self, seed: Optional[int] = None):
         """nn.Linear's default initialisation (uniform in +-1/sqrt(fan_in) for weight and bias), drawn on the CPU."""
         g = torch.Generator()
@@ -96,26 +77,9 @@ class OnlineLanguageCodec:
         self.exp_avg_sq.zero_()
         self.step_dev.zero_()
 
-    def state_dict(self):
-        """Keys and shapes of EncoderDecoderOnline.state_dict(); clones."""
-        return OrderedDict((k, v.clone()) for k, v in self.views.items())
-
-    def load_state_dict(self, state):
-        """A state_dict of EncoderDecoderOnline (a reference online_15_*.pth); Adam's state is left as it is."""
-        load_state(self.flat, state)
-
     # ---- calls ---------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _buffer(self, key, shape):
-        t = self._out.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._out[key] = torch.empty(shape, dtype=torch.float32, device=self.device)
-        return t
-
     def _codes_buffer(self, key, N, layout):
-        return self._buffer(key, (N, _abi.LANG_AE_CODE) if layout == "rows" else (_abi.LANG_AE_CODE, N))
+        return self._out.get(key, (N, _abi.LANG_AE_CODE) if layout == "rows" else (_abi.LANG_AE_CODE, N))
 
     def train_step(self, features, lr: float, codes: Optional[str] = "pre", layout: str = "rows", grad_out=None,
                    step: int = 0) -> Tuple[torch.Tensor, Optional[torch.Tensor]]:
@@ -144,9 +108,9 @@ class OnlineLanguageCodec:
                                             self.exp_avg_sq.data_ptr(), self.step_dev.data_ptr(), self.loss.data_ptr(),
                                             out.data_ptr() if codes == "pre" else None,
                                             None if grad_out is None else grad_out.data_ptr(), self._scratch.data_ptr(),
-                                            self._stream()))
+                                            stream_ptr(self.device)))
             if codes == "post":
-                check(L.olsr_lang_ae_encode(N, x.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), self._stream()))
+                check(L.olsr_lang_ae_encode(N, x.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), stream_ptr(self.device)))
         return self.loss, out
 
     def encode(self, features, layout: str = "rows", out=None):
@@ -157,7 +121,7 @@ class OnlineLanguageCodec:
         if out is None:
             out = self._codes_buffer("encoded", N, layout)
         with torch.cuda.device(self.device):
-            check(lib().olsr_lang_ae_encode(N, x.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), self._stream()))
+            check(lib().olsr_lang_ae_encode(N, x.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), stream_ptr(self.device)))
         return out
 
     def decode(self, codes, layout: str = "rows"):
@@ -174,9 +138,9 @@ class OnlineLanguageCodec:
         else:
             c = _rows("decode: codes", codes, _abi.LANG_AE_CODE, self.device)
             N = c.shape[0]
-        out = self._buffer("decoded", (N, _abi.LANG_AE_IN))
+        out = self._out.get("decoded", (N, _abi.LANG_AE_IN))
         with torch.cuda.device(self.device):
-            check(lib().olsr_lang_ae_decode(N, c.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), self._stream()))
+            check(lib().olsr_lang_ae_decode(N, c.data_ptr(), self.flat.data_ptr(), lay, out.data_ptr(), stream_ptr(self.device)))
         return out
 
     def language_target(self, features, hw=(192, 192)):
@@ -187,3 +151,13 @@ class OnlineLanguageCodec:
             raise RuntimeError(f"language_target: features must be [{h * w},32] for hw = {(h, w)}")
         out = torch.empty(_abi.LANG_AE_CODE, h * w, dtype=torch.float32, device=self.device)
         return self.encode(features, "channels", out=out).view(_abi.LANG_AE_CODE, h, w)
+
+
+def state_views(flat):
+    """name -> view of a flat [2351] tensor in the module's shape, in state_dict order."""
+    return OnlineLanguageCodec.views_of(flat)
+
+
+def load_state(flat, state):
+    """Copies a state_dict of EncoderDecoderOnline into a flat [2351] tensor; keys and shapes must be the module's."""
+    OnlineLanguageCodec.load_into(flat, state)

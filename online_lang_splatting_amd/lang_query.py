@@ -14,8 +14,9 @@ from typing import Optional, Tuple
 
 import torch
 
-from . import _abi, _flat_state
-from ._flat_state import CHECKPOINT_PREFIX
+from . import _abi
+from ._flat_state import CHECKPOINT_PREFIX, FlatNet
+from ._host import Outputs, gpu_float32, stream_ptr
 from ._lib import check, lib
 from .lang_codec import OnlineLanguageCodec
 
@@ -23,52 +24,31 @@ N_DECODER = _abi.LANG_QUERY_DECODER_PARAMS
 FEATURE_DIM = _abi.LANG_QUERY_FEATURE_DIM
 
 
-_WHAT = ("flat decoder array", "decoder state")
+class LanguageDecoder(FlatNet):
+    """The general decoder 32 -> 192 -> 256 -> 384 -> 512 -> 768 (AutoencoderMLP.decoder) as a flat float32 array on `device`."""
+
+    TABLE, WHO, WHAT = _abi.LANG_QUERY_STATE, "lang_query", ("flat decoder array", "decoder state")
+    HINT = f"the widths {_abi.LANG_QUERY_WIDTHS} are compiled into the kernels"
+    PREFIX, KEEP = CHECKPOINT_PREFIX, "decoder."
 
 
 def decoder_views(flat):
     """name -> view of a flat [745536] tensor in the shapes of AutoencoderMLP.decoder, in state_dict order."""
-    return _flat_state.views(flat, _abi.LANG_QUERY_STATE, "lang_query", _WHAT[0])
+    return LanguageDecoder.views_of(flat)
 
 
 def load_decoder_state(flat, state):
     """Copies the decoder of an AutoencoderMLP into a flat [745536] tensor.  `state` is a Lightning checkpoint
     ({"state_dict": {"model.decoder.0.weight": ...}}, what load_from_checkpoint reads), its state_dict, or a plain
     AutoencoderMLP state dict; encoder and BatchNorm entries are ignored, the decoder's names and shapes must be the module's."""
-    _flat_state.load(flat, state, _abi.LANG_QUERY_STATE, "lang_query", _WHAT,
-                     f"the widths {_abi.LANG_QUERY_WIDTHS} are compiled into the kernels", CHECKPOINT_PREFIX, "decoder.")
-
-
-class LanguageDecoder:
-    """The general decoder 32 -> 192 -> 256 -> 384 -> 512 -> 768 (AutoencoderMLP.decoder) as a flat float32 array on `device`."""
-
-    def __init__(self, device, state=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("LanguageDecoder: a GPU device is required (there is no torch fallback)")
-        self.flat = torch.zeros(N_DECODER, dtype=torch.float32, device=self.device)
-        if state is not None:
-            self.load_state_dict(state)
-
-    @property
-    def views(self):
-        return decoder_views(self.flat)
-
-    def load_state_dict(self, state):
-        load_decoder_state(self.flat, state)
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self.views.items())
+    LanguageDecoder.load_into(flat, state)
 
 
 def _embeds(name, t, dev, allow_empty=False):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.float32:
-        raise RuntimeError(f"{name} must be a float32 tensor on the GPU")
-    if t.device != dev:
-        raise RuntimeError(f"{name} is on {t.device}, expected {dev}")
+    t = gpu_float32(name, t, dev)
     if t.dim() != 2 or t.shape[1] != FEATURE_DIM or (t.shape[0] < 1 and not allow_empty):
         raise RuntimeError(f"{name} has shape {tuple(t.shape)}, expected [n,{FEATURE_DIM}] with n >= 1")
-    return t.detach()
+    return t
 
 
 class LanguageQuery:
@@ -87,7 +67,7 @@ class LanguageQuery:
         self._pos = self._neg = None
         self._labels = torch.zeros(0, FEATURE_DIM, dtype=torch.float32, device=self.device)
         self._phrases = None
-        self._out = {}
+        self._out, self._scratch = Outputs(self.device), None
 
     # ---- phrases -------------------------------------------------------------------------------------------------------
     def _rebuild(self):
@@ -131,25 +111,13 @@ class LanguageQuery:
         return (0 if self._pos is None else self._pos.shape[0], self._labels.shape[0], 0 if self._neg is None else self._neg.shape[0])
 
     # ---- calls ---------------------------------------------------------------------------------------------------------
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-
-    def _buffer(self, key, shape, dtype=torch.float32):
-        t = self._out.get(key)
-        if t is None or tuple(t.shape) != tuple(shape):
-            t = self._out[key] = torch.empty(shape, dtype=dtype, device=self.device)
-        return t
-
     def _codes(self, who, codes):
-        if not isinstance(codes, torch.Tensor) or not codes.is_cuda or codes.dtype != torch.float32:
-            raise RuntimeError(f"{who}: codes must be a float32 tensor on the GPU")
-        if codes.device != self.device:
-            raise RuntimeError(f"{who}: codes is on {codes.device}, expected {self.device}")
+        codes = gpu_float32(f"{who}: codes", codes, self.device)
         if codes.dim() == 2:   # [15,N]: a map of one row
             codes = codes.unsqueeze(1)
         if codes.dim() != 3 or codes.shape[0] != _abi.LANG_AE_CODE or codes.shape[1] < 1 or codes.shape[2] < 1:
             raise RuntimeError(f"{who}: codes has shape {tuple(codes.shape)}, expected [15,h,w] (or [15,N])")
-        return codes.detach().contiguous()
+        return codes.contiguous()
 
     def _params(self, who, codes, decode_hw, out_hw, want_mask=False, want_labels=False):
         if self._phrases is None:
@@ -160,19 +128,17 @@ class LanguageQuery:
         if min(dh, dw, oh, ow) < 1:
             raise RuntimeError(f"{who}: decode_hw = {decode_hw} and out_hw = {out_hw} must be positive")
         n_pos, n_lab, _ = self.counts
-        p = _abi.OlsrLangQueryParams(n_widths=len(_abi.LANG_QUERY_WIDTHS), K=self._phrases.shape[0], n_pos=n_pos, n_labels=n_lab,
+        p = _abi.OlsrLangQueryParams(K=self._phrases.shape[0], n_pos=n_pos, n_labels=n_lab,
                                      in_width=w, in_height=h, dec_width=dw, dec_height=dh, out_width=ow, out_height=oh,
                                      thresh=float(self.thresh),
                                      flags=(_abi.LANG_QUERY_WANT_MASK if want_mask else 0) | (_abi.LANG_QUERY_WANT_LABELS if want_labels else 0))
-        for k, v in enumerate(_abi.LANG_QUERY_WIDTHS):
-            p.widths[k] = v
-        return p
+        return _abi.set_widths(p, _abi.LANG_QUERY_WIDTHS)
 
     def _sims(self, p, codes):
-        sims = self._buffer("sims", (p.K, p.dec_height, p.dec_width))
+        sims = self._out.get("sims", (p.K, p.dec_height, p.dec_width))
         with torch.cuda.device(self.device):
             check(lib().olsr_lang_query_sims(C.byref(p), codes.data_ptr(), self.codec.flat.data_ptr(), self.decoder.flat.data_ptr(),
-                                             self._phrases.data_ptr(), sims.data_ptr(), self._stream()))
+                                             self._phrases.data_ptr(), sims.data_ptr(), stream_ptr(self.device)))
         return sims
 
     def similarities(self, codes, decode_hw: Optional[Tuple[int, int]] = None):
@@ -210,19 +176,19 @@ class LanguageQuery:
         H, W = p.out_height, p.out_width
         L = lib()
         nbytes = L.olsr_lang_query_scratch_bytes(C.byref(p))
-        scratch = self._out.get("scratch")
+        scratch = self._scratch
         if scratch is None or scratch.numel() < nbytes:
-            scratch = self._out["scratch"] = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-        out = OrderedDict(relevancy=self._buffer("relevancy", (n_pos, H, W)), smoothed=self._buffer("smoothed", (n_pos, H, W)),
-                          blended=self._buffer("blended", (n_pos, H, W)), score=self._buffer("score", (n_pos,)),
-                          coord=self._buffer("coord", (n_pos, 2), torch.int32), minmax=self._buffer("minmax", (n_pos, 2)),
-                          mask=self._buffer("mask", (n_pos, H, W), torch.uint8))
+            scratch = self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        out = OrderedDict(relevancy=self._out.get("relevancy", (n_pos, H, W)), smoothed=self._out.get("smoothed", (n_pos, H, W)),
+                          blended=self._out.get("blended", (n_pos, H, W)), score=self._out.get("score", (n_pos,)),
+                          coord=self._out.get("coord", (n_pos, 2), torch.int32), minmax=self._out.get("minmax", (n_pos, 2)),
+                          mask=self._out.get("mask", (n_pos, H, W), torch.uint8))
         if n_lab > 0:
-            out["labels"] = self._buffer("labels", (H, W), torch.int32)
+            out["labels"] = self._out.get("labels", (H, W), torch.int32)
         with torch.cuda.device(self.device):
             check(L.olsr_lang_query_relevancy(C.byref(p), sims.data_ptr(), out["relevancy"].data_ptr(), out["smoothed"].data_ptr(),
                                               out["blended"].data_ptr(), out["score"].data_ptr(), out["coord"].data_ptr(),
                                               out["minmax"].data_ptr(), out["mask"].data_ptr(),
-                                              out["labels"].data_ptr() if n_lab > 0 else None, scratch.data_ptr(), self._stream()))
+                                              out["labels"].data_ptr() if n_lab > 0 else None, scratch.data_ptr(), stream_ptr(self.device)))
         out["similarities"] = sims
         return out

@@ -10,78 +10,29 @@ and SingleStageTargets.  The 2-D evaluation decodes a rendered code map with mod
 QueryEvaluator and tsdf.label_points take it as it is.  GPU only; there is no torch fallback.
 """
 import ctypes as C
-from collections import OrderedDict
 from typing import Dict, Sequence
 
 import torch
 
-from . import _abi, _flat_state
-from ._flat_state import CHECKPOINT_PREFIX
+from . import _abi
+from ._flat_state import CHECKPOINT_PREFIX, BatchNormEncoder, FlatNet
+from ._host import Outputs, stream_ptr
 from ._lib import OlsrError, check, lib
 from .lang_codec import _layout
-from .lang_encoder import BN_EPS, feature_items
+from .lang_encoder import feature_items
 from .lang_query import FEATURE_DIM, LanguageQuery
 
 N_ENCODER, N_DECODER = _abi.SS_ENCODER_PARAMS, _abi.SS_DECODER_PARAMS
 CODE_DIM = _abi.SS_ENCODER_WIDTHS[-1]
 MASK_THRESH = 0.5   # evaluate_langslam.py's --mask_thresh
 
-_WHAT_E = ("flat encoder array", "encoder state")
-_WHAT_D = ("flat decoder array", "decoder state")
-_WHO = "lang_single_stage"
 
-
-def encoder_views(flat):
-    """name -> view of a flat [396927] tensor in the shapes of the single-stage AutoencoderMLP.encoder, in state_dict order."""
-    return _flat_state.views(flat, _abi.SS_ENCODER_STATE, _WHO, _WHAT_E[0])
-
-
-def decoder_views(flat):
-    """name -> view of a flat [542544] tensor in the shapes of the single-stage AutoencoderMLP.decoder, in state_dict order."""
-    return _flat_state.views(flat, _abi.SS_DECODER_STATE, _WHO, _WHAT_D[0])
-
-
-def load_encoder_state(flat, state):
-    """Copies the encoder of a single-stage AutoencoderMLP into a flat [396927] tensor.  `state` is a Lightning checkpoint
-    ({"state_dict": {"model.encoder.0.weight": ...}}), its state_dict, or a plain AutoencoderMLP state dict; decoder entries
-    and num_batches_tracked are ignored, the encoder's names and shapes must be the module's."""
-    _flat_state.load(flat, state, _abi.SS_ENCODER_STATE, _WHO, _WHAT_E,
-                     f"the widths {_abi.SS_ENCODER_WIDTHS} are compiled into the kernel", CHECKPOINT_PREFIX, "encoder.")
-
-
-def load_decoder_state(flat, state):
-    """Copies the decoder of a single-stage AutoencoderMLP into a flat [542544] tensor; `state` as load_encoder_state takes it,
-    encoder and BatchNorm entries are ignored."""
-    _flat_state.load(flat, state, _abi.SS_DECODER_STATE, _WHO, _WHAT_D,
-                     f"the widths {_abi.SS_DECODER_WIDTHS} are compiled into the kernels", CHECKPOINT_PREFIX, "decoder.")
-
-
-class SingleStageEncoder:
+class SingleStageEncoder(BatchNormEncoder):
     """AutoencoderMLP.encoder 768 -> 15 with its BatchNorm running statistics as a flat float32 array on `device`."""
 
-    def __init__(self, device, state=None, eps: float = BN_EPS):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SingleStageEncoder: a GPU device is required (there is no torch fallback)")
-        self.flat = torch.zeros(N_ENCODER, dtype=torch.float32, device=self.device)
-        self.eps = float(eps)
-        self._out = {}
-        if state is not None:
-            self.load_state_dict(state, eps)
-
-    @property
-    def views(self):
-        return encoder_views(self.flat)
-
-    def load_state_dict(self, state, eps: float = BN_EPS):
-        """eps: the BatchNorm1d layers' eps (a module attribute, not part of a state dict)."""
-        if not float(eps) > 0.0:
-            raise RuntimeError(f"{_WHO}: eps must be positive, got {eps!r}")
-        load_encoder_state(self.flat, state)
-        self.eps = float(eps)
-
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self.views.items())
+    TABLE, WIDTHS, PARAMS = _abi.SS_ENCODER_STATE, _abi.SS_ENCODER_WIDTHS, _abi.OlsrSsEncoderParams
+    WHO = "lang_single_stage"
+    HINT = f"the widths {WIDTHS} are compiled into the kernel"
 
     def encode(self, features, layout: str = "channels", out=None):
         """features [N,768], [768,h,w], [1,768,h,w] or [B,768,h,w] (read in place, one launch per item) -> unit codes [15,N]
@@ -93,17 +44,11 @@ class SingleStageEncoder:
         item = (CODE_DIM, N) if code_layout == _abi.LANG_AE_CODES_CHANNELS else (N, CODE_DIM)
         shape = item if B == 1 else (B,) + item
         if out is None:
-            out = self._out.get(layout)
-            if out is None or tuple(out.shape) != shape:
-                out = self._out[layout] = torch.empty(shape, dtype=torch.float32, device=self.device)
-        elif (not isinstance(out, torch.Tensor) or out.device != self.device or out.dtype != torch.float32
-              or tuple(out.shape) != shape or not out.is_contiguous()):
-            raise RuntimeError(f"encode: out must be a contiguous float32 {list(shape)} tensor on {self.device}")
-        p = _abi.OlsrSsEncoderParams(n_widths=len(_abi.SS_ENCODER_WIDTHS), in_layout=lay, code_layout=code_layout,
-                                     plane_stride=stride, bn_eps=self.eps)
-        for k, v in enumerate(_abi.SS_ENCODER_WIDTHS):
-            p.widths[k] = v
-        stream = C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            out = self._out.get(layout, shape)
+        else:
+            self._out.check_out(f"encode: out must be a contiguous float32 {list(shape)} tensor", out, shape)
+        p = self._params(lay, code_layout, stride)
+        stream = stream_ptr(self.device)
         per = N * CODE_DIM * 4
         with torch.cuda.device(self.device):
             for b, ptr in enumerate(ptrs):
@@ -111,26 +56,35 @@ class SingleStageEncoder:
         return out
 
 
-class SingleStageDecoder:
+class SingleStageDecoder(FlatNet):
     """AutoencoderMLP.decoder 15 -> 24 -> 48 -> 96 -> 192 -> 384 -> 384 -> 768 as a flat float32 array on `device`."""
 
-    def __init__(self, device, state=None):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("SingleStageDecoder: a GPU device is required (there is no torch fallback)")
-        self.flat = torch.zeros(N_DECODER, dtype=torch.float32, device=self.device)
-        if state is not None:
-            self.load_state_dict(state)
+    TABLE, WHO, WHAT = _abi.SS_DECODER_STATE, "lang_single_stage", ("flat decoder array", "decoder state")
+    HINT = f"the widths {_abi.SS_DECODER_WIDTHS} are compiled into the kernels"
+    PREFIX, KEEP = CHECKPOINT_PREFIX, "decoder."
 
-    @property
-    def views(self):
-        return decoder_views(self.flat)
 
-    def load_state_dict(self, state):
-        load_decoder_state(self.flat, state)
+def encoder_views(flat):
+    """name -> view of a flat [396927] tensor in the shapes of the single-stage AutoencoderMLP.encoder, in state_dict order."""
+    return SingleStageEncoder.views_of(flat)
 
-    def state_dict(self):
-        return OrderedDict((k, v.clone()) for k, v in self.views.items())
+
+def decoder_views(flat):
+    """name -> view of a flat [542544] tensor in the shapes of the single-stage AutoencoderMLP.decoder, in state_dict order."""
+    return SingleStageDecoder.views_of(flat)
+
+
+def load_encoder_state(flat, state):
+    """Copies the encoder of a single-stage AutoencoderMLP into a flat [396927] tensor.  `state` is a Lightning checkpoint
+    ({"state_dict": {"model.encoder.0.weight": ...}}), its state_dict, or a plain AutoencoderMLP state dict; decoder entries
+    and num_batches_tracked are ignored, the encoder's names and shapes must be the module's."""
+    SingleStageEncoder.load_into(flat, state)
+
+
+def load_decoder_state(flat, state):
+    """Copies the decoder of a single-stage AutoencoderMLP into a flat [542544] tensor; `state` as load_encoder_state takes it,
+    encoder and BatchNorm entries are ignored."""
+    SingleStageDecoder.load_into(flat, state)
 
 
 class SingleStageQuery(LanguageQuery):
@@ -146,18 +100,15 @@ class SingleStageQuery(LanguageQuery):
         self._pos = self._neg = None
         self._labels = torch.zeros(0, FEATURE_DIM, dtype=torch.float32, device=self.device)
         self._phrases = None
-        self._out = {}
+        self._out, self._scratch = Outputs(self.device), None
 
     def _sims(self, p, codes):
         # p carries the two-stage width list, which stage B validates; stage A takes the same sizes under its own list
-        ps = _abi.OlsrLangQueryParams.from_buffer_copy(p)
-        ps.n_widths = len(_abi.SS_DECODER_WIDTHS)
-        for k, v in enumerate(_abi.SS_DECODER_WIDTHS):
-            ps.widths[k] = v
-        sims = self._buffer("sims", (p.K, p.dec_height, p.dec_width))
+        ps = _abi.set_widths(_abi.OlsrLangQueryParams.from_buffer_copy(p), _abi.SS_DECODER_WIDTHS)
+        sims = self._out.get("sims", (p.K, p.dec_height, p.dec_width))
         with torch.cuda.device(self.device):
             check(lib().olsr_ss_query_sims(C.byref(ps), codes.data_ptr(), self.decoder.flat.data_ptr(), self._phrases.data_ptr(),
-                                           sims.data_ptr(), self._stream()))
+                                           sims.data_ptr(), stream_ptr(self.device)))
         return sims
 
 

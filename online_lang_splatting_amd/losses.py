@@ -11,6 +11,7 @@ import ctypes as C
 import torch
 
 from . import _abi
+from ._host import ptr, stream_ptr
 from ._lib import check, lib
 
 
@@ -98,12 +99,11 @@ def mapping_loss(image, depth, language, gt_image, gt_depth, gt_language=None, e
                              else _exposure_slot("mapping_loss", dL_dexposure_out, dev)))
     L = lib()
     scratch = torch.empty(L.olsr_mapping_loss_scratch_bytes(W, H), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
     with torch.cuda.device(dev):
         check(L.olsr_mapping_loss(C.byref(p), ptr(image), ptr(depth), ptr(language), ptr(gt_image), ptr(gt_depth),
                                   ptr(gt_language), ptr(exposure), ptr(out["dL_dimage"]), ptr(out["dL_ddepth"]),
                                   ptr(out["dL_dlanguage"]), ptr(out["loss"]), ptr(out["dL_dexposure"]),
-                                  scratch.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                  scratch.data_ptr(), stream_ptr(dev)))
     return out
 
 
@@ -136,12 +136,11 @@ def tracking_loss(image, depth, opacity, gt_image, gt_depth, grad_mask=None, exp
                dL_dexposure=torch.empty(2, **f32))
     L = lib()
     scratch = torch.empty(L.olsr_mapping_loss_scratch_bytes(W, H), dtype=torch.uint8, device=dev)
-    ptr = lambda t: t.data_ptr() if t is not None and t.numel() > 0 else None
     with torch.cuda.device(dev):
         check(L.olsr_tracking_loss(C.byref(p), ptr(image), ptr(depth), ptr(opacity), ptr(gt_image), ptr(gt_depth), ptr(gm),
                                    ptr(exposure), ptr(out["dL_dimage"]), ptr(out["dL_ddepth"]), ptr(out["loss"]),
                                    ptr(out["dL_dexposure"]), scratch.data_ptr(),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                   stream_ptr(dev)))
     return out
 
 
@@ -172,7 +171,7 @@ def refinement_loss(image, gt_image, *, lambda_dssim=0.2, want_grad=True, buffer
     with torch.cuda.device(dev):
         check(L.olsr_refinement_loss(W, H, float(lambda_dssim), image.data_ptr(), gt_image.data_ptr(),
                                      out["dL_dimage"].data_ptr() if want_grad else None, out["loss"].data_ptr(),
-                                     scratch.data_ptr(), C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                     scratch.data_ptr(), stream_ptr(dev)))
     return out
 
 
@@ -193,7 +192,7 @@ def isotropic_loss(scales, activations=0, weight=10.0, want_grad=False):
     with torch.cuda.device(dev):
         check(L.olsr_isotropic_reg(P, scales.data_ptr() if P else None, int(activations), float(weight),
                                    grad.data_ptr() if want_grad and P else None, loss.data_ptr(), scratch.data_ptr(),
-                                   C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+                                   stream_ptr(dev)))
     return (loss, grad) if want_grad else loss
 
 

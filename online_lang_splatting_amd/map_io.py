@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._host import stream_ptr
 from ._lib import check, lib
 
 FLOAT_TYPES = ("float", "float32")
@@ -170,7 +171,7 @@ def pack_rows(gmap) -> torch.Tensor:
     width = ply_width(gmap.M, gmap.F)
     rows = torch.empty(gmap.P, width, dtype=torch.float32, device=gmap.device)
     src = gmap._struct(gmap._bufs[gmap._front])
-    check(lib().olsr_map_ply_pack(gmap.P, gmap.M, gmap.F, C.byref(src), rows.data_ptr() if gmap.P else None, gmap._stream()))
+    check(lib().olsr_map_ply_pack(gmap.P, gmap.M, gmap.F, C.byref(src), rows.data_ptr() if gmap.P else None, stream_ptr(gmap.device)))
     return rows
 
 
@@ -242,7 +243,7 @@ def load_ply(path: str, lrs: Dict[str, float], device, F: Optional[int] = None, 
         rows = host.to(dev, non_blocking=True)
         table = (C.c_int32 * len(col))(*col)
         dst = gmap._struct(gmap._bufs[gmap._front])
-        check(lib().olsr_map_ply_unpack(P, M, F, n_cols, table, rows.data_ptr(), C.byref(dst), gmap._stream()))
+        check(lib().olsr_map_ply_unpack(P, M, F, n_cols, table, rows.data_ptr(), C.byref(dst), stream_ptr(gmap.device)))
         torch.cuda.current_stream(dev).synchronize()   # `host` and `rows` may go once the copy and the launch have run
     return gmap
 

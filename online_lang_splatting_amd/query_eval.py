@@ -12,28 +12,15 @@ One head only (the online pipeline has one level).  The annotated masks are take
 cv2.resize of the annotation (:157) stays with the caller.  The colour maps and every file the reference writes are not part
 of this.  GPU only; there is no torch fallback.
 """
-import ctypes as C
 import math
 
 import numpy as np
 import torch
 
 from . import _abi
+from ._host import scratch_for, stream_ptr
 from ._lib import check, lib
 from .lang_query import LanguageQuery
-
-_scratch = {}   # (device, kind) -> uint8 tensor, grown on demand and reused
-
-
-def _scratch_for(device, kind, nbytes):
-    buf = _scratch.get((device, kind))
-    if buf is None or buf.numel() < nbytes:
-        buf = _scratch[(device, kind)] = torch.empty(nbytes, dtype=torch.uint8, device=device)
-    return buf
-
-
-def _stream(device):
-    return C.c_void_p(torch.cuda.current_stream(device).cuda_stream)
 
 
 def _planes(who, name, t, dtype, shape=None, device=None):
@@ -63,7 +50,7 @@ def smooth_masks(mask):
     out = torch.empty_like(m)
     P, H, W = m.shape
     with torch.cuda.device(m.device):
-        check(lib().olsr_mask_smooth(P, H, W, m.data_ptr(), out.data_ptr(), _stream(m.device)))
+        check(lib().olsr_mask_smooth(P, H, W, m.data_ptr(), out.data_ptr(), stream_ptr(m.device)))
     return out if mask.dim() == 3 else out[0]
 
 
@@ -129,13 +116,13 @@ class QueryEvaluator:
         boxes = boxes.detach().contiguous()
         off = _box_offsets(who, box_offsets, P, boxes.shape[0])
         L = lib()
-        scratch = _scratch_for(self.device, "query_eval", L.olsr_query_eval_scratch_bytes(P, H, W))
+        scratch = scratch_for(self.device, "query_eval", L.olsr_query_eval_scratch_bytes(P, H, W))
         result = torch.empty((P, 4), dtype=torch.int32, device=self.device)
         mask_smoothed = torch.empty_like(mask)
         with torch.cuda.device(self.device):
             check(L.olsr_query_eval(P, H, W, mask.data_ptr(), smoothed.data_ptr(), score.detach().contiguous().data_ptr(),
                                     gt.data_ptr(), boxes.data_ptr() if boxes.numel() else None, off.ctypes.data,
-                                    result.data_ptr(), mask_smoothed.data_ptr(), scratch.data_ptr(), _stream(self.device)))
+                                    result.data_ptr(), mask_smoothed.data_ptr(), scratch.data_ptr(), stream_ptr(self.device)))
         host = result.cpu().numpy().astype(np.int64)
         inter, union, n_max, hit = (host[:, k] for k in range(4))
         with np.errstate(divide="ignore", invalid="ignore"):
@@ -175,10 +162,10 @@ def psnr_sums(image, gt):
     dev = image.device
     L = lib()
     out = torch.empty(2, dtype=torch.float64, device=dev)
-    scratch = _scratch_for(dev, "psnr", L.olsr_image_psnr_scratch_bytes())
+    scratch = scratch_for(dev, "psnr", L.olsr_image_psnr_scratch_bytes())
     Cn, H, W = image.shape
     with torch.cuda.device(dev):
-        check(L.olsr_image_psnr(Cn, H, W, image.data_ptr(), gt.data_ptr(), out.data_ptr(), scratch.data_ptr(), _stream(dev)))
+        check(L.olsr_image_psnr(Cn, H, W, image.data_ptr(), gt.data_ptr(), out.data_ptr(), scratch.data_ptr(), stream_ptr(dev)))
     return out
 
 

@@ -27,6 +27,8 @@ import os
 
 import torch
 
+from ._host import stream_ptr
+
 NCCL_UNIQUE_ID_BYTES = 128
 _DTYPES = {torch.int8: 0, torch.uint8: 1, torch.int32: 2, torch.int64: 4, torch.float16: 6, torch.float32: 7,
            torch.float64: 8}
@@ -102,14 +104,12 @@ class DirectComm:
             _check(L.ncclCommInitRank(C.byref(comm), world, uid, rank), "ncclCommInitRank")
         return cls(comm, rank, world, device)
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def all_reduce(self, t, op="sum"):
         """in place"""
         assert t.is_cuda and t.is_contiguous()
         _check(rccl().ncclAllReduce(t.data_ptr(), t.data_ptr(), t.numel(), _DTYPES[t.dtype], _OPS[op], self.comm,
-                                    self._stream()), "ncclAllReduce")
+                                    stream_ptr(self.device)), "ncclAllReduce")
 
     def reduce_scatter(self, out, inp, op="sum"):
         """out (inp.numel() / world elements; may be a slice of inp: in place when it is rank r's chunk) = this rank's chunk
@@ -117,14 +117,14 @@ class DirectComm:
         assert out.is_cuda and inp.is_cuda and out.is_contiguous() and inp.is_contiguous()
         assert out.numel() * self.world == inp.numel()
         _check(rccl().ncclReduceScatter(inp.data_ptr(), out.data_ptr(), out.numel(), _DTYPES[inp.dtype], _OPS[op], self.comm,
-                                        self._stream()), "ncclReduceScatter")
+                                        stream_ptr(self.device)), "ncclReduceScatter")
 
     def all_gather(self, out, inp):
         """out (world x inp.numel()) = the ranks' inp in rank order (inp may be rank r's chunk of out: in place)"""
         assert out.is_cuda and inp.is_cuda and out.is_contiguous() and inp.is_contiguous()
         assert inp.numel() * self.world == out.numel()
         _check(rccl().ncclAllGather(inp.data_ptr(), out.data_ptr(), inp.numel(), _DTYPES[inp.dtype], self.comm,
-                                    self._stream()), "ncclAllGather")
+                                    stream_ptr(self.device)), "ncclAllGather")
 
     def destroy(self):
         if self.comm:

@@ -1,10 +1,9 @@
 """Host side of olsr_knn_mean_dist2 (include/olsr.h): drop-in for simple_knn._C.distCUDA2
 (/root/reference/submodules/simple-knn/spatial.cu:15-26), the reference's second native dependency
 (Gaussian scale initialisation, gaussian_splatting/scene/gaussian_model.py:256-263).  GPU only."""
-import ctypes as C
-
 import torch
 
+from ._host import stream_ptr
 from ._lib import check, lib
 
 
@@ -21,5 +20,5 @@ def distCUDA2(points: torch.Tensor) -> torch.Tensor:
     scratch = torch.empty(L.olsr_knn_scratch_bytes(P), dtype=torch.uint8, device=pts.device)
     with torch.cuda.device(pts.device):
         check(L.olsr_knn_mean_dist2(P, pts.data_ptr(), out.data_ptr(), scratch.data_ptr(),
-                                    C.c_void_p(torch.cuda.current_stream(pts.device).cuda_stream)))
+                                    stream_ptr(pts.device)))
     return out

@@ -32,6 +32,7 @@ from typing import Callable, Dict, Optional, Sequence
 import torch
 
 from . import _abi, losses
+from ._host import stream_ptr
 from ._lib import OlsrError, check, lib
 from .frame_shard import FrameLanes, FusedAdam, GradLayout, RasterWorkspace
 
@@ -82,7 +83,7 @@ class PoseState:
                                          dL_dexposure.data_ptr() if dL_dexposure is not None else None,
                                          self.proj.data_ptr(), self.state.data_ptr(), self.status.data_ptr(),
                                          frame_status.data_ptr() if frame_status is not None else None,
-                                         C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                         stream_ptr(self.device)))
 
     def step(self, dL_dtau_sum: torch.Tensor, dL_dexposure: Optional[torch.Tensor] = None,
              frame_status: Optional[torch.Tensor] = None):
@@ -181,7 +182,7 @@ class KeyframeWindow:
                                           self.grad_exposure.data_ptr(), self.proj.data_ptr(), self.state.data_ptr(),
                                           self.status.data_ptr(),
                                           frame_status.data_ptr() if frame_status is not None else None,
-                                          C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)))
+                                          stream_ptr(self.device)))
 
     def step(self, frame_status: Optional[torch.Tensor] = None):
         """keyframe_optimizers.step() and update_pose of every view, from the gradients in grad_tau / grad_exposure.

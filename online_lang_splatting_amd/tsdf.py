@@ -16,6 +16,7 @@ import numpy as np
 import torch
 
 from . import _abi
+from ._host import require_gpu_device, stream_ptr
 from ._lib import check, lib
 
 COLOR_CONST = 256 * 256
@@ -58,9 +59,7 @@ class TSDFVolume:
     (fusion.py:30-42), except that the caller's vol_bnds array is not modified."""
 
     def __init__(self, vol_bnds, voxel_size, feature_dim=15, device="cuda"):
-        self.device = torch.device(device)
-        if self.device.type != "cuda":
-            raise RuntimeError("TSDFVolume: a GPU device is required (there is no torch fallback)")
+        self.device = require_gpu_device(device, "TSDFVolume")
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         bnds = np.array(vol_bnds, dtype=np.float64)
@@ -97,7 +96,7 @@ class TSDFVolume:
         self._scratch = None
         self._status = torch.zeros(4, dtype=torch.int32, device=self.device)
         with torch.cuda.device(self.device):
-            check(lib().olsr_tsdf_init(C.byref(self._vol), self._stream()))
+            check(lib().olsr_tsdf_init(C.byref(self._vol), stream_ptr(self.device)))
 
     # ---- what the reference's attributes hold ----------------------------------------------------------------------------
     @property
@@ -120,8 +119,6 @@ class TSDFVolume:
     def trunc_margin(self):
         return self._trunc_margin
 
-    def _stream(self):
-        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     # ---- one view ----------------------------------------------------------------------------------------------------------
     def _image(self, who, name, t, shapes):
@@ -188,7 +185,7 @@ class TSDFVolume:
             for s in range(0, len(views), _abi.TSDF_MAX_VIEWS):
                 chunk = views[s:s + _abi.TSDF_MAX_VIEWS]
                 arr = (_abi.OlsrTsdfView * len(chunk))(*[v for v, _ in chunk])
-                check(L.olsr_tsdf_integrate(C.byref(self._vol), len(chunk), arr, self._stream()))
+                check(L.olsr_tsdf_integrate(C.byref(self._vol), len(chunk), arr, stream_ptr(self.device)))
 
     def integrate(self, color_im, depth_im, cam_intr, cam_pose, obs_weight=1., opacity=None, min_opacity=0.0, layout=None):
         """Fuses one frame (the reference's signature).  color_im: [H,W,F] (numpy, as in the reference, or a device tensor) or
@@ -257,7 +254,7 @@ class TSDFVolume:
             self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             check(L.olsr_tsdf_surface_plan(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(),
-                                           self._status.data_ptr(), self._stream()))
+                                           self._status.data_ptr(), stream_ptr(self.device)))
             n = int(self._status[0].item())   # the extraction's one host synchronisation
             F = self.feature_dim
             points = torch.empty((n, 3), dtype=torch.float32, device=self.device)
@@ -265,7 +262,7 @@ class TSDFVolume:
             index = torch.empty((n,), dtype=torch.int32, device=self.device)
             check(L.olsr_tsdf_surface_emit(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(), n,
                                            points.data_ptr() if n else None, feats.data_ptr() if F > 0 and n else None,
-                                           index.data_ptr() if n else None, self._stream()))
+                                           index.data_ptr() if n else None, stream_ptr(self.device)))
         return points, feats, index
 
     def get_mesh(self, min_weight=0.0):
@@ -285,7 +282,7 @@ class TSDFVolume:
             self._scratch = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
         with torch.cuda.device(self.device):
             check(L.olsr_tsdf_mesh_plan(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(),
-                                        self._status.data_ptr(), self._stream()))
+                                        self._status.data_ptr(), stream_ptr(self.device)))
             n, m = self._status.tolist()[:2]   # the extraction's one host synchronisation: 16 bytes
             if m > (2 ** 31 - 1) // 3:
                 raise RuntimeError(f"get_mesh: {m} or more faces, 3 * faces must stay below 2^31")
@@ -298,7 +295,7 @@ class TSDFVolume:
             check(L.olsr_tsdf_mesh_emit(C.byref(self._vol), float(min_weight), self._scratch.data_ptr(), n, m,
                                         verts.data_ptr() if n else None, norms.data_ptr() if n else None,
                                         colors.data_ptr() if F > 0 and n else None, index.data_ptr() if n else None,
-                                        faces.data_ptr() if m else None, self._stream()))
+                                        faces.data_ptr() if m else None, stream_ptr(self.device)))
         return verts, faces, norms, colors, index
 
     def get_point_cloud(self, min_weight=0.0):

@@ -44,6 +44,7 @@ args = ap.parse_args()
 if not torch.cuda.is_available():
     raise SystemExit("bench_map_io.py needs the GPU: nothing here can be measured without one")
 from online_lang_splatting_amd import map_io  # noqa: E402
+from online_lang_splatting_amd._host import stream_ptr  # noqa: E402
 from online_lang_splatting_amd._lib import check, lib  # noqa: E402
 from online_lang_splatting_amd.gaussian_map import GaussianMap  # noqa: E402
 
@@ -170,7 +171,7 @@ for M in (1, 16):
     rows = map_io.pack_rows(gm)
     col = (C.c_int32 * width)(*range(width))
     dst = back._struct(back._bufs[back._front])
-    stream = back._stream()
+    stream = stream_ptr(back.device)
 
     def unpack():
         check(lib().olsr_map_ply_unpack(P, M, F, width, col, rows.data_ptr(), C.byref(dst), stream))

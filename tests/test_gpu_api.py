@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from online_lang_splatting_amd import _abi
+from online_lang_splatting_amd._host import stream_ptr
 from online_lang_splatting_amd.scene import make_config_scene, make_scene
 from parity_common import fwd_args, rel_err, run_backend
 
@@ -1087,7 +1088,7 @@ def test_per_view_tile_orders_of_the_dropin_entry_never_change_a_result(hip):
         check_(lib_.olsr_forward_async(C.byref(ws._scene), ws.geom.data_ptr(), ws.binning.data_ptr(), ws.capacity,
                                        ws.img.data_ptr(), o["color"].data_ptr(), o["language"].data_ptr(),
                                        o["depth"].data_ptr(), o["opacity"].data_ptr(), o["radii"].data_ptr(),
-                                       o["n_touched"].data_ptr(), ws.num_rendered.data_ptr(), None, ws._stream()))
+                                       o["n_touched"].data_ptr(), ws.num_rendered.data_ptr(), None, stream_ptr(ws.device)))
         ref.append({k: v.clone() for k, v in o.items()})
     order = list(range(20)) + [0, 1, 2, 19, 0, 10, 0]
     for v in order:

@@ -26,7 +26,7 @@ import torch
 import hr_net_ref as R
 import lang_codec_ref as RC
 import lang_encoder_ref as RE
-from test_gpu_lang_codec import _ratio_rule
+from test_gpu_lang_codec import _raises_exactly, _ratio_rule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -212,3 +212,23 @@ def test_keyframe_size(hip):
     assert torch.equal(net.forward(*x), out)
     xs, t64, t32 = _reference("12x12")
     _ratio_rule("12x12", net.forward(*_dev(xs)).cpu()[0], t64, t32)
+
+
+def test_validator_sentences(hip):
+    """The shared input and output checks' sentences, word for word, on the smallest inputs that reach them."""
+    from online_lang_splatting_amd.hr_net import HighResLanguageNet
+    net = HighResLanguageNet(DEV)   # (zero weights: nothing is launched)
+    fv, f3, f2 = (torch.rand(1, c, s, s, device=DEV) for c, s in ((768, 2), (384, 4), (192, 8)))
+    with _raises_exactly("HighResLanguageNet: a GPU device is required (there is no torch fallback)"):
+        HighResLanguageNet("cpu")
+    with _raises_exactly("hr_net.forward: fv must be a float32 tensor on the GPU"):
+        net.forward(fv.double(), f3, f2)
+    with _raises_exactly("hr_net.forward: f3 must be a float32 tensor on the GPU"):
+        net.forward(fv, f3.cpu(), f2)
+    with _raises_exactly("hr_net.forward: fv has shape (1, 767, 2, 2), expected [768,h,w] or [B,768,h,w]"):
+        net.forward(fv[:, :767].contiguous(), f3, f2)
+    with _raises_exactly("hr_net.forward: every channel plane of fv must be contiguous and the planes must not overlap "
+                         "(strides (3072, 4, 1, 2) for shape (1, 768, 2, 2))"):
+        net.forward(fv.transpose(2, 3), f3, f2)
+    with _raises_exactly("hr_net.forward: out must be a float32 [1, 768, 16, 16] tensor on cuda:0"):
+        net.forward(fv, f3, f2, out=torch.empty(1, 768, 8, 8, device=DEV))

@@ -327,3 +327,27 @@ def test_online_language_targets(hip):
     torch.cuda.synchronize()
     assert torch.isfinite(ms.last_loss).all() and float(ms.last_loss.reshape(-1, 4)[..., 3].abs().sum()) > 0   # a language term
     assert torch.isfinite(params["language"]).all() and not torch.equal(params["language"], start)
+
+
+def _raises_exactly(sentence):
+    """pytest.raises for a RuntimeError whose whole message is `sentence`."""
+    import re
+    return pytest.raises(RuntimeError, match="^" + re.escape(sentence) + "$")
+
+
+def test_validator_sentences(hip):
+    """The opening checks' sentences, word for word, on the smallest inputs that reach them."""
+    from online_lang_splatting_amd.lang_codec import OnlineLanguageCodec
+    c = _codec(R.initial_params(0))
+    with _raises_exactly("OnlineLanguageCodec: a GPU device is required (there is no torch fallback)"):
+        OnlineLanguageCodec("cpu")
+    with _raises_exactly("train_step: features must be a float32 tensor on the GPU"):
+        c.train_step(torch.rand(2, 32), 1e-4)
+    with _raises_exactly("encode: features must be a float32 tensor on the GPU"):
+        c.encode(torch.rand(2, 32, device=DEV).double())
+    with _raises_exactly("encode: features has shape (2, 31), expected [N,32] with N >= 1"):
+        c.encode(torch.rand(2, 31, device=DEV))
+    with _raises_exactly("decode: codes must be a float32 tensor on the GPU"):
+        c.decode(torch.rand(2, 15, device=DEV).double())
+    with _raises_exactly("decode: codes has shape (2, 31), expected [N,15] with N >= 1"):
+        c.decode(torch.rand(2, 31, device=DEV))

@@ -20,7 +20,7 @@ import torch
 import lang_codec_ref as RC
 import lang_encoder_ref as R
 import lang_query_ref as RQ
-from test_gpu_lang_codec import _ratio_rule
+from test_gpu_lang_codec import _raises_exactly, _ratio_rule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -276,3 +276,26 @@ def test_round_trip_through_the_query(hip):
     _ratio_rule("round trip: features32", f32.cpu(), R.encode(_state(), x, torch.float64), R.encode(_state(), x, torch.float32))
     _ratio_rule("round trip: codes", codes.cpu().t(), ref[0][0], ref[1][0])
     _ratio_rule("round trip: similarities", sims, ref[0][1], ref[1][1])
+
+
+def test_validator_sentences(hip):
+    """The shared input and output checks' sentences, word for word, on the smallest inputs that reach them."""
+    from online_lang_splatting_amd.lang_encoder import LanguageEncoder
+    enc, m = _encoder(), torch.rand(1, 768, 2, 2, device=DEV)
+    with _raises_exactly("LanguageEncoder: a GPU device is required (there is no torch fallback)"):
+        LanguageEncoder("cpu")
+    with _raises_exactly("encode: features must be a float32 tensor on the GPU"):
+        enc.encode(m.double())
+    with _raises_exactly("encode_codes: features must be a float32 tensor on the GPU"):
+        enc.encode_codes(m.cpu(), _codec())
+    with _raises_exactly("encode: features has shape (1, 767, 2, 2), expected [N,768], [768,h,w] or [B,768,h,w]"):
+        enc.encode(m[:, :767].contiguous())
+    with _raises_exactly("encode: every channel plane must be contiguous and the planes must not overlap "
+                         "(strides (3072, 4, 1, 2) for shape (1, 768, 2, 2))"):
+        enc.encode(m.transpose(2, 3))
+    with _raises_exactly("encode: features has shape (2, 31), expected [N,768] with N >= 1"):
+        enc.encode(torch.rand(2, 31, device=DEV))
+    with _raises_exactly("encode: [N,768] rows must be contiguous"):
+        enc.encode(torch.rand(768, 2, device=DEV).t())
+    with _raises_exactly("encode: out must be a contiguous float32 [4,32] tensor on cuda:0"):
+        enc.encode(m, out=torch.empty(3, 32, device=DEV))

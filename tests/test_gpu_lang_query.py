@@ -22,7 +22,7 @@ import torch
 
 import lang_codec_ref as RC
 import lang_query_ref as R
-from test_gpu_lang_codec import _ratio_rule, _scalar_rule
+from test_gpu_lang_codec import _raises_exactly, _ratio_rule, _scalar_rule
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -253,3 +253,23 @@ def test_query_on_a_rendered_language_map(hip):
     q, hip_out = _check("rendered 160 x 120", case)
     again = q.relevancy(lang)
     assert torch.equal(again["relevancy"].cpu(), hip_out["relevancy"])
+
+
+def test_validator_sentences(hip):
+    """The opening checks' sentences, word for word, on the smallest inputs that reach them."""
+    from online_lang_splatting_amd.lang_query import LanguageDecoder
+    case = R.make_case(40, 48, 0, 3, 0)
+    q = _query(case)
+    with _raises_exactly("LanguageDecoder: a GPU device is required (there is no torch fallback)"):
+        LanguageDecoder("cpu")
+    with _raises_exactly("relevancy: codes must be a float32 tensor on the GPU"):
+        q.relevancy(case["codes"])
+    with _raises_exactly("similarities: codes must be a float32 tensor on the GPU"):
+        q.similarities(case["codes"].to(DEV).double())
+    with _raises_exactly("set_phrases: pos_embeds must be a float32 tensor on the GPU"):
+        q.set_phrases(case["pos"], case["neg"].to(DEV))
+    with _raises_exactly("set_phrases: neg_embeds has shape (2, 31), expected [n,768] with n >= 1"):
+        q.set_phrases(case["pos"].to(DEV), torch.rand(2, 31, device=DEV))
+    with _raises_exactly("set_labels: label_embeds must be a float32 tensor on the GPU"):
+        q.set_labels(torch.zeros(2, 768, device=DEV).double())
+    assert q.counts == (3, 0, 4)
