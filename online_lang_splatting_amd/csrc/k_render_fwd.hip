@@ -16,6 +16,11 @@
 //     predicates are 64-bit wave masks in scalar registers (v_cmp + s_and, "any lane" = s_cmp, the
 //     accumulation under inverse_ballot), two list entries are evaluated per iteration with their
 //     geometry / power / exp on packed fp32, the accumulation is v_pk_mul_f32 + v_pk_fma_f32;
+//   * what a wave does BETWEEN its vector instructions is kept short: the pair loop has one exit, its
+//     trip test (a wave whose last pixel saturates takes the bound to 0 in the instruction that retires the pixel:
+//     retire_lanes); a wave's hit records of a batch stay in ONE vector register (lane l: entries 2 l and 2 l + 1, written by
+//     v_writelane_b32 from a scalar word per pair) and go to LDS once per batch, two 2-byte writes per lane, instead of a trip
+//     to lane 0 and an LDS write per blending entry;
 //   * n_touched is counted with per-wave popcounts (each wave owns 16 bits of the splat's LDS
 //     record: no LDS atomics) and ONE global integer atomic per (splat, batch);
 //   * tiles are launched heaviest-first inside each XCD's chunk when the caller hands back the
@@ -35,6 +40,43 @@
 namespace olsr {
 
 constexpr int FWD_BATCH = 128;
+
+// v with its lane j / 2 replaced by `value` (both wave-uniform: scalar registers).  One v_writelane_b32; the lane select goes
+// through m0 because a gfx9 VOP3 instruction reads one scalar register, m0 apart — and is formed there from the loop's own
+// index, so the loop carries no lane counter.
+__device__ __forceinline__ u32 write_lane_half(u32 v, u32 value, u32 j) {
+  // (readfirstlane of a uniform value is no instruction; it makes the "s" operands hold where the compiler keeps one in a VGPR)
+  value = (u32)__builtin_amdgcn_readfirstlane((int)value);
+  j = (u32)__builtin_amdgcn_readfirstlane((int)j);
+  asm("s_lshr_b32 m0, %2, 1\n\tv_writelane_b32 %0, %1, m0" : "+v"(v) : "s"(value), "s"(j) : "m0");
+  return v;
+}
+// {hi[15:0], lo[15:0]} in one scalar instruction
+__device__ __forceinline__ u32 pack_halves(u32 lo, u32 hi) {
+  u32 r;
+  asm("s_pack_ll_b32_b16 %0, %1, %2" : "=s"(r) : "s"(lo), "s"(hi));
+  return r;
+}
+// live &= ~term, and the trip bound goes to 0 when no lane is left: s_andn2_b64 leaves "not empty" in SCC, the select reads it
+__device__ __forceinline__ void retire_lanes(u64& live, int& lim, u64 term) {
+  asm("s_andn2_b64 %0, %0, %2\n\ts_cselect_b32 %1, %1, 0" : "+s"(live), "+s"(lim) : "s"(term) : "scc");
+}
+// 0 in a scalar register the compiler takes for a value of its own: ONE move at the head of the pair instead of a move on
+// every path that skips an entry
+__device__ __forceinline__ u32 scalar_zero() {
+  u32 r;
+  asm("s_mov_b32 %0, 0" : "=s"(r));
+  return r;
+}
+// (a & b) != 0 ? YES : no, on the scalar unit in two instructions: s_and_b64 leaves "not empty" in SCC and the select reads it
+// (from C++ the compiler spends a compare between the two).  YES is a literal, `no` a register or an inline constant.
+template <u32 YES>
+__device__ __forceinline__ u32 select_if_any(u64 a, u64 b, u32 no) {
+  u32 r;
+  u64 t;
+  asm("s_and_b64 %1, %2, %3\n\ts_cselect_b32 %0, %4, %5" : "=s"(r), "=&s"(t) : "s"(a), "s"(b), "i"(YES), "s"(no) : "scc");
+  return r;
+}
 #ifndef OLSR_FWD_WAVES
 #define OLSR_FWD_WAVES 7  // waves per SIMD the default accumulation is compiled for at F <= 16 (8: spills, measured slower)
 #endif
@@ -61,8 +103,16 @@ constexpr int FWD_BATCH = 128;
 //      the tile's partial loss sums are produced here instead of by a kernel that re-reads the images (csrc/olsr_loss_device.h).
 // CUT:  the per-tile depth cut-off bookkeeping (include/olsr.h) — its own instantiation: carried as a run-time test it cost the
 //       plain kernel 4 % (0.1588 -> 0.1647 ms at config 3, two more live scalars across the entry loop).
+
+// waves per SIMD an instantiation is compiled for, and the most it may be resident with.  The upper bound only binds the MFMA
+// variant at F = 0 / 3, whose registers would allow more since the hit records left the entry loop: it keeps the residency it
+// was measured with.
+constexpr int fwd_waves_min(int F, int ACC, int LOSS) {
+  return F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FWD_ACC2_WAVES : ((LOSS == 1 && F >= 15) ? OLSR_FWD_LOSS1_WAVES : OLSR_FWD_WAVES))) : (ACC == 1 ? 4 : 5);
+}
+constexpr int fwd_waves_max(int TILE, int F, int ACC) { return (ACC == 1 && F <= 3) ? ((TILE == 15 && F == 0) ? 7 : 6) : 8; }
 template <int TILE, int F, int ACC, int LOSS, bool CUT>
-__global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FWD_ACC2_WAVES : ((LOSS == 1 && F >= 15) ? OLSR_FWD_LOSS1_WAVES : OLSR_FWD_WAVES))) : (ACC == 1 ? 4 : 5))) void render_fwd_kernel(
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(fwd_waves_min(F, ACC, LOSS), fwd_waves_max(TILE, F, ACC)))) void render_fwd_kernel(
     const u32* ranges, u32* ranges_rw, const u32* __restrict__ inst_gid, const u32* __restrict__ src, int W, int H,
     int gx, int ntiles, const float* __restrict__ means2D, const float* __restrict__ conic_opacity,
     const float* __restrict__ depths, const float* __restrict__ colors, const float* __restrict__ lang,
@@ -124,14 +174,13 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
   const int px = bx * TILE + rank % TILE, py = by * TILE + rank / TILE;
   const bool inside = (rank < BS) && (px < W) && (py < H);
   const float pixfx = (float)px, pixfy = (float)py;
-  bool done = !inside;
   // backward wave (0 / 1) of this pixel among the survivors of the reference's tree, 2 = not a survivor
   int cls = 2;
   if constexpr (TILE == 15) {
     if (rank < BS && ref15_survives(rank)) cls = ref15_packed_of_rank(rank) >> 6;
   }
   const u64 cls_m0 = ballot(cls == 0), cls_m1 = ballot(cls == 1);  // wave-uniform lane masks (scalar registers)
-  u64 done_m = ballot(done);  // lanes that are outside the image or saturated
+  u64 live_m = ballot(inside);  // lanes inside the image and not yet saturated (the loop retires them: retire_lanes)
   const bool lane0 = (tid & 63) == 0;
   if (tid == 0) {
     s_work = 0;
@@ -186,7 +235,7 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
 
   for (int base = 0; base < n; base += B) {
     // also the barrier that separates the previous batch's flush from this batch's staging
-    if (__syncthreads_and(done_m == ~0ull)) break;
+    if (__syncthreads_and(live_m == 0ull)) break;
     const int cnt = min(B, n - base);
     if constexpr (CUT) last_base = base;
     {
@@ -202,7 +251,6 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
         if (tid < B) {
           s_id[e] = gid;
           s_src[e] = u;
-          s_hit[e] = make_uint2(0u, 0u);
           const float2 m = reinterpret_cast<const float2*>(means2D)[gid];
           const float4 c = reinterpret_cast<const float4*>(conic_opacity)[gid];
           // alpha = o * exp(power) can only reach 1/255 if power >= -ln(255 o).  Keep a margin far
@@ -232,37 +280,44 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
     }
     __syncthreads();
 
-    if (done_m != ~0ull) {
+    // this wave's hit records of the batch: lane l holds the record of entry 2 l in its low half and of entry 2 l + 1 in its
+    // high half — the two entries of pair l.  A wave blends an entry at most once, so the record of a pair is one scalar
+    // word written into its lane (v_writelane_b32) and the register goes to s_hit once, behind the entry loop: no trip to
+    // lane 0 and no LDS write per blending entry.  Zeroed here, per batch: a record of the previous batch must not survive.
+    u32 hrec = 0u;
+    if (live_m != 0ull) {
       // The lane predicates of CR/forward.cu:449-476 live in scalar registers as 64-bit wave masks: every test
       // is one v_cmp whose result is combined with s_and / s_andn2, "any lane" is an s_cmp, and only the
       // accumulation runs under a lane mask (inverse_ballot -> exec).  Two list entries are evaluated per
       // iteration: their geometry, power and exp run on packed fp32 (each component is the IEEE operation of the
       // scalar code, so the bits are unchanged); the compositing itself stays strictly sequential.
       const v2f pixx2 = {pixfx, pixfx}, pixy2 = {pixfy, pixfy};
-      for (int j = 0; j < cnt; j += 2) {
+      int lim = cnt;  // (wave-uniform) the trip bound: 0 once the wave's last pixel has saturated
+      for (int j = 0; j < lim; j += 2) {
         const float4 q0 = s_pair[(j >> 1) * 4 + 0], q1 = s_pair[(j >> 1) * 4 + 1], q2 = s_pair[(j >> 1) * 4 + 2];
         const v2f dx = v2f{q0.x, q0.y} - pixx2, dy = v2f{q0.z, q0.w} - pixy2;
         const v2f ca = {q1.z, q1.w}, cb = {q2.x, q2.y}, cc = {q2.z, q2.w};
         const v2f power = v2f{-0.5f, -0.5f} * (ca * dx * dx + cc * dy * dy) - cb * dx * dy;
-        u64 live = ~done_m;
         // wave-level early-out: no live pixel of this slot can reach the alpha floor of either entry
-        const u64 reach0 = ballot(!(power.x < q1.x)) & live, reach1 = ballot(!(power.y < q1.y)) & live;
+        const u64 reach0 = ballot(!(power.x < q1.x)) & live_m, reach1 = ballot(!(power.y < q1.y)) & live_m;
         if ((reach0 | reach1) == 0ull) continue;
         const float2 op = *reinterpret_cast<const float2*>(&s_pair[(j >> 1) * 4 + 3]);
         const v2f G = pinned_expf2(power);
         const float alpha0 = fminf_ref(0.99f, op.x * G.x), alpha1 = fminf_ref(0.99f, op.y * G.y);
+        u32 rec2 = scalar_zero();  // (wave-uniform) the pair's two records, entry j low, entry j + 1 high
 #pragma unroll
         for (int h = 0; h < 2; ++h) {
           const u64 reach = h ? reach1 : reach0;
           if (reach == 0ull) continue;
           const float pw = h ? power.y : power.x, alpha = h ? alpha1 : alpha0;
           const int jj = j + h;
-          live = ~done_m;
           const float test_T = T * (1 - alpha);
-          const u64 ok_m = ballot(!(pw > 0.0f)) & ballot(!(alpha < 1.0f / 255.0f)) & live;
+          const u64 ok_m = ballot(!(pw > 0.0f)) & ballot(!(alpha < 1.0f / 255.0f)) & live_m;
           const u64 term_m = ok_m & ballot(test_T < 0.0001f);
           const u64 contrib_m = ok_m & ~term_m;
-          done_m |= term_m;
+          // ONE loop exit, the trip test: the wave whose last pixel saturates here takes the bound down (a `break` behind the
+          // pair, and the `continue` above as a jump, were ~19 scalar instructions and four branches of exit encoding per pair)
+          retire_lanes(live_m, lim, term_m);
           if (MFMA && contrib_m != 0ull) {
             const bool cl = __builtin_amdgcn_inverse_ballot_w64(contrib_m);
             const float wv = cl ? alpha * T : 0.0f;
@@ -297,24 +352,34 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
             }
             const u32 tc = (u32)__popcll(contrib_m & ballot(test_T > 0.5f));
             u32 rec = 0x8000u | tc;
-            if constexpr (TILE == 15) rec |= ((contrib_m & cls_m0) ? 0x100u : 0u) | ((contrib_m & cls_m1) ? 0x200u : 0u);
-            if (lane0) reinterpret_cast<uint16_t*>(s_hit)[4 * jj + w] = (uint16_t)rec;
+            if constexpr (TILE == 15)
+              rec = select_if_any<0x8100u>(contrib_m, cls_m0, 0x8000u) | select_if_any<0x200u>(contrib_m, cls_m1, 0u) | tc;
+            rec2 = h ? pack_halves(rec2, rec) : rec;
           }
           // (no exit between the two entries of a pair: once every pixel of the wave is saturated `live` is empty, the second
-          //  entry blends nothing, records nothing and changes no T — and the loop leaves below.  The break that stood here
+          //  entry blends nothing, records nothing and changes no T — and the trip test ends the loop.  The break that stood here
           //  cost every blending entry ~12 scalar instructions of the structuriser's exit encoding.  The cut-off variant needs
-          //  the entry at which the wave saturated.)
+          //  the entry at which the wave saturated: the first one behind which no pixel is live.)
           if constexpr (CUT) {
-            if (done_m == ~0ull) {
-              my_stop = base + jj;
-              break;
-            }
+            if (live_m == 0ull && my_stop < 0) my_stop = base + jj;
           }
         }
-        if (done_m == ~0ull) break;
+        hrec = write_lane_half(hrec, rec2, (u32)j);
       }
       // the entries still waiting read their features from THIS batch's LDS rows: flush before it is restaged
       if (MFMA && gfill != 0) mfma_flush();
+    }
+    {
+      // the batch's records go to s_hit, 16 bits per (entry, wave): two 2-byte LDS writes per lane and batch.  Every wave writes
+      // all 128 of its records, also a saturated wave its zeros: s_hit needs no clearing when a batch is staged.
+      // (the address is formed here, per batch, from a copy of tid the compiler cannot see through: hoisted out of the batch
+      //  loop it would hold a vector register across the entry loop, where the seven-wave instantiations have none to spare:
+      //  the 16 x 16 cut-off variant at F = 16 spilled two words)
+      int t = tid;
+      asm volatile("" : "+v"(t));
+      uint16_t* h16 = reinterpret_cast<uint16_t*>(s_hit) + 8 * (t & 63) + (t >> 6);
+      h16[0] = (uint16_t)hrec;
+      h16[4] = (uint16_t)(hrec >> 16);
     }
     __syncthreads();
     if (tid < B) {  // (waves 0 and 1, whole: the ballots below need every lane)
@@ -350,7 +415,7 @@ __global__ __launch_bounds__(256, (F <= 16 ? (ACC == 1 ? 5 : (ACC == 2 ? OLSR_FW
   // staged last, still in LDS) + 0.01, +infinity if a wave never saturated; the tile-order kernel dilates them (k_binning.hip).
   if constexpr (CUT) {
     if (lane0) {
-      if (done_m != ~0ull) atomicAdd(&s_undone, 1);
+      if (live_m != 0ull) atomicAdd(&s_undone, 1);
       else if (my_stop >= 0) atomicMax(&s_stop, my_stop);
     }
     __syncthreads();
