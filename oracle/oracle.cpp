@@ -4,12 +4,12 @@
 // library; the product (online_lang_splatting_amd) never does.
 //
 // PARITY UNPINNED by the reference's own tests: rpng/online_lang_splatting ships no
-// tests, golden vectors or fixtures for the rasterizer and no CPU path, and its CUDA
-// sources cannot be built in this image (no nvcc / cub / cooperative_groups; SURVEY.md
-// §8(c)).  What IS pinned: SH evaluation, projection-matrix and SE(3) conventions
+// tests, golden vectors or fixtures for the rasterizer and no CPU path.  What pins this file: the reference's own
+// kernel sources compiled as host C++ over an execution model (ref_shim/, ref_build.py: every stage of the forward and
+// the backward equal bit for bit, tests/test_ref_build_cpu.py), SH evaluation, projection-matrix and SE(3) conventions
 // against fixtures generated from the reference's importable Python helpers
 // (tests/golden/), and the `exact` backward against PyTorch autograd on an independent
-// dense formulation (tests/test_oracle_autograd.py).
+// dense formulation (tests/test_oracle_autograd.py).  DESIGN.md section 4 lists what remains unpinned.
 //
 // Every function cites the reference lines it restates:
 //   CR  = /root/reference/submodules/diff-gaussian-rasterization/cuda_rasterizer
@@ -34,6 +34,7 @@
 #include <omp.h>
 
 #include "../include/olsr.h"
+#include "pinned_exp.h"
 
 namespace {
 
@@ -91,40 +92,14 @@ const float SH_C2[] = {1.0925484305920792f, -1.0925484305920792f, 0.315391565252
 const float SH_C3[] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f,
                        -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
 
-// float -> int conversion with the GPU's saturating semantics (cvt.rzi.s32.f32 on the
-// reference's hardware, v_cvt_i32_f32 on gfx950): truncate toward zero, clamp, NaN -> 0.
-static inline int f2i_sat(float v) {
-  if (v != v) return 0;
-  if (v >= 2147483648.0f) return 2147483647;
-  if (v <= -2147483648.0f) return (int)0x80000000;
-  return (int)v;
-}
-
-// The pinned exp (see header).  Valid for x <= 88; x is clamped below at -87 (the result,
-// ~1.6e-38, times any opacity <= 1 is far under the 1/255 alpha floor).
-static inline float bits2f(uint32_t u) { float f; std::memcpy(&f, &u, 4); return f; }
-static inline uint32_t f2bits(float f) { uint32_t u; std::memcpy(&u, &f, 4); return u; }
+// f2i_sat (the GPU's saturating float -> int conversion), bits2f / f2bits and the pinned exp itself live in pinned_exp.h,
+// which the host build of the reference's own kernels (ref_shim/) includes too: both resolve `exp(power)` to one routine.
 static float oracle_expf(float x) {
 #ifdef ORACLE_LIBM_EXP
   // sensitivity variant (scripts/cuda_sensitivity.py): the host libm instead of the pinned routine
   return std::exp(x);
 #endif
-  x = (x < -87.0f) ? -87.0f : x;
-  x = (x > 88.0f) ? 88.0f : x;
-  float n = std::nearbyintf(x * 1.44269504088896341f);  // round-half-even
-  float r = __builtin_fmaf(n, -0.693359375f, x);
-  r = __builtin_fmaf(n, 2.12194440e-4f, r);
-  float p = 1.9875691500e-4f;
-  p = __builtin_fmaf(p, r, 1.3981999507e-3f);
-  p = __builtin_fmaf(p, r, 8.3334519073e-3f);
-  p = __builtin_fmaf(p, r, 4.1665795894e-2f);
-  p = __builtin_fmaf(p, r, 1.6666665459e-1f);
-  p = __builtin_fmaf(p, r, 5.0000001201e-1f);
-  float e = __builtin_fmaf(p, r * r, r) + 1.0f;
-  // (n is NaN for a NaN argument: `(int)n` would be undefined.  f2i_sat is the device's v_cvt_i32_f32, 0 for a NaN, and
-  //  e * 2^0 is still NaN; for every other argument n is an integer in [-126, 127] and the conversion is exact)
-  int ni = f2i_sat(n);
-  return e * bits2f((uint32_t)(ni + 127) << 23);
+  return pinned_expf(x);
 }
 
 // CR/auxiliary.h:41-44 — evaluated in double (the literals are double), then narrowed.
@@ -161,6 +136,9 @@ struct State {
   std::vector<uint32_t> ranges;  // [tiles][2]
   std::vector<float> final_T;
   std::vector<uint32_t> n_contrib;
+  // per pixel, the 1-based list position of the entry at which the pixel saturated (test_T < 1e-4: `done`), 0 if it walked
+  // its list to the end.  Inspection only (tests/ref_scenes.py asserts its scenes' conditions on it); nothing reads it back.
+  std::vector<uint32_t> sat_pos;
   // backward internals (kept for inspection)
   std::vector<float> dL_dconic, dL_ddepths;
   // optional (oracle_set_record): per sorted list position, which thread ranks of its tile blended it (256 bits)
@@ -449,7 +427,7 @@ static void render_forward(const olsr_scene& s, State& st, float* out_color, flo
         const size_t pix_id = (size_t)W * py + px;
         const float pixfx = (float)px, pixfy = (float)py;
         float T = 1.0f;
-        uint32_t contributor = 0, last_contributor = 0;
+        uint32_t contributor = 0, last_contributor = 0, sat = 0;
         float C[3] = {0, 0, 0};
         std::fill(L.begin(), L.end(), 0.0f);
         float D = 0.0f;
@@ -464,13 +442,22 @@ static void render_forward(const olsr_scene& s, State& st, float* out_color, flo
           const float alpha = std::min(0.99f, co[3] * oracle_expf(power));
           if (alpha < 1.0f / 255.0f) continue;
           const float test_T = T * (1 - alpha);
-          if (test_T < 0.0001f) break;  // done = true
+          if (test_T < 0.0001f) { sat = contributor; break; }  // done = true
           // `C += f * alpha * T` (CR/forward.cu:479-484): the reference is built by nvcc with its default
           // --fmad=true, which contracts the last product into the sum, fma(f * alpha, T, C).  Written
           // out because this file is built with -ffp-contract=off.
+          // -DORACLE_PLAIN_ACCUM (liboracle_plain.so): a multiply and an add instead, which is what a build of the
+          // reference's source with contraction off performs; that variant exists so that the whole forward can be
+          // compared with such a build (oracle/ref_build.py) as an equality.  These three statements are its only difference.
+#ifdef ORACLE_PLAIN_ACCUM
+          for (int ch = 0; ch < 3; ch++) C[ch] += features[(size_t)id * 3 + ch] * alpha * T;
+          for (int ch = 0; ch < F; ch++) L[ch] += lang[(size_t)id * F + ch] * alpha * T;
+          D += st.depths[id] * alpha * T;
+#else
           for (int ch = 0; ch < 3; ch++) C[ch] = std::fmaf(features[(size_t)id * 3 + ch] * alpha, T, C[ch]);
           for (int ch = 0; ch < F; ch++) L[ch] = std::fmaf(lang[(size_t)id * F + ch] * alpha, T, L[ch]);
           D = std::fmaf(st.depths[id] * alpha, T, D);
+#endif
           if (g_record_contrib) {  // (each list position belongs to one tile, each tile to one OpenMP thread)
             const int rank = ty * tile + tx;
             st.contrib_mask[(size_t)k * 8 + (rank >> 5)] |= 1u << (rank & 31);
@@ -484,6 +471,7 @@ static void render_forward(const olsr_scene& s, State& st, float* out_color, flo
         }
         st.final_T[pix_id] = T;
         st.n_contrib[pix_id] = last_contributor;
+        st.sat_pos[pix_id] = sat;
         for (int ch = 0; ch < 3; ch++) out_color[ch * HW + pix_id] = C[ch] + T * s.background[ch];
         for (int ch = 0; ch < F; ch++) out_lang[ch * HW + pix_id] = L[ch];
         out_depth[pix_id] = D;
@@ -1044,6 +1032,7 @@ int oracle_forward(void* h, const olsr_scene* s, float* out_color, float* out_la
   st.ranges.assign((size_t)2 * st.gx * st.gy, 0);
   st.final_T.assign(N, 0.f);
   st.n_contrib.assign(N, 0);
+  st.sat_pos.assign(N, 0);
   std::fill(out_color, out_color + 3 * N, 0.f);  // torch::full(..., 0.0) DGR/rasterize_points.cu:170-175
   if (F > 0) std::fill(out_language, out_language + (size_t)F * N, 0.f);
   std::fill(out_depth, out_depth + N, 0.f);
@@ -1169,6 +1158,7 @@ int64_t oracle_get_field(void* h, const char* name, void* dst) {
   if (!std::strcmp(name, "ranges")) return cp(st.ranges.data(), st.ranges.size(), 4);
   if (!std::strcmp(name, "final_T")) return cp(st.final_T.data(), st.final_T.size(), 4);
   if (!std::strcmp(name, "n_contrib")) return cp(st.n_contrib.data(), st.n_contrib.size(), 4);
+  if (!std::strcmp(name, "sat_pos")) return cp(st.sat_pos.data(), st.sat_pos.size(), 4);
   if (!std::strcmp(name, "contrib_mask")) return cp(st.contrib_mask.data(), st.contrib_mask.size(), 4);
   return -1;
 }
@@ -1194,6 +1184,8 @@ const char* oracle_variant() {
   return "libm_exp";
 #elif defined(ORACLE_CONTRACT_FAST)
   return "contract_fast";
+#elif defined(ORACLE_PLAIN_ACCUM)
+  return "plain_accum";
 #else
   return "default";
 #endif

@@ -32,8 +32,9 @@ def build(force=False):
     so = os.path.join(_HERE, "liboracle.so")
     src = os.path.join(_HERE, "oracle.cpp")
     hdr = os.path.join(_HERE, "..", "include", "olsr.h")
+    exp_hdr = os.path.join(_HERE, "pinned_exp.h")
     stale = (not os.path.exists(so)) or any(
-        os.path.exists(p) and os.path.getmtime(p) > os.path.getmtime(so) for p in (src, hdr))
+        os.path.exists(p) and os.path.getmtime(p) > os.path.getmtime(so) for p in (src, hdr, exp_hdr))
     if force or stale:
         subprocess.check_call(["make", "-C", _HERE, "-s", "-B", "liboracle.so"])
     return so
@@ -44,9 +45,10 @@ _variant = "default"
 
 def use_variant(name):
     """Switch the library behind this module: "default" (the parity oracle), "libm_exp" or "contract_fast"
-    (sensitivity variants built by `make -C oracle variants`; scripts/cuda_sensitivity.py only)."""
+    (sensitivity variants built by `make -C oracle variants`; scripts/cuda_sensitivity.py only), or "plain_accum" (the
+    forward's accumulations as a multiply and an add: the comparison variant of tests/test_ref_build_cpu.py)."""
     global _lib, _variant
-    assert name in ("default", "libm_exp", "contract_fast"), name
+    assert name in ("default", "libm_exp", "contract_fast", "plain_accum"), name
     if name != _variant:
         _states.clear()
         _lib, _variant = None, name
@@ -58,7 +60,8 @@ def lib():
         so = build()
         if _variant != "default":
             subprocess.check_call(["make", "-C", _HERE, "-s", "variants"])
-            so = os.path.join(_HERE, {"libm_exp": "liboracle_libmexp.so", "contract_fast": "liboracle_contract.so"}[_variant])
+            so = os.path.join(_HERE, {"libm_exp": "liboracle_libmexp.so", "contract_fast": "liboracle_contract.so",
+                                     "plain_accum": "liboracle_plain.so"}[_variant])
         L = C.CDLL(so)
         L.oracle_set_record.argtypes = [C.c_int]
         L.oracle_variant.restype = C.c_char_p
@@ -191,7 +194,7 @@ def release(geomBuffer):
 
 _FIELD_DT = {"clamped": torch.uint8, "tiles_touched": torch.int32, "point_offsets": torch.int32,
              "point_list": torch.int32, "keys": torch.int64, "ranges": torch.int32, "n_contrib": torch.int32,
-             "contrib_mask": torch.int32}
+             "sat_pos": torch.int32, "contrib_mask": torch.int32}
 
 
 def get_field(geomBuffer, name):
