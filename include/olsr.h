@@ -103,6 +103,13 @@ typedef void *(*olsr_alloc_fn)(void *user, size_t nbytes);
  *       (DGR-D/cuda_rasterizer/forward.cu:391-431), so the caller that composes the two passes must know the radius of
  *       the set that covered none.  A backward must be given max(radii, 0). */
 #define OLSR_FLAG_SIGNED_EMPTY_RADII 1
+/*   OLSR_FLAG_ORACLE_KEEP_ZERO_DET  (forward; the CPU oracle only - the library rejects it as an unknown bit) a Gaussian
+ *       whose float32 2D covariance has determinant a c - b b == 0 is NOT dropped: it goes on with the conic 1 / 0 gives
+ *       (+inf, -+inf or NaN, +inf) and the radius its eigenvalues give.  DGR-D's preprocess does that to a covariance set
+ *       whenever the Gaussian's OTHER set has a non-zero determinant (DGR-D/cuda_rasterizer/forward.cu:356-366);
+ *       tests/dgrd_oracle.py composes the rule.  Thin needles close to the camera reach it: with a footprint variance of
+ *       1e7 px^2 and more, a c and b b round to the same float although 0.3 was added to the diagonal. */
+#define OLSR_FLAG_ORACLE_KEEP_ZERO_DET 0x100
 /*   OLSR_FLAG_FWD_ACCUM_MFMA  (forward) the per-pixel feature accumulation C += f alpha T of the forward composite — a dense
  *       [64 pixels x K entries] x [K x (4 + F) channels] contraction per wave — runs on the matrix cores
  *       (v_mfma_f32_16x16x4_f32: exact fp32, a k-ordered fma chain) instead of the vector ALU.  Every decision (alpha

@@ -17,6 +17,7 @@ ACT_OPACITY_SIGMOID = 1      # OLSR_ACT_*: the array holds the raw parameter, th
 ACT_SCALE_EXP = 2
 ACT_ROTATION_NORMALIZE = 4
 ACT_ALL = 7
+FLAG_ORACLE_KEEP_ZERO_DET = 0x100  # OLSR_FLAG_ORACLE_KEEP_ZERO_DET: oracle only; the library rejects it
 FLAG_SIGNED_EMPTY_RADII = 1  # OLSR_FLAG_SIGNED_EMPTY_RADII: radii = -radius for a bounding square that covers no tile
 FLAG_FWD_ACCUM_WEIGHT = 4    # OLSR_FLAG_FWD_ACCUM_WEIGHT: fma(alpha T, f, C) on the vector ALU (images to ~1e-7)
 FLAG_FRAMES_IN_FLIGHT = 8    # OLSR_FLAG_FRAMES_IN_FLIGHT: several frames in flight on several streams -> four-wave radix blocks

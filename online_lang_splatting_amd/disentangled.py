@@ -19,8 +19,15 @@ DGR-D/cuda_rasterizer/config.h:17-18):
             One coupling: preprocess returns early only if BOTH bounding squares cover no tile (forward.cu:391-397)
             and then writes both radii (:421-431), so a set whose square covers no tile still reports its radius when
             the other set is visible.  The passes run with OLSR_FLAG_SIGNED_EMPTY_RADII and `_merge_radii` applies
-            the rule.  (DGR-D also keeps going when exactly one determinant is zero, :375-378; a 2D covariance with
-            0.3 added to its diagonal has det >= 0.09, so that branch is not reachable with finite inputs.)
+            the rule.
+            KNOWN DIFFERENCE: DGR-D returns on a zero determinant only when BOTH sets' determinants are zero
+            (:356-366).  In float32 a 2D covariance with 0.3 added to its diagonal can still have a c - b b == 0: a
+            thin needle close to the camera, footprint variance of 1e7 px^2 and more.  With exactly one zero, DGR-D
+            lets that set go on with the conic 1 / 0 gives and a radius that covers the image, blends it with alpha
+            0.99 where its power is NaN, and its backward writes NaN for that Gaussian.  Each pass here drops such a
+            set (radius 0, no instance, finite gradients), because a pass cannot know the other set's determinant.
+            Scene `one_zero_det` of tests/dgrd_scenes.py shows it; tests/dgrd_oracle.py follows DGR-D there and is
+            held to DGR-D's own kernels on the CPU (tests/test_dgrd_ref_build_cpu.py); DESIGN.md section 9.
   backward  language_render_cuda (DGR-D/cuda_rasterizer/backward.cu:1052-1428): the colour loop is the RGB
             rasterizer's backward (skip-guarded recursions, 256-lane block sum); the language loop is the language
             rasterizer's loop with the colour / depth terms removed — the language recursion is not skip-guarded

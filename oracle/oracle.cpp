@@ -256,7 +256,9 @@ static void preprocess(const olsr_scene& s, State& st, int* radii_out) {
     cov2D_common(p_orig, focal_x, focal_y, s.tan_fovx, s.tan_fovy, cov3D, s.viewmatrix, ci);
     f3 cov = {ci.cov2D.c[0][0] + 0.3f, ci.cov2D.c[0][1], ci.cov2D.c[1][1] + 0.3f};
     float det = (cov.x * cov.z - cov.y * cov.y);
-    if (det == 0.0f) continue;
+    // (OLSR_FLAG_ORACLE_KEEP_ZERO_DET: DGR-D goes on when the Gaussian's other covariance set has a determinant,
+    // DGR-D/cuda_rasterizer/forward.cu:356-366; the conic is then what 1 / 0 gives)
+    if (det == 0.0f && !(s.flags & OLSR_FLAG_ORACLE_KEEP_ZERO_DET)) continue;
     float det_inv = 1.f / det;
     f3 conic = {cov.z * det_inv, -cov.y * det_inv, cov.x * det_inv};
     float mid = 0.5f * (cov.x + cov.z);
