@@ -17,6 +17,7 @@ from .lang_encoder import LanguageEncoder  # noqa: F401,E402  (the general encod
 from .lang_single_stage import (SingleStageDecoder, SingleStageEncoder,  # noqa: F401,E402  (single_stage_ae: True: one
                                 SingleStageQuery, SingleStageTargets)     # autoencoder 768 -> 15 -> 768, nothing online)
 from .hr_net import HighResLanguageNet  # noqa: F401,E402  (the high-resolution feature net ahead of that encoder)
+from .clip_trunk import ClipTrunk  # noqa: F401,E402  (the CLIP ConvNeXt image tower ahead of the HR net: a frame in, its maps out)
 from .tsdf import TSDFVolume  # noqa: F401,E402  (TSDF fusion of depth and language maps into a 3-D map)
 from .cloud_metrics import (chamfer_distance, chamfer_segments, earth_mover_distance,  # noqa: F401,E402  (the 3-D evaluation's
                             emd_segments, evaluate_classes)                            # Chamfer and earth mover's distances)
@@ -29,7 +30,7 @@ from .slam import OnlineSlam, ate_rmse, ate_statistics  # noqa: F401,E402  (the 
 from . import map_io  # noqa: F401,E402  (the map on disk: point_cloud.ply packed on the device, the resumable .npz)
 from .losses import isotropic_loss  # noqa: F401,E402  (the mapping loss's isotropic regulariser)
 
-__all__ = ["render", "OnlineSlam", "ate_rmse", "ate_statistics", "map_io", "ingest_frame", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "SingleStageEncoder", "SingleStageDecoder", "SingleStageQuery", "SingleStageTargets", "HighResLanguageNet", "TSDFVolume", "earth_mover_distance", "emd_segments",
+__all__ = ["render", "OnlineSlam", "ate_rmse", "ate_statistics", "map_io", "ingest_frame", "KeyframeWindow", "isotropic_loss", "seed_rows", "tracking_mask", "median_depth", "KeyframeSelector", "LanguageDecoder", "LanguageQuery", "LanguageEncoder", "SingleStageEncoder", "SingleStageDecoder", "SingleStageQuery", "SingleStageTargets", "HighResLanguageNet", "ClipTrunk", "TSDFVolume", "earth_mover_distance", "emd_segments",
            "chamfer_distance", "chamfer_segments", "evaluate_classes", "query_eval", "QueryEvaluator", "smooth_masks", "frame_metrics", "GaussianRasterizationSettings", "GaussianRasterizer", "LanguageGaussianRasterizer",
            "rasterize_gaussians", "rasterize_language_gaussians", "BWD_REFERENCE", "BWD_EXACT", "set_backward_mode",
            "set_tile", "BINNING_RECT", "BINNING_ELLIPSE", "set_binning"]

@@ -308,6 +308,54 @@ class OlsrHrNetParams(C.Structure):
         ("bn_eps", C.c_double), ("workspace_bytes", C.c_uint64)]
 
 
+# the CLIP ConvNeXt image tower (include/olsr_clip_trunk.h, OLSR_CLIP_TRUNK_*)
+CLIP_TRUNK_FUSED_MAX_C, CLIP_TRUNK_MAX_LAUNCHES, CLIP_TRUNK_MAX_DIM = 256, 128, 4096
+CLIP_TRUNK_DEPTHS, CLIP_TRUNK_DIMS, CLIP_TRUNK_EMBED = (3, 3, 27, 3), (192, 384, 768, 1536), 768   # convnext_large_d_320
+CLIP_PIXEL_MEAN = (122.7709383, 116.7460125, 104.09373615)   # language/sed/config.py:67-68
+CLIP_PIXEL_STD = (68.5005327, 66.6321579, 70.3231630)
+CLIP_LN_EPS = 1e-6
+
+
+class OlsrConvnextBlockParams(C.Structure):
+    """struct olsr_convnext_block_params, include/olsr_clip_trunk.h."""
+
+    _fields_ = [("C", C.c_int32), ("h", C.c_int32), ("w", C.c_int32), ("_pad0", C.c_int32), ("ln_eps", C.c_double),
+                ("workspace_bytes", C.c_uint64)]
+
+
+class OlsrClipTrunkParams(C.Structure):
+    """struct olsr_clip_trunk_params, include/olsr_clip_trunk.h."""
+
+    _fields_ = [("depths", C.c_int32 * 4), ("dims", C.c_int32 * 4), ("embed_dim", C.c_int32), ("H", C.c_int32),
+                ("W", C.c_int32), ("R", C.c_int32), ("mean", C.c_float * 3), ("std", C.c_float * 3), ("_pad0", C.c_int32),
+                ("_pad1", C.c_int32), ("ln_eps", C.c_double), ("launches", C.c_uint64 * 2), ("workspace_bytes", C.c_uint64)]
+
+
+def clip_block_state(prefix, c):
+    """((state_dict name, shape), ...) of one ConvNeXt block of c channels, in the packed order."""
+    return ((f"{prefix}.conv_dw.weight", (c, 1, 7, 7)), (f"{prefix}.conv_dw.bias", (c,)), (f"{prefix}.norm.weight", (c,)),
+            (f"{prefix}.norm.bias", (c,)), (f"{prefix}.mlp.fc1.weight", (4 * c, c)), (f"{prefix}.mlp.fc1.bias", (4 * c,)),
+            (f"{prefix}.mlp.fc2.weight", (c, 4 * c)), (f"{prefix}.mlp.fc2.bias", (c,)), (f"{prefix}.gamma", (c,)))
+
+
+def clip_trunk_state(depths, dims, embed_dim, root="visual."):
+    """((state_dict name, shape), ...) of the tower in the packed order: the names of open_clip's TimmModel around timm's
+    ConvNeXt, restated from memory (timm is not a dependency and no checkpoint was at hand: unverified)."""
+    t = root + "trunk."
+    out = [(t + "stem.0.weight", (dims[0], 3, 4, 4)), (t + "stem.0.bias", (dims[0],)), (t + "stem.1.weight", (dims[0],)),
+           (t + "stem.1.bias", (dims[0],))]
+    for i in range(4):
+        s = f"{t}stages.{i}."
+        if i > 0:
+            out += [(s + "downsample.0.weight", (dims[i - 1],)), (s + "downsample.0.bias", (dims[i - 1],)),
+                    (s + "downsample.1.weight", (dims[i], dims[i - 1], 2, 2)), (s + "downsample.1.bias", (dims[i],))]
+        for j in range(depths[i]):
+            out += clip_block_state(f"{s}blocks.{j}", dims[i])
+    out += [(t + "head.norm.weight", (dims[3],)), (t + "head.norm.bias", (dims[3],)),
+            (root + "head.proj.weight", (embed_dim, dims[3]))]
+    return tuple(out)
+
+
 # point-cloud metrics (OLSR_CLOUD_*)
 CLOUD_MAX_SEGMENTS = 32767
 

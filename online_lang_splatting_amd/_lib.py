@@ -1,5 +1,5 @@
-"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h, include/olsr_single_stage.h, include/olsr_frame_ingest.h and
-include/olsr_map_io.h) and declares its prototypes.
+"""Loads libolsr.so (the HIP kernels + C-ABI of include/olsr.h, include/olsr_single_stage.h, include/olsr_frame_ingest.h,
+include/olsr_map_io.h and include/olsr_clip_trunk.h) and declares its prototypes.
 
 There is no fallback: if the library is missing or a symbol is absent this raises, loudly.
 """
@@ -28,6 +28,10 @@ EXPORTS_FRAME_INGEST = ("olsr_frame_ingest",)
 # every symbol include/olsr_map_io.h declares (the same library)
 EXPORTS_MAP_IO = ("olsr_map_ply_width", "olsr_map_ply_pack", "olsr_map_ply_unpack")
 
+# every symbol include/olsr_clip_trunk.h declares (the same library)
+EXPORTS_CLIP_TRUNK = ("olsr_convnext_block_workspace_bytes", "olsr_convnext_block", "olsr_clip_trunk_workspace_bytes",
+                      "olsr_clip_trunk_packed_floats", "olsr_clip_trunk_launches", "olsr_clip_trunk_forward")
+
 _lib = None
 
 
@@ -46,7 +50,7 @@ def lib():
             f"{LIB_PATH} is missing: build it with `python -m online_lang_splatting_amd.build` "
             "(hipcc, gfx950).  There is no CPU or PyTorch fallback for the rasterizer.")
     L = C.CDLL(LIB_PATH)
-    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE + EXPORTS_FRAME_INGEST + EXPORTS_MAP_IO if not hasattr(L, s)]
+    missing = [s for s in EXPORTS + EXPORTS_SINGLE_STAGE + EXPORTS_FRAME_INGEST + EXPORTS_MAP_IO + EXPORTS_CLIP_TRUNK if not hasattr(L, s)]
     if missing:
         raise ImportError(f"{LIB_PATH} lacks symbols {missing}; rebuild it")
     vp, i32, i64, sz = C.c_void_p, C.c_int32, C.c_int64, C.c_size_t
@@ -158,6 +162,13 @@ def lib():
     L.olsr_map_ply_width.argtypes, L.olsr_map_ply_width.restype = [i32, i32], C.c_int
     L.olsr_map_ply_pack.argtypes, L.olsr_map_ply_pack.restype = [i32, i32, i32, mb, vp, vp], C.c_int
     L.olsr_map_ply_unpack.argtypes, L.olsr_map_ply_unpack.restype = [i32, i32, i32, i32, C.POINTER(i32), vp, mb, vp], C.c_int
+    L.olsr_convnext_block_workspace_bytes.argtypes, L.olsr_convnext_block_workspace_bytes.restype = [i32, i32, i32], sz
+    L.olsr_convnext_block.argtypes, L.olsr_convnext_block.restype = [C.POINTER(_abi.OlsrConvnextBlockParams)] + [vp] * 5, C.c_int
+    tp = C.POINTER(_abi.OlsrClipTrunkParams)
+    L.olsr_clip_trunk_workspace_bytes.argtypes, L.olsr_clip_trunk_workspace_bytes.restype = [tp], sz
+    L.olsr_clip_trunk_packed_floats.argtypes, L.olsr_clip_trunk_packed_floats.restype = [tp], sz
+    L.olsr_clip_trunk_launches.argtypes, L.olsr_clip_trunk_launches.restype = [tp], i32
+    L.olsr_clip_trunk_forward.argtypes, L.olsr_clip_trunk_forward.restype = [tp] + [vp] * 7, C.c_int
     L.olsr_bucket_add.argtypes, L.olsr_bucket_add.restype = [i32, i32] + [vp] * 9, C.c_int
     L.olsr_knn_scratch_bytes.argtypes, L.olsr_knn_scratch_bytes.restype = [i32], sz
     L.olsr_knn_mean_dist2.argtypes, L.olsr_knn_mean_dist2.restype = [i32, vp, vp, vp, vp], C.c_int

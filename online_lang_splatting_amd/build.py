@@ -42,6 +42,7 @@ UNITS = [
     ("k_lang_query.hip", "k_lang_query.o", []),
     ("k_lang_encoder.hip", "k_lang_encoder.o", []),
     ("k_hr_net.hip", "k_hr_net.o", []),
+    ("k_clip_trunk.hip", "k_clip_trunk.o", []),
     ("k_knn.hip", "k_knn.o", []),
     ("k_adam.hip", "k_adam.o", []),
     ("k_map_edit.hip", "k_map_edit.o", []),
@@ -56,7 +57,7 @@ UNITS = [
 ]
 HEADERS = ["olsr_device.h", "olsr_collectives.h", "olsr_select.h", "olsr_dense.h", "olsr_lang_ae_device.h", "olsr_state.h", "olsr_kernels.h", "olsr_loss_device.h", "olsr_host.h", "olsr_mc_table.h", os.path.join("..", "..", "include", "olsr.h"),
            os.path.join("..", "..", "include", "olsr_single_stage.h"), os.path.join("..", "..", "include", "olsr_frame_ingest.h"),
-           os.path.join("..", "..", "include", "olsr_map_io.h")]
+           os.path.join("..", "..", "include", "olsr_map_io.h"), os.path.join("..", "..", "include", "olsr_clip_trunk.h")]
 
 
 def hipcc():

@@ -1,5 +1,5 @@
 // olsr_entries.hip — the C-ABI entries that check their arguments and make one launch: visibility, the Adam steps, the pose
-// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, the map's PLY record, TSDF fusion, point-cloud metrics, the 2-D evaluation's query scoring.
+// step, kNN, the stand-alone losses, gradient accumulation and buckets, the sparse exchange, map edits, keyframe seeding, the front end's frame step, the map's PLY record, the CLIP image tower, TSDF fusion, point-cloud metrics, the 2-D evaluation's query scoring.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -757,6 +757,86 @@ int olsr_map_ply_unpack(int32_t P, int32_t M, int32_t F, int32_t n_cols, const i
   if (!rows || (uintptr_t)rows % 4) return fail(OLSR_ERR_ARG, "map_ply_unpack: rows is required, aligned to 4 bytes");
   launch_map_ply_unpack(P, M, F, n_cols, col, rows, *dst, (hipStream_t)hip_stream);
   return launch_check("map_ply_unpack");
+}
+
+// ---- the CLIP ConvNeXt image tower (include/olsr_clip_trunk.h)
+static const char* convnext_block_sizes_error(int64_t C, int64_t h, int64_t w) {
+  if (C < 64 || C % 64 != 0 || C > OLSR_CLIP_TRUNK_MAX_DIM) return "C must be a multiple of 64 in 64 ... 4096";
+  if (h < 1 || w < 1) return "h and w must be >= 1";
+  if (h > 0x7FFFFFFF / w || h * w > 0x7FFFFFFF / (4 * C)) return "4 C h w must stay below 2^31";
+  return nullptr;
+}
+
+size_t olsr_convnext_block_workspace_bytes(int32_t C, int32_t h, int32_t w) {
+  return convnext_block_sizes_error(C, h, w) ? 0 : convnext_block_workspace_bytes(C, h, w);
+}
+
+int olsr_convnext_block(const olsr_convnext_block_params* p, const float* x, const float* block_params, float* y,
+                        void* workspace, void* hip_stream) {
+  if (!p) return fail(OLSR_ERR_ARG, "convnext_block: the parameter struct is NULL");
+  if (const char* e = convnext_block_sizes_error(p->C, p->h, p->w)) return fail(OLSR_ERR_ARG, std::string("convnext_block: ") + e);
+  if (!(p->ln_eps > 0.0) || !std::isfinite(p->ln_eps)) return fail(OLSR_ERR_ARG, "convnext_block: ln_eps must be positive");
+  if (!x || !block_params || !y || !workspace)
+    return fail(OLSR_ERR_ARG, "convnext_block: x, block_params, y and workspace are required");
+  if ((uintptr_t)block_params % 16 || (uintptr_t)workspace % 16 || (uintptr_t)x % 4 || (uintptr_t)y % 4)
+    return fail(OLSR_ERR_ARG, "convnext_block: block_params and workspace must be 16-byte aligned, x and y 4-byte aligned");
+  if (p->workspace_bytes < (uint64_t)convnext_block_workspace_bytes(p->C, p->h, p->w))
+    return fail(OLSR_ERR_ARG, "convnext_block: the workspace is smaller than olsr_convnext_block_workspace_bytes");
+  return launch_check("convnext_block",
+                      launch_convnext_block(*p, x, block_params, y, (float*)workspace, (hipStream_t)hip_stream));
+}
+
+// what is wrong with a tower's configuration, if anything (launches, ln_eps and the workspace are the forward's own checks)
+static const char* clip_trunk_config_error(const olsr_clip_trunk_params* p) {
+  if (!p) return "the parameter struct is NULL";
+  for (int i = 0; i < 4; ++i) {
+    if (p->dims[i] < 64 || p->dims[i] % 64 != 0 || p->dims[i] > OLSR_CLIP_TRUNK_MAX_DIM)
+      return "every dim must be a multiple of 64 in 64 ... 4096";
+    if (p->depths[i] < 1 || p->depths[i] > OLSR_CLIP_TRUNK_MAX_LAUNCHES) return "every depth must lie in 1 ... 128";
+  }
+  if (p->embed_dim < 16 || p->embed_dim % 16 != 0 || p->embed_dim > OLSR_CLIP_TRUNK_MAX_DIM)
+    return "embed_dim must be a multiple of 16 in 16 ... 4096";
+  if (p->R < 32 || p->R % 32 != 0 || p->R > 4096) return "R must be a multiple of 32 in 32 ... 4096";
+  if (p->H < 1 || p->W < 1 || (int64_t)p->H * p->W > (int64_t)0x7FFFFFFF / 3) return "H, W must be >= 1 and 3 H W below 2^31";
+  if (clip_trunk_launches(*p) > OLSR_CLIP_TRUNK_MAX_LAUNCHES) return "the depths need more launches than the mask holds";
+  for (int i = 0; i < 4; ++i) {
+    const int64_t side = p->R >> (2 + i);
+    if (side * side > (int64_t)0x7FFFFFFF / (4 * (int64_t)p->dims[i])) return "a stage's hidden map must stay below 2^31 elements";
+  }
+  for (int c = 0; c < 3; ++c)
+    if (!std::isfinite(p->mean[c]) || !std::isfinite(p->std[c]) || p->std[c] == 0.0f) return "mean must be finite, std finite and not 0";
+  return nullptr;
+}
+
+size_t olsr_clip_trunk_workspace_bytes(const olsr_clip_trunk_params* p) {
+  return clip_trunk_config_error(p) ? 0 : clip_trunk_workspace_bytes(*p);
+}
+
+size_t olsr_clip_trunk_packed_floats(const olsr_clip_trunk_params* p) {
+  return clip_trunk_config_error(p) ? 0 : (size_t)clip_trunk_packed_floats(*p);
+}
+
+int32_t olsr_clip_trunk_launches(const olsr_clip_trunk_params* p) {
+  return clip_trunk_config_error(p) ? 0 : (int32_t)clip_trunk_launches(*p);
+}
+
+int olsr_clip_trunk_forward(const olsr_clip_trunk_params* p, const float* image, const float* packed_params, float* res2,
+                            float* res3, float* clip_vis_dense, void* workspace, void* hip_stream) {
+  if (const char* e = clip_trunk_config_error(p)) return fail(OLSR_ERR_ARG, std::string("clip_trunk_forward: ") + e);
+  if (!(p->ln_eps > 0.0) || !std::isfinite(p->ln_eps)) return fail(OLSR_ERR_ARG, "clip_trunk_forward: ln_eps must be positive");
+  const int n = (int)clip_trunk_launches(*p);
+  for (int k = n; k < OLSR_CLIP_TRUNK_MAX_LAUNCHES; ++k)
+    if ((p->launches[k >> 6] >> (k & 63)) & 1u) return fail(OLSR_ERR_ARG, "clip_trunk_forward: launches names a launch that does not exist");
+  if (!image || !packed_params || !res2 || !res3 || !clip_vis_dense || !workspace)
+    return fail(OLSR_ERR_ARG, "clip_trunk_forward: image, packed_params, res2, res3, clip_vis_dense and workspace are required");
+  if ((uintptr_t)packed_params % 16 || (uintptr_t)workspace % 16)
+    return fail(OLSR_ERR_ARG, "clip_trunk_forward: packed_params and workspace must be 16-byte aligned");
+  if ((uintptr_t)image % 4 || (uintptr_t)res2 % 4 || (uintptr_t)res3 % 4 || (uintptr_t)clip_vis_dense % 4)
+    return fail(OLSR_ERR_ARG, "clip_trunk_forward: image, res2, res3 and clip_vis_dense must be 4-byte aligned");
+  if (p->workspace_bytes < (uint64_t)clip_trunk_workspace_bytes(*p))
+    return fail(OLSR_ERR_ARG, "clip_trunk_forward: the workspace is smaller than olsr_clip_trunk_workspace_bytes");
+  return launch_check("clip_trunk_forward", launch_clip_trunk(*p, image, packed_params, res2, res3, clip_vis_dense,
+                                                              (float*)workspace, (hipStream_t)hip_stream));
 }
 
 // what is wrong with a TSDF volume, if anything (surface: the extraction's tighter size limit)

@@ -7,6 +7,7 @@
 #include "../../include/olsr_single_stage.h"
 #include "../../include/olsr_frame_ingest.h"
 #include "../../include/olsr_map_io.h"
+#include "../../include/olsr_clip_trunk.h"
 #include "olsr_state.h"
 
 namespace olsr {
@@ -330,6 +331,17 @@ hipError_t launch_ss_query_sims(const olsr_lang_query_params& p, const float* co
 size_t hr_net_workspace_bytes(long long h, long long w);
 void launch_hr_net(const olsr_hr_net_params& p, const float* fv, const float* f3, const float* f2, const float* packed,
                    float* workspace, float* out, hipStream_t st);
+
+// k_clip_trunk.hip: the CLIP ConvNeXt image tower ahead of the HR net (include/olsr_clip_trunk.h).  The sizes are what the
+// entries checked; a returned error is the LDS attribute call's of a fused block.
+size_t convnext_block_workspace_bytes(long long C, long long h, long long w);
+long long clip_trunk_packed_floats(const olsr_clip_trunk_params& p);
+long long clip_trunk_launches(const olsr_clip_trunk_params& p);
+size_t clip_trunk_workspace_bytes(const olsr_clip_trunk_params& p);
+hipError_t launch_convnext_block(const olsr_convnext_block_params& p, const float* x, const float* block_params, float* y,
+                                 float* workspace, hipStream_t st);
+hipError_t launch_clip_trunk(const olsr_clip_trunk_params& p, const float* image, const float* packed, float* res2, float* res3,
+                             float* clip_vis_dense, float* workspace, hipStream_t st);
 
 // k_tsdf.hip: TSDF fusion of depth and feature images, and the volume's surface as a point cloud and as a mesh (include/olsr.h)
 void launch_tsdf_init(const olsr_tsdf_volume& vol, hipStream_t st);
