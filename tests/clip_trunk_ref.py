@@ -7,6 +7,8 @@ what scripts/bench_clip_trunk.py times.
   forward(state, image, dtype, ...)  normalise, resize, stem, stages, dense head (open_clip timm_model.py:125-146)
   trunk_state / block_state          drawn parameters that keep the activations O(1) through 36 blocks
   *_kernel_order                     the same in float32 with every sum in the kernels' order (CPU only, small sizes)
+  TRUNK_CASES / BLOCK_CASES          the cases beyond one pixel tile and one neuron tile, each with a note of what it resolves;
+  trunk_case_refs / block_case_refs  their references, computed once per process
 
 State-dict names: _abi.clip_trunk_state (open_clip's around timm's ConvNeXt, unverified); a block's own entries carry the
 names behind `blocks.j.`: conv_dw, norm, mlp.fc1, mlp.fc2, gamma.
@@ -25,6 +27,44 @@ MEAN, STD = _abi.CLIP_PIXEL_MEAN, _abi.CLIP_PIXEL_STD
 SMALL = dict(depths=(1, 1, 2, 1), dims=(64, 128, 256, 512), embed_dim=64, resolution=32)
 GOLDEN_CASES = {"c64_5x7": (64, 5, 7, 1), "c64_1x1": (64, 1, 1, 2), "c192_5x7": (192, 5, 7, 3), "c192_1x1": (192, 1, 1, 4)}
 BLOCK_KEYS = tuple(k[2:] for k, _ in _abi.clip_block_state("b", 1))   # conv_dw.weight ... gamma
+
+# ---- the cases beyond one 64-pixel tile and one 64-neuron tile (tests/test_gpu_clip_trunk_tiles.py) ---------------------------
+# Every launch tiles its work over 64 pixels x 64 neurons; the cases above stay inside tile 0 of both.  A case's note says what
+# it is there to resolve and names the mutants of tests/test_clip_trunk_ref_golden.py that it must tell from the truth.
+MUTANTS = ("pixel-tile blind", "neuron-tile blind", "second output dropped")
+_TILES = dict(depths=(1, 1, 2, 1), dims=(64, 128, 256, 512))
+_SMALL = dict(depths=SMALL["depths"], dims=SMALL["dims"], embed_dim=SMALL["embed_dim"], resolution=SMALL["resolution"])
+TRUNK_CASES = {
+    "wide": dict(depths=(1, 1, 2, 1), dims=(192, 384, 768, 1536), embed_dim=48, resolution=64, image=(50, 75), state_seed=11,
+                 image_seed=11,
+                 note="real widths; stem 16x16 = 4 pixel tiles (pixel-tile blind); res3 from a three-launch block that writes "
+                      "both outputs (second output dropped); downsample to 1536; head over 1536 with a partial neuron tile "
+                      "(neuron-tile blind); up- and downsampling in one call"),
+    "tiles96": dict(_TILES, embed_dim=80, resolution=96, image=(96, 131), state_seed=12, image_seed=12,
+                    note="24x24 = 9 tiles, 12x12 = 2 1/4 tiles (pixel-tile blind); head on 3x3 with two neuron tiles, the "
+                         "second partial (neuron-tile blind); H = R"),
+    "tiles64": dict(_TILES, embed_dim=16, resolution=64, image=(77, 64), state_seed=13, image_seed=13,
+                    note="16x16 = 4 tiles (pixel-tile blind); W = R; E = 16, three waves of the head without neurons "
+                         "(neuron-tile blind)"),
+    "same_size": dict(_SMALL, image=(32, 32), state_seed=1, image_seed=15, note="H = W = R: torch copies, the kernel samples "
+                                                                               "with lambda = 0"),
+    "one_row": dict(_SMALL, image=(1, 3), state_seed=1, image_seed=16, note="a one-row image: y0 = y1 = 0 everywhere"),
+    "deep": dict(depths=(1, 1, 30, 1), dims=(64, 64, 64, 64), embed_dim=16, resolution=32, image=(32, 32), state_seed=14,
+                 image_seed=14, note="72 launches: the mask's second word; E = 16 (neuron-tile blind)"),
+}
+# the trunk cases the suite compared before these: the small trunk at R = 32, state and image seed 1
+OLD_TRUNK_CASES = {f"small_{h}x{w}": dict(_SMALL, image=(h, w), state_seed=1, image_seed=1, note="") for h, w in ((20, 27), (45, 61))}
+# block_state(c, c) on make_map(c, h, w, c + h), as test_block_widths draws them.  64, 128, 256: the fused kernel's NT = 1, 2, 4
+# (256 is OLSR_CLIP_TRUNK_FUSED_MAX_C); 320: the first three-launch width, 5 partial sums of 64 k, OUT = 1280.
+BLOCK_CASES = {f"c{c}_{h}x{w}": dict(c=c, h=h, w=w, note=note + " (pixel-tile blind)")
+               for c in (64, 128, 256, 320)
+               for h, w, note in ((9, 12, "two tiles, w a multiple of 4"),
+                                  (11, 13, "three tiles, w = 1 mod 4, pixels with a full 7x7 window"))}
+_CASE_REFS = {}
+
+
+def trunk_config(case):
+    return {k: case[k] for k in ("depths", "dims", "embed_dim", "resolution")}
 
 
 def golden():
@@ -121,8 +161,9 @@ def normalised(image, dtype):
     return (image.to(dtype) * 255.0 - m) / s
 
 
-def forward(state, image, dtype, depths, dims, embed_dim, resolution, eps=EPS):
-    """image [3,H,W] in [0, 1] -> {"clip_vis_dense" [E,R/32,R/32], "res3", "res2"} in `dtype` (on the image's device)."""
+def forward(state, image, dtype, depths, dims, embed_dim, resolution, eps=EPS, last_inputs=None):
+    """image [3,H,W] in [0, 1] -> {"clip_vis_dense" [E,R/32,R/32], "res3", "res2"} in `dtype` (on the image's device).
+    last_inputs: a list to which the input of each stage's last block is appended ([d_i,h,w])."""
     R, t = resolution, "visual.trunk."
     with torch.no_grad():
         s = {k: v.to(dtype) for k, v in state.items()}
@@ -135,6 +176,8 @@ def forward(state, image, dtype, depths, dims, embed_dim, resolution, eps=EPS):
                 x = _ln2d(x, s[p + "downsample.0.weight"], s[p + "downsample.0.bias"], eps)
                 x = F.conv2d(x, s[p + "downsample.1.weight"], s[p + "downsample.1.bias"], stride=2)
             for j in range(depths[i]):
+                if last_inputs is not None and j + 1 == depths[i]:
+                    last_inputs.append(x[0])
                 x = _block(s, f"{p}blocks.{j}.", x, eps)
             outs.append(x)
         h = F.layer_norm(x.permute(0, 2, 3, 1), (dims[3],), s[t + "head.norm.weight"], s[t + "head.norm.bias"], eps)
@@ -242,3 +285,32 @@ def forward_kernel_order(state, image, depths, dims, embed_dim, resolution, eps=
         h = _ln_ko(x.reshape(n * n, dims[3]), s[t + "head.norm.weight"], s[t + "head.norm.bias"], eps)
         fv = _dense_ko(h, s["visual.head.proj.weight"], None).reshape(n, n, embed_dim).permute(2, 0, 1)
         return {"clip_vis_dense": fv, "res3": outs[1], "res2": outs[0]}
+
+
+# ---- the cases' references, computed once and shared by the CPU and the GPU tests -------------------------------------------------
+def trunk_case_state(case):
+    """The case's drawn state (the wide one is 32 M floats: a second on the CPU), once per seed and configuration."""
+    key = ("state", case["state_seed"], case["depths"], case["dims"], case["embed_dim"])
+    if key not in _CASE_REFS:
+        _CASE_REFS[key] = trunk_state(case["state_seed"], case["depths"], case["dims"], case["embed_dim"])
+    return _CASE_REFS[key]
+
+
+def trunk_case_refs(name):
+    """(image, truth, ref32, stage 1's last block's input in float32) of a TRUNK_CASES / OLD_TRUNK_CASES entry."""
+    key = ("trunk", name)
+    if key not in _CASE_REFS:
+        case = TRUNK_CASES[name] if name in TRUNK_CASES else OLD_TRUNK_CASES[name]
+        st, img, kw, ins = trunk_case_state(case), make_image(*case["image"], case["image_seed"]), trunk_config(case), []
+        _CASE_REFS[key] = (img, forward(st, img, torch.float64, **kw), forward(st, img, torch.float32, last_inputs=ins, **kw), ins[1])
+    return _CASE_REFS[key]
+
+
+def block_case_refs(name):
+    """(state, x, truth, ref32) of a BLOCK_CASES entry."""
+    key = ("block", name)
+    if key not in _CASE_REFS:
+        c, h, w = (BLOCK_CASES[name][k] for k in ("c", "h", "w"))
+        st, x = block_state(c, c), make_map(c, h, w, c + h)
+        _CASE_REFS[key] = (st, x, block(st, x, torch.float64), block(st, x, torch.float32))
+    return _CASE_REFS[key]

@@ -16,6 +16,21 @@
     protocol asks, the kernels' order was changed, not the rule: a dense layer now sums each 64 k from zero and adds the
     partial sums to the running sum (include/olsr_clip_trunk.h, ARITHMETIC), and LayerNorm's sums are in double.  The
     figures are printed and asserted below 2.
+  - the same two conditions for the cases beyond one pixel tile and one neuron tile (clip_trunk_ref.TRUNK_CASES, BLOCK_CASES;
+    tests/test_gpu_clip_trunk_tiles.py): max|truth| is 1.9 - 5.8, and kernel order against ref32 measured
+        wide      clip_vis_dense 0.43 0.43   res3 0.35 0.43   res2 0.91 0.93
+        tiles96   clip_vis_dense 1.03 1.01   res3 0.99 1.01   res2 1.00 1.01
+        tiles64   clip_vis_dense 0.61 0.69   res3 0.42 0.65   res2 0.73 0.93
+        same_size clip_vis_dense 1.00 1.04   res3 0.51 0.65   res2 1.41 0.92
+        one_row   clip_vis_dense 0.93 0.82   res3 0.57 0.70   res2 0.73 0.90
+        deep      clip_vis_dense 1.08 0.95   res3 0.47 0.65   res2 1.12 0.94
+        block 64  9x12 0.71 0.84  11x13 0.65 0.86     block 128  9x12 0.73 0.80  11x13 0.84 0.81
+        block 256 9x12 1.00 0.75  11x13 0.99 0.79     block 320  9x12 0.76 0.69  11x13 0.73 0.69
+    (about 4 s, 3 of them the wide case).
+  - what those cases are for: three "tile-blind" mutants of the float32 reference output (a kernel that ignores its pixel
+    tile, one that ignores its neuron tile or never writes a partial one, a three-launch block that loses its channel-major
+    output) are the unmutated bits on every trunk case the suite compared before, and fail the GPU tests' rule on every new
+    case whose note names them.
 """
 import pytest
 import torch
@@ -92,6 +107,11 @@ def test_every_compared_case_has_an_order_one_truth():
     for j in range(27):
         x = R.block(st, x, torch.float64, prefix=f"visual.trunk.stages.0.blocks.{j}.")
     _scale_ok("27 blocks at C = 64", x)
+    for name in R.TRUNK_CASES:
+        for k, v in R.trunk_case_refs(name)[1].items():
+            _scale_ok(f"{name} {k}", v)
+    for name in R.BLOCK_CASES:
+        _scale_ok(f"block {name}", R.block_case_refs(name)[2])
 
 
 def _ratios(label, ko, t64, t32):
@@ -113,3 +133,75 @@ def test_kernel_order_stays_within_twice_the_float32_reference():
     for k in ko:
         assert ko[k].shape == t64[k].shape
         _ratios(f"small trunk {k}", ko[k], t64[k], t32[k])
+    for name, case in R.TRUNK_CASES.items():
+        img, t64, t32, _ = R.trunk_case_refs(name)
+        ko = R.forward_kernel_order(R.trunk_case_state(case), img, **R.trunk_config(case))
+        for k in ko:
+            assert ko[k].shape == t64[k].shape
+            _ratios(f"{name} {k}", ko[k], t64[k], t32[k])
+    for name in R.BLOCK_CASES:
+        state, x, t64, t32 = R.block_case_refs(name)
+        _ratios(f"block {name}", R.block_kernel_order(state, x), t64, t32)
+
+
+# ---- resolving power: what the cases beyond one tile are there for ----------------------------------------------------------------
+def _mutant(mutant, case, out32, stage1_in):
+    """A "tile-blind" kernel's outputs: the float32 reference's (ordinary float32 noise) with the planted error."""
+    out = {k: v.clone() for k, v in out32.items()}
+    if mutant == "pixel-tile blind":          # P0 = 0 in every tile: pixel p (row-major) holds what pixel p mod 64 should
+        for k, v in out.items():
+            c, h, w = v.shape
+            if h * w > 64:
+                out[k] = v.reshape(c, h * w)[:, torch.arange(h * w) % 64].reshape(c, h, w)
+    elif mutant == "neuron-tile blind":       # blockIdx.y = 0 in every tile, and a partial last tile never written
+        v = out["clip_vis_dense"]
+        full = 64 * (v.shape[0] // 64)
+        if v.shape[0] > 64:
+            v[:full] = v[torch.arange(full) % 64]
+        v[full:] = 0.0
+    elif mutant == "second output dropped":   # a three-launch block whose out_chw write is lost: res3 keeps the stage's input
+        if case["dims"][1] > _abi.CLIP_TRUNK_FUSED_MAX_C:
+            out["res3"] = stage1_in.clone()
+    else:
+        raise KeyError(mutant)
+    return out
+
+
+def _passes(label, got, t64, t32):
+    from test_gpu_lang_codec import _ratio_rule
+    try:
+        for k in got:
+            _ratio_rule(f"{label} {k}", got[k], t64[k], t32[k])
+    except AssertionError:
+        return False
+    return True
+
+
+@pytest.mark.parametrize("mutant", R.MUTANTS)
+def test_the_new_cases_tell_a_tile_blind_kernel_that_the_old_ones_cannot(mutant):
+    """The gap as a test: on every trunk case the suite compared before (the small trunk at R = 32: maps of 64, 16, 4 and 1
+    pixels, E = 64, fused blocks only) each mutant IS the unmutated output, bit for bit; every new case whose note names the
+    mutant fails the GPU tests' own rule on it."""
+    assert R.MUTANTS == ("pixel-tile blind", "neuron-tile blind", "second output dropped")
+    for name, case in R.OLD_TRUNK_CASES.items():
+        _, t64, t32, s1 = R.trunk_case_refs(name)
+        assert _passes(f"{name} unmutated", t32, t64, t32)
+        for k, v in _mutant(mutant, case, t32, s1).items():
+            assert _bits(v.contiguous(), t32[k]), f"the old case {name} already resolves {mutant} in {k}"
+    caught, named = [], [n for n, c in R.TRUNK_CASES.items() if mutant in c["note"]]
+    assert named, f"no case's note names {mutant}"
+    for name in named:
+        _, t64, t32, s1 = R.trunk_case_refs(name)
+        assert _passes(f"{name} unmutated", t32, t64, t32)
+        if not _passes(f"{name} {mutant}", _mutant(mutant, R.TRUNK_CASES[name], t32, s1), t64, t32):
+            caught.append(name)
+    if mutant == "pixel-tile blind":
+        for name, case in R.BLOCK_CASES.items():
+            assert mutant in case["note"]
+            _, _, t64, t32 = R.block_case_refs(name)
+            named.append(name)
+            if not _passes(f"block {name} {mutant}", _mutant(mutant, None, {"y": t32}, None), {"y": t64}, {"y": t32}):
+                caught.append(name)
+    print(f"{mutant}: caught by {caught}")
+    assert caught, f"no case resolves the mutant {mutant}"
+    assert caught == named, f"{mutant}: named by {named}, caught by {caught}"

@@ -6,7 +6,10 @@ its header's, on tests/extent_harness.py as it is.
 | olsr_convnext_block     | C = 64 and 320 on 5 x 7; C = 64 on 9 x 13               | 35 and 117 pixels: no multiple of the 64-pixel  |
 |                         |                                                         | tile nor of the depthwise kernel's 4; 64: the   |
 |                         |                                                         | fused block, 320: the three-launch block        |
+|                         | C = 256 on 11 x 13                                      | the widest fused block, three tiles (143 pixels)|
 | olsr_clip_trunk_forward | the small trunk (maps 8x8 ... 1x1, E = 48), image 20x27 | E = 48: the head's last neuron tile is partial  |
+|                         | clip_trunk_ref's tiles64 (maps 16x16 ... 2x2, E = 16,   | four pixel tiles in the stem and stage 0; three |
+|                         | R = 64), image 77x64                                    | waves of the head without neurons               |
 
 Each entry runs three ways: plain buffers, guarded buffers (64 KiB of a known byte on either side; every output pre-filled
 with a pattern no input holds), and guarded buffers whose inputs and outputs start 4 bytes past a 256-byte boundary.  The
@@ -61,7 +64,7 @@ def _out(shape, misalign):
     return H.prefill(torch.empty(shape, dtype=F32, device=DEV)) if misalign is None else H.guarded_tensor(shape, F32, misalign)
 
 
-@pytest.mark.parametrize("c,h,w", [(64, 5, 7), (320, 5, 7), (64, 9, 13)])
+@pytest.mark.parametrize("c,h,w", [(64, 5, 7), (320, 5, 7), (64, 9, 13), (256, 11, 13)])
 def test_convnext_block(hip, c, h, w):
     from online_lang_splatting_amd import ClipTrunk
     L = _L()
@@ -92,11 +95,21 @@ def test_convnext_block(hip, c, h, w):
 
 
 def test_clip_trunk_forward(hip):
+    _forward_extents(KW, 32, (20, 27), 7, dict(res2=(64, 8, 8), res3=(128, 4, 4), clip_vis_dense=(48, 1, 1)))
+
+
+def test_clip_trunk_forward_tiles64(hip):
+    case = R.TRUNK_CASES["tiles64"]
+    kw = {k: case[k] for k in ("depths", "dims", "embed_dim")}
+    assert case["embed_dim"] == 16 and case["resolution"] == 64 and case["image"] == (77, 64)
+    _forward_extents(kw, 64, case["image"], case["state_seed"], dict(res2=(64, 16, 16), res3=(128, 8, 8), clip_vis_dense=(16, 2, 2)))
+
+
+def _forward_extents(kw, resolution, hw, seed, shapes):
     from online_lang_splatting_amd import ClipTrunk
     L = _L()
-    trunk = ClipTrunk(DEV, R.trunk_state(7, **KW), resolution=32, **KW)
-    img = R.make_image(20, 27, 7)
-    shapes = dict(res2=(64, 8, 8), res3=(128, 4, 4), clip_vis_dense=(48, 1, 1))
+    trunk = ClipTrunk(DEV, R.trunk_state(seed, **kw), resolution=resolution, **kw)
+    img = R.make_image(*hw, seed)
     nbytes = trunk.workspace().numel()
     flat = trunk.flat.cpu()
     results = []
@@ -106,7 +119,7 @@ def test_clip_trunk_forward(hip):
         outs = {k: _out(s, misalign) for k, s in shapes.items()}
         params = _placed(flat, None if misalign is None else 0)
         work = torch.empty(nbytes, dtype=torch.uint8, device=DEV) if misalign is None else H.guarded(nbytes, 0)
-        p = trunk._params(20, 27, 0, nbytes)
+        p = trunk._params(*hw, 0, nbytes)
         _check_rc(L.olsr_clip_trunk_forward(C.byref(p), x.data_ptr(), params.data_ptr(), outs["res2"].data_ptr(),
                                             outs["res3"].data_ptr(), outs["clip_vis_dense"].data_ptr(), work.data_ptr(), _stream()))
         if misalign is not None:
